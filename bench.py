@@ -26,11 +26,24 @@ Launch: `python bench.py --gpus N` starts N rank processes itself (before any
 GPU call) when WORLD_SIZE is not set; under torch.distributed.run (one process
 per GPU, WORLD_SIZE/RANK/LOCAL_RANK set) it runs as that rank.
 
-Printed (rank 0, one JSON line): metric/value/unit as BASELINE.json, roofline of
-the histogram kernel (algorithmic bytes = the rank's input ASCII bytes + int32
-output) timed with HIP events around that kernel on its own
-stream, and the reference CPU path (its own permutationsCountAll compiled from
-/root/reference into oracle/_ref) on every host core this process may use.
+Printed (rank 0, one JSON line): metric/value/unit as BASELINE.json, ms_per_step
+(wall time of the timed region over its K steps), and the roofline of the
+histogram kernel (algorithmic bytes = the rank's input ASCII bytes + int32
+output) from the HIP events that the timed steps themselves
+record around that kernel.
+
+A plain run sets up, runs one untimed step and the clock settle, the W warm-up
+steps and the K timed steps, and prints the line.  `--full` adds everything that
+takes work of its own: the correctness guard before the warm-up (column sums,
+and a 1 Mbase slice against a host histogram), at N > 1 the all-reduce timed
+alone after the timed region, and the reference CPU path (its own
+permutationsCountAll, compiled by the oracle's Makefile into oracle/_ref) on
+every host core this process may use.
+
+`--dump-outputs DIR` writes what the last timed step computed, the int32 count
+matrix after its all-reduce, as DIR/counts.npy (float64).  The input is a pure
+function of the arguments (seed 0x5EED0000 + k), so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -45,12 +58,20 @@ sys.path.insert(0, os.path.join(REPO, "dna-kmeres-parallel_amd"))
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
 SEED_BASE = 0x5EED0000
+DUMP_MAX_VALUES = 7_000_000  # --dump-outputs: float64 values per file (56 MB, under the 64 MB a dump may take)
+DUMP_SEED = 0x5EEDD0C5
 
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what a plain run leaves out: the correctness guard before the warm-up, the "
+                         "all-reduce timed alone (N > 1), and the reference CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the count matrix of the last timed step to DIR/counts.npy "
+                         "(float64; a fixed seeded sample of a matrix of more than %d values)" % DUMP_MAX_VALUES)
     ap.add_argument("--warmup", type=int, default=14)  # the clocks settle over ~10 launches (after the guard step)
     ap.add_argument("--settle-ms", type=float, default=150.0,
                     help="untimed: histogram launches back to back for this long (wall) after the correctness "
@@ -62,18 +83,23 @@ def parse(argv=None):
     ap.add_argument("--records", type=int, default=10)
     ap.add_argument("--record-len", type=int, default=1_000_000_000, help="bases per record")
     ap.add_argument("--cpu-sample", type=int, default=0,
-                    help="bases per CPU worker for the reference CPU baseline (0 = sized to ~15 s; -1 = skip)")
+                    help="--full: bases per CPU worker for the reference CPU baseline (0 = sized to ~15 s; -1 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core this process may run on")
     ap.add_argument("--pmc", default=os.path.join(REPO, "profiles", "pmc_dense_k8_shards.json"),
                     help="HBM traffic per launch measured by rocprofv3 --pmc, per shard size (see profiles/)")
     ap.add_argument("--pmc-lds", default=os.path.join(REPO, "profiles", "pmc_lds_k8_10gbase.json"),
                     help="LDS-array cycles per window of the k = 8 kernel (rocprofv3 --pmc, see profiles/)")
     ap.add_argument("--allreduce-reps", type=int, default=20,
-                    help="N > 1: all-reduces timed alone after the timed region")
+                    help="--full at N > 1: all-reduces timed alone after the timed region")
     ap.add_argument("--reserve-cus", type=int, default=-1,
                     help="CUs left out of the histogram grid for the overlapped all-reduce, whose RCCL "
                          "channels are capped to match (NCCL_MAX_NCHANNELS); -1 = 4 at N > 1, 0 at N = 1")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -267,6 +293,25 @@ def run_cpu_baseline(args, data, k):
 
 
 # ---------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed, for a comparison between builds
+# ---------------------------------------------------------------------------
+def dump_outputs(path, matrix):
+    """Write the count matrix (int32 [bins, records], what a caller of the step
+    receives) as path/counts.npy in float64, which holds every int32 exactly.  A
+    matrix of more than DUMP_MAX_VALUES entries is sampled: a one-dimensional
+    array of the entries at ascending flat positions drawn once from DUMP_SEED, so
+    every run with the same shape stores the same positions."""
+    import numpy as np
+    import torch
+    out = matrix
+    if matrix.numel() > DUMP_MAX_VALUES:
+        pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, matrix.numel(), size=DUMP_MAX_VALUES))
+        out = matrix.reshape(-1)[torch.from_numpy(pos).to(matrix.device)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "counts.npy"), out.cpu().numpy().astype(np.float64))
+
+
+# ---------------------------------------------------------------------------
 def main():
     argv = sys.argv[1:]
     args = parse(argv)
@@ -351,25 +396,30 @@ def main():
     # ~10 launches of this kernel (profiles/r01_kernel_launches.json): the driver's
     # kernel time then included the ramp (BENCH_r05 2.126 ms, against 2.05-2.07 ms
     # with 14 warm-up steps).
+    # A plain run keeps the guard's one untimed step (not one of the W) and leaves
+    # its checks to --full.
     s_lo = win_lo - base
     s_len = min(1 << 20, L - (win_lo % (L + 1)), max(win_hi - win_lo, 0))
-    exp = host_kmer_hist(kmc.synth_host_range(win_lo, win_lo + s_len, L, seed), k) if s_len >= k else None
+    exp = None
+    if args.full and s_len >= k:
+        exp = host_kmer_hist(kmc.synth_host_range(win_lo, win_lo + s_len, L, seed), k)
     last = step(0)
     drain()
     torch.cuda.synchronize()
-    # (1) every window of the synthetic input is valid: after the all-reduce each
-    # record's column sums to L-k+1; (2) bins, not only totals: a 1 Mbase slice of
-    # this rank's bytes counted as a record of its own equals a numpy histogram of
-    # the same bytes regenerated on the host
-    tot = bufs[last].to(torch.int64).sum(dim=0)
-    if not bool((tot == (L - k + 1)).all()):
-        raise SystemExit("count check failed: column sums %s" % tot[:4].tolist())
-    if exp is not None:
-        sl = torch.zeros(s_len + 16, dtype=torch.uint8, device=dev)
-        sl[:s_len] = data[s_lo:s_lo + s_len]
-        got, _ = kmc.count_dense(sl, torch.tensor([0, s_len + 1], dtype=torch.int64, device=dev), k)
-        if not np.array_equal(got.view(-1).cpu().numpy().astype(np.int64), exp):
-            raise SystemExit("count check failed: a 1 Mbase slice differs from its host histogram")
+    if args.full:
+        # (1) every window of the synthetic input is valid: after the all-reduce each
+        # record's column sums to L-k+1; (2) bins, not only totals: a 1 Mbase slice of
+        # this rank's bytes counted as a record of its own equals a numpy histogram of
+        # the same bytes regenerated on the host
+        tot = bufs[last].to(torch.int64).sum(dim=0)
+        if not bool((tot == (L - k + 1)).all()):
+            raise SystemExit("count check failed: column sums %s" % tot[:4].tolist())
+        if exp is not None:
+            sl = torch.zeros(s_len + 16, dtype=torch.uint8, device=dev)
+            sl[:s_len] = data[s_lo:s_lo + s_len]
+            got, _ = kmc.count_dense(sl, torch.tensor([0, s_len + 1], dtype=torch.int64, device=dev), k)
+            if not np.array_equal(got.view(-1).cpu().numpy().astype(np.int64), exp):
+                raise SystemExit("count check failed: a 1 Mbase slice differs from its host histogram")
     # clock settle (round 6): the guard's host work above idles the GPU, and the clock
     # then ramps over ~10-25 launches of this kernel -- with the driver's --warmup 5
     # the first ~10 timed steps were still ramping (profiles/r06w_bench5.json:
@@ -405,6 +455,8 @@ def main():
     kmc.trace_events(None, None)
     if kmc.lib().kmc_dense_status(local) != 0:  # a k = 8 spill list overflowed (never expected)
         raise SystemExit("count check failed: kmc_dense_status reports a spill overflow")
+    if args.dump_outputs and rank == 0:  # after the all-reduce every rank holds the same matrix
+        dump_outputs(args.dump_outputs, bufs[(args.steps - 1) % nbuf])
     # algorithmic bytes of one histogram launch on this GPU: its ASCII input bytes +
     # the int32 matrix it writes
     alg_bytes = (win_hi - win_lo) + 4 * nb * n_tot
@@ -522,15 +574,16 @@ def lds_floor(path, k, build_id):
 
 def finalize(args, world, rank, backend, data, matrix, L, k, n_tot, win, elapsed, kern_ms, alg_bytes, timer,
              step_ms=None):
-    """Everything after the timed region, at every N: the all-reduce timed alone,
-    the max-over-ranks statistics, the reference CPU path on rank 0, and the JSON
-    line (returned on rank 0, None elsewhere).  tests/test_multi.py runs it with
-    gloo at world 2 on CPU tensors (timer "host")."""
+    """Everything after the timed region, at every N: the max-over-ranks statistics
+    and the JSON line (returned on rank 0, None elsewhere); with --full also the
+    all-reduce timed alone and the reference CPU path on rank 0.
+    tests/test_multi.py runs it with gloo at world 2 on CPU tensors (timer "host")."""
     import torch.distributed as dist
     win_lo, win_hi = win
     nb = 1 << (2 * k)
     dev = matrix.device
-    ar_ms = measure_allreduce(matrix, args.allreduce_reps, timer) if world > 1 else 0.0
+    full = bool(getattr(args, "full", False))
+    ar_ms = measure_allreduce(matrix, args.allreduce_reps, timer) if world > 1 and full else 0.0
     build_id = dense_code_object_id() if timer == "cuda" else None
     traffic = pmc_traffic(args.pmc, k, win_hi - win_lo, build_id)
     achieved_rank = alg_bytes / (kern_ms * 1e-3) / 1e9
@@ -613,13 +666,15 @@ def finalize(args, world, rank, backend, data, matrix, L, k, n_tot, win, elapsed
             "alg_bytes_per_kmer": job_bytes / kmers_per_step,
         },
         "allreduce": {
-            "ms": ar_ms,
+            "ms": ar_ms if full or world == 1 else None,
             "bytes": 4 * nb * n_tot,
-            "how": ("%d synchronous all-reduces (SUM, int32) of a matrix shaped like the count matrix, timed alone "
+            "how": "none (1 GPU)" if world == 1 else
+                   ("%d synchronous all-reduces (SUM, int32) of a matrix shaped like the count matrix, timed alone "
                     "after the timed region with HIP events on the current stream (slowest rank); in the timed "
-                    "steps each all-reduce overlaps the next step's counting" % args.allreduce_reps)
-                   if world > 1 else "none (1 GPU)",
+                    "steps each all-reduce overlaps the next step's counting" % args.allreduce_reps) if full else
+                   "not timed alone (--full does); in the timed steps each all-reduce overlaps the next step's counting",
         },
+        "full": full,
     }
     # the roof that binds k = 8: the LDS array, not HBM
     m = lds_floor(getattr(args, "pmc_lds", None), k, build_id)
@@ -636,14 +691,15 @@ def finalize(args, world, rank, backend, data, matrix, L, k, n_tot, win, elapsed
                        % (m["array_cycles_per_atomic"], 100 * m["conflict_frac"], m["cus"], m["launches"],
                           os.path.relpath(args.pmc_lds, REPO)),
         })
-    if world > 1:
-        dist.barrier()  # every rank's GPU work is done before rank 0 takes the host cores
-    if rank == 0 and args.cpu_sample >= 0:
-        result["cpu_baseline"] = run_cpu_baseline(args, data, k)
     if backend != "nccl":
         result["rehearsal"] = "KMC_BENCH_BACKEND=%s, %d ranks sharing device(s): not a measurement" % (backend, world)
-    if world > 1:
-        dist.barrier()
+    if full and args.cpu_sample >= 0:
+        if world > 1:
+            dist.barrier()  # every rank's GPU work is done before rank 0 takes the host cores
+        if rank == 0:
+            result["cpu_baseline"] = run_cpu_baseline(args, data, k)
+        if world > 1:
+            dist.barrier()
     return result if rank == 0 else None
 
 

@@ -260,10 +260,11 @@ def test_bench_host_histogram_matches_oracle(oracle):
         np.testing.assert_array_equal(bench.host_kmer_hist(b, k), exp[:, 0])
 
 
-def _finalize_worker(rank, world, port, q):
+def _finalize_worker(rank, world, port, full, q):
     """bench.finalize (everything after the timed region) at world 2 with gloo on
-    CPU tensors: the N > 1 line must carry the all-reduce time, the node roofline
-    fraction, the RCCL world size and backend, and the reference CPU path on rank 0."""
+    CPU tensors: the N > 1 line must carry the node roofline fraction, the RCCL
+    world size and backend and, with --full, the all-reduce time and the reference
+    CPU path on rank 0."""
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     repo = os.path.dirname(here)
@@ -278,7 +279,8 @@ def _finalize_worker(rank, world, port, q):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     k, L, records = 8, 200_000, 4
     args = bench.parse(["--gpus", str(world), "--steps", "5", "--cpu-sample", "30000", "--cpu-threads", "2",
-                        "--allreduce-reps", "3", "--k", str(k), "--records", str(records), "--record-len", str(L)])
+                        "--allreduce-reps", "3", "--k", str(k), "--records", str(records), "--record-len", str(L)]
+                       + (["--full"] if full else []))
     plan = bench.rank_plan("strong", world, rank, records, L, k)
     base, hold_hi = plan["hold"]
     data = torch.from_numpy(kmc.synth_host_range(base, hold_hi, L, bench.SEED_BASE + k).copy())
@@ -294,9 +296,10 @@ def _finalize_worker(rank, world, port, q):
 
 
 def test_gloo_world2_bench_line_fields():
-    res = dict(_spawn(_finalize_worker, 2))
+    res = dict(_spawn(_finalize_worker, 2, True))
     assert res[1] is None
     r = res[0]
+    assert r["full"] is True
     assert r["n_gpus"] == 2 and r["config"]["rccl_world"] == 2 and r["config"]["backend"] == "gloo"
     assert "reserved_cus" in r["config"] and "rccl_max_channels" in r["config"]
     # the untimed clock settle is reported beside W (finalize alone ran none)
@@ -315,6 +318,52 @@ def test_gloo_world2_bench_line_fields():
     assert r["allreduce"]["ms"] > 0 and r["allreduce"]["bytes"] == 4 * 65536 * 4
     cb = r["cpu_baseline"]
     assert cb["value"] > 0 and cb["cores"] == 2 and cb["kind"] in ("reference", "port")
+
+
+def test_gloo_world2_plain_bench_line_leaves_the_extras_to_full():
+    """Without --full the line keeps the headline fields and the roofline of the
+    timed steps, and neither times the all-reduce alone nor runs the CPU baseline."""
+    res = dict(_spawn(_finalize_worker, 2, False))
+    assert res[1] is None
+    r = res[0]
+    assert r["full"] is False and "cpu_baseline" not in r and r["allreduce"]["ms"] is None
+    assert r["metric"].startswith("k-mers/sec") and r["unit"] == "k-mers/s" and r["dtype"] == "u8"
+    assert r["higher_is_better"] is True and r["steps"] == 5
+    # max over ranks of the timed region over its steps, and k-mers of the job over that time
+    assert abs(r["ms_per_step"] - 0.02 / 5 * 1e3) < 1e-9
+    assert abs(r["value"] - 4 * (200_000 - 8 + 1) * 5 / 0.02) < 1e-3
+    assert r["roofline"]["kernel_ms"] == 1.5 and r["roofline"]["node_frac"] > 0
+
+
+def test_bench_steps_and_full_options():
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_bench_dump_outputs_is_exact_and_its_sample_is_fixed(tmp_path, monkeypatch):
+    """--dump-outputs: counts.npy holds the int32 matrix exactly as float64; above
+    the size limit it holds the same seeded positions of the matrix on every run."""
+    import torch
+
+    import bench
+    m = torch.arange(-6, 6, dtype=torch.int32).reshape(4, 3) * 178_956_970  # up to the int32 range
+    bench.dump_outputs(str(tmp_path / "a"), m)
+    got = np.load(tmp_path / "a" / "counts.npy")
+    assert got.dtype == np.float64 and got.shape == (4, 3)
+    np.testing.assert_array_equal(got.astype(np.int64), m.numpy().astype(np.int64))
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 1000)
+    big = torch.arange(50_000, dtype=torch.int32).reshape(500, 100)
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    bench.dump_outputs(str(tmp_path / "c"), big + 1)
+    b, c = np.load(tmp_path / "b" / "counts.npy"), np.load(tmp_path / "c" / "counts.npy")
+    assert b.ndim == 1 and 900 < b.size <= 1000 and b.dtype == np.float64
+    assert np.all(np.diff(b) > 0) and b.min() >= 0 and b.max() < 50_000  # ascending positions of the matrix
+    np.testing.assert_array_equal(c, b + 1)  # the same positions in another run
 
 
 def test_multi_refuses_a_record_of_2p31_windows_on_the_host(kmc):
