@@ -39,6 +39,7 @@
 #include "kmc.h"
 #include "kmc_internal.h"
 #include "kmc_stream.h"
+#include "kmc_workspace.h"
 
 namespace kmc {
 // k == 8, HM 3: tiles per wave between two scans that move hot 16-bit halves to
@@ -659,7 +660,6 @@ template <> struct Cfg<7> { static constexpr int R = 1, BLOCK = 512, HM = 0; sta
 template <> struct Cfg<8> { static constexpr int R = 1, BLOCK = 1024, HM = 3; static constexpr bool P16 = true; };
 
 struct DevInfo {
-    int cus = 0;
     int occ[KMC_DENSE_MAX_K + 1][2] = {};  // [k][idx64]
     uint32_t *status_host = nullptr;       // kmc_dense_status flag (host-mapped, allocated on first use)
     uint32_t *status_dev = nullptr;
@@ -684,15 +684,11 @@ std::atomic<uint32_t> g_diag_spill_cap{0};
 
 template <int K, class Idx>
 int grid_size(int device, int &G) {
+    int dev_cus = 0;
+    if (int e = device_cus(device, &dev_cus)) return e;
     std::lock_guard<std::mutex> lk(g_mu);
     if ((int)g_dev.size() <= device) g_dev.resize(device + 1);
     DevInfo &d = g_dev[device];
-    if (d.cus == 0) {
-        int v = 0;
-        hipError_t e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device);
-        if (e != hipSuccess) return (int)e;
-        d.cus = v;
-    }
     const int ix = sizeof(Idx) == 8 ? 1 : 0;
     if (d.occ[K][ix] == 0) {
         const void *kp = kernel_ptr<K, Idx>();
@@ -702,7 +698,7 @@ int grid_size(int device, int &G) {
         d.occ[K][ix] = nb > 0 ? nb : 1;
     }
     // kmc_set_reserved_cus: leave that many CUs to a concurrent kernel
-    const int cus = d.cus - t_reserved_cus;
+    const int cus = dev_cus - t_reserved_cus;
     G = (cus > 0 ? cus : 1) * d.occ[K][ix];
     return 0;
 }
@@ -744,25 +740,24 @@ int take_status(int device) {
     return (int)v;  // the code a kernel stored, KMC_OK if none
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
+// The workspace of a call with G workgroups, carved from `base` (null: only the
+// total means anything)
 struct WsLayout {
-    size_t slot_rec, spill_cnt, slab, spill, total;
+    int64_t *slot_rec;
+    uint32_t *spill_cnt, *slab;
+    Spill *spill;
+    size_t total;
 };
 
-inline WsLayout ws_layout(int k, int G, uint32_t spill_cap) {
-    WsLayout L;
+inline WsLayout ws_layout(void *base, int k, int G, uint32_t spill_cap) {
     const size_t nb = (size_t)1 << (2 * k);
-    size_t o = 0;
-    L.slot_rec = o;
-    o += align256((size_t)G * 2 * sizeof(int64_t));
-    L.spill_cnt = o;
-    o += align256((size_t)G * sizeof(uint32_t));
-    L.slab = o;
-    o += align256((size_t)G * 2 * nb * sizeof(uint32_t));
-    L.spill = o;
-    o += align256((size_t)G * spill_cap * sizeof(Spill));
-    L.total = o;
+    Carver c(base);
+    WsLayout L;
+    L.slot_rec = c.take<int64_t>((size_t)G * 2);
+    L.spill_cnt = c.take<uint32_t>((size_t)G);
+    L.slab = c.take<uint32_t>((size_t)G * 2 * nb);
+    L.spill = c.take<Spill>((size_t)G * spill_cap);
+    L.total = c.total();
     return L;
 }
 
@@ -785,7 +780,7 @@ inline uint32_t spill_cap_for(int64_t tiles_per_wg) {
 struct Plan {
     int G;
     uint32_t spill_cap;
-    WsLayout L;
+    size_t ws_bytes;
 };
 
 template <int K, class Idx>
@@ -807,35 +802,11 @@ int make_plan(int device, bool derive, int64_t wl, int64_t wh, Plan &pl) {
         }
     }
     pl.G = G;
-    pl.L = ws_layout(K, G, pl.spill_cap);
+    pl.ws_bytes = ws_layout(nullptr, K, G, pl.spill_cap).total;
     return 0;
 }
 
-// library-owned workspace, per device
-struct WsCache {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-};
-std::vector<WsCache> g_ws;
-
-int cached_workspace(int device, size_t need, void **out) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if ((int)g_ws.size() <= device) g_ws.resize(device + 1);
-    WsCache &c = g_ws[device];
-    if (c.bytes < need) {
-        if (c.ptr) {
-            hipError_t e = hipFree(c.ptr);
-            if (e != hipSuccess) return (int)e;
-            c.ptr = nullptr;
-            c.bytes = 0;
-        }
-        hipError_t e = hipMalloc(&c.ptr, need);
-        if (e != hipSuccess) return KMC_ERR_NOMEM;
-        c.bytes = need;
-    }
-    *out = c.ptr;
-    return 0;
-}
+DeviceCache g_ws;  // library-owned workspace
 
 struct Request {
     const char *data;        // 16-byte aligned
@@ -876,12 +847,12 @@ int run_dense(const Request &q, hipStream_t st) {
     if (e) return e;
     void *ws = q.ws;
     if (ws == nullptr) {
-        e = cached_workspace(device, pl.L.total, &ws);
+        e = g_ws.get(device, pl.ws_bytes, &ws);
         if (e) return e;
-    } else if (q.ws_bytes < pl.L.total) {
+    } else if (q.ws_bytes < pl.ws_bytes) {
         return KMC_ERR_WORKSPACE;
     }
-    char *base = static_cast<char *>(ws);
+    const WsLayout L = ws_layout(ws, K, pl.G, pl.spill_cap);
     Params p;
     p.data = q.data;
     p.indices = q.indices;
@@ -896,10 +867,10 @@ int run_dense(const Request &q, hipStream_t st) {
     p.rh = rh;
     p.derive = derive ? 1 : 0;
     p.G = pl.G;
-    p.slot_rec = reinterpret_cast<int64_t *>(base + pl.L.slot_rec);
-    p.spill_cnt = Cfg<K>::P16 ? reinterpret_cast<uint32_t *>(base + pl.L.spill_cnt) : nullptr;
-    p.slab = reinterpret_cast<uint32_t *>(base + pl.L.slab);
-    p.spill = Cfg<K>::P16 ? reinterpret_cast<Spill *>(base + pl.L.spill) : nullptr;
+    p.slot_rec = L.slot_rec;
+    p.spill_cnt = Cfg<K>::P16 ? L.spill_cnt : nullptr;
+    p.slab = L.slab;
+    p.spill = Cfg<K>::P16 ? L.spill : nullptr;
     p.spill_cap = pl.spill_cap;
     p.status = q.status;
     if (!p.status) {
@@ -975,7 +946,7 @@ size_t workspace_for(int k, int device, bool derive, int64_t wl, int64_t wh) {
         case 8: e = make_plan<8, Idx>(device, derive, wl, wh, pl); break;
         default: return 0;
     }
-    return e ? 0 : pl.L.total;
+    return e ? 0 : pl.ws_bytes;
 }
 
 }  // namespace

@@ -25,10 +25,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <mutex>
-#include <vector>
 
 #include "kmc.h"
+#include "kmc_workspace.h"
 
 namespace kmc {
 namespace {
@@ -215,20 +214,7 @@ inline Plan plan_for(int64_t n, int k, int cus) {
     return P;
 }
 
-std::mutex d_mu;
-std::vector<int> d_cus;
-std::vector<std::pair<void *, size_t>> d_ws;
-
-int cus_of(int device, int &cus) {
-    std::lock_guard<std::mutex> lk(d_mu);
-    if ((int)d_cus.size() <= device) d_cus.resize(device + 1, 0);
-    if (d_cus[device] == 0) {
-        hipError_t e = hipDeviceGetAttribute(&d_cus[device], hipDeviceAttributeMultiprocessorCount, device);
-        if (e != hipSuccess) return (int)e;
-    }
-    cus = d_cus[device];
-    return 0;
-}
+DeviceCache d_ws;  // library-owned scratch (the split sums)
 
 }  // namespace
 }  // namespace kmc
@@ -238,7 +224,7 @@ using namespace kmc;
 extern "C" size_t kmc_pair_distances_workspace_size(uint64_t num_seqs, int k, int device) {
     if (k < 1 || k > KMC_DENSE_MAX_K || num_seqs < 2) return 0;
     int cus = 0;
-    if (cus_of(device, cus)) return 0;
+    if (device_cus(device, &cus)) return 0;
     return plan_for((int64_t)num_seqs, k, cus).ws;
 }
 
@@ -253,7 +239,7 @@ extern "C" int kmc_pair_distances(const int32_t *sum, uint64_t sum_ld, const int
     hipError_t he = hipGetDevice(&device);
     if (he != hipSuccess) return (int)he;
     int cus = 0;
-    int e = cus_of(device, cus);
+    int e = device_cus(device, &cus);
     if (e) return e;
     const int64_t n = (int64_t)num_seqs;
     const Plan P = plan_for(n, k, cus);
@@ -261,16 +247,7 @@ extern "C" int kmc_pair_distances(const int32_t *sum, uint64_t sum_ld, const int
     void *ws = workspace;
     if (P.ws) {
         if (ws == nullptr) {
-            std::lock_guard<std::mutex> lk(d_mu);
-            if ((int)d_ws.size() <= device) d_ws.resize(device + 1, {nullptr, 0});
-            auto &c = d_ws[device];
-            if (c.second < P.ws) {
-                if (c.first && hipFree(c.first) != hipSuccess) return KMC_ERR_NOMEM;
-                c = {nullptr, 0};
-                if (hipMalloc(&c.first, P.ws) != hipSuccess) return KMC_ERR_NOMEM;
-                c.second = P.ws;
-            }
-            ws = c.first;
+            if ((e = d_ws.get(device, P.ws, &ws))) return e;
         } else if (workspace_bytes < P.ws) {
             return KMC_ERR_WORKSPACE;
         }

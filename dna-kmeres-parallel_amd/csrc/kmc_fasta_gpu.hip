@@ -24,12 +24,11 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
-#include <vector>
 
 #include "kmc.h"
 #include "kmc_scan.h"
 #include "kmc_stream.h"
+#include "kmc_workspace.h"
 
 namespace kmc {
 namespace {
@@ -347,32 +346,30 @@ __global__ void fp_finish_kernel(FParams p, int has_tail) {
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-struct FCache {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-};
-std::mutex f_mu;
-std::vector<FCache> f_ws[2];  // [0]: per-tile arrays (sized from the raw bytes), [1]: per-line arrays
+DeviceCache f_ws[2];  // [0]: per-tile arrays (sized from the raw bytes), [1]: per-line arrays
 
-inline size_t fal(size_t x) { return (x + 255) & ~(size_t)255; }
+// The per-tile arrays (and the scan's block sums), then the per-line arrays, bound
+// into p from `base`; the bytes they take (base null: the size only).
+size_t tile_layout(void *base, FParams &p, uint64_t *&bsum) {
+    Carver c(base);
+    p.tile_nl = c.take<uint32_t>(p.ntiles);
+    p.tile_lb = c.take<uint64_t>(p.ntiles + 1);
+    p.tile_keep = c.take<uint32_t>(p.ntiles);
+    p.tile_ob = c.take<uint64_t>(p.ntiles + 1);
+    p.tile_open = c.take<uint32_t>(p.ntiles);
+    p.tile_rb = c.take<uint64_t>(p.ntiles + 1);
+    bsum = c.take<uint64_t>(scan_tiles(p.ntiles) + 1);
+    p.result = c.take<uint64_t>(2);
+    p.lfinal = c.take<uint32_t>(1);
+    return c.total();
+}
 
-int f_workspace(int which, size_t need, char **out) {
-    int device = 0;
-    hipError_t he = hipGetDevice(&device);
-    if (he != hipSuccess) return (int)he;
-    std::lock_guard<std::mutex> lk(f_mu);
-    std::vector<FCache> &v = f_ws[which];
-    if ((int)v.size() <= device) v.resize(device + 1);
-    FCache &c = v[device];
-    if (c.bytes < need) {
-        if (c.ptr && hipFree(c.ptr) != hipSuccess) return KMC_ERR_NOMEM;
-        c.ptr = nullptr;
-        c.bytes = 0;
-        if (hipMalloc(&c.ptr, need) != hipSuccess) return KMC_ERR_NOMEM;
-        c.bytes = need;
-    }
-    *out = static_cast<char *>(c.ptr);
-    return 0;
+size_t line_layout(void *base, FParams &p) {
+    Carver c(base);
+    p.fn = c.take<uint8_t>((size_t)p.nlines);
+    p.act = c.take<uint8_t>((size_t)p.nlines);
+    p.lagg = c.take<uint32_t>((size_t)(p.ltiles + 1));
+    return c.total();
 }
 
 // Parses raw[0, n) into out (capacity >= n + 1 always suffices) and the record
@@ -398,28 +395,13 @@ int parse_device(const char *raw, uint64_t n, int dialect, char *out, uint64_t o
     p.n = (int64_t)n;
     p.dialect = dialect;
     p.ntiles = (int64_t)((n + kFpTile - 1) / kFpTile);
-    size_t o = 0;
-    const size_t o_tnl = o; o += fal(p.ntiles * 4);
-    const size_t o_tlb = o; o += fal((p.ntiles + 1) * 8);
-    const size_t o_tk = o; o += fal(p.ntiles * 4);
-    const size_t o_tob = o; o += fal((p.ntiles + 1) * 8);
-    const size_t o_to = o; o += fal(p.ntiles * 4);
-    const size_t o_trb = o; o += fal((p.ntiles + 1) * 8);
-    const size_t o_bs = o; o += fal((scan_tiles(p.ntiles) + 1) * 8);
-    const size_t o_res = o; o += fal(2 * 8);
-    const size_t o_lfin = o; o += fal(4);
-    char *ws = nullptr;
-    int e = f_workspace(0, o, &ws);
+    int device = 0;
+    if ((he = hipGetDevice(&device))) return (int)he;
+    void *ws = nullptr;
+    uint64_t *bsum = nullptr;
+    int e = f_ws[0].get(device, tile_layout(nullptr, p, bsum), &ws);
     if (e) return e;
-    p.tile_nl = reinterpret_cast<uint32_t *>(ws + o_tnl);
-    p.tile_lb = reinterpret_cast<uint64_t *>(ws + o_tlb);
-    p.tile_keep = reinterpret_cast<uint32_t *>(ws + o_tk);
-    p.tile_ob = reinterpret_cast<uint64_t *>(ws + o_tob);
-    p.tile_open = reinterpret_cast<uint32_t *>(ws + o_to);
-    p.tile_rb = reinterpret_cast<uint64_t *>(ws + o_trb);
-    uint64_t *bsum = reinterpret_cast<uint64_t *>(ws + o_bs);
-    p.result = reinterpret_cast<uint64_t *>(ws + o_res);
-    p.lfinal = reinterpret_cast<uint32_t *>(ws + o_lfin);
+    tile_layout(ws, p, bsum);
     // newlines -> line count
     hipLaunchKernelGGL(fp_count_kernel, dim3((unsigned)p.ntiles), dim3(kFpBlock), 0, st, p);
     excl_scan_u32(p.tile_nl, p.ntiles, bsum, p.tile_lb, st);
@@ -431,14 +413,8 @@ int parse_device(const char *raw, uint64_t n, int dialect, char *out, uint64_t o
     const int has_tail = last != '\n';
     p.nlines = (int64_t)nl + has_tail;
     p.ltiles = (p.nlines + kLsTile - 1) / kLsTile;
-    o = 0;
-    const size_t o_fn = o; o += fal((size_t)p.nlines);
-    const size_t o_act = o; o += fal((size_t)p.nlines);
-    const size_t o_lagg = o; o += fal((size_t)(p.ltiles + 1) * 4);
-    if ((e = f_workspace(1, o, &ws))) return e;
-    p.fn = reinterpret_cast<uint8_t *>(ws + o_fn);
-    p.act = reinterpret_cast<uint8_t *>(ws + o_act);
-    p.lagg = reinterpret_cast<uint32_t *>(ws + o_lagg);
+    if ((e = f_ws[1].get(device, line_layout(nullptr, p), &ws))) return e;
+    line_layout(ws, p);
     // line states -> actions -> kept bytes and records per tile
     hipLaunchKernelGGL(fp_class_kernel, dim3((unsigned)p.ntiles), dim3(kFpBlock), 0, st, p);
     hipLaunchKernelGGL(fp_lscan_reduce_kernel, dim3((unsigned)p.ltiles), dim3(kFpBlock), 0, st, p);

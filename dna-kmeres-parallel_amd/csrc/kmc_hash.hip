@@ -38,6 +38,12 @@
 //               bits, larger ones in a side array)
 // Bytes per window: the input twice (K1, K3a), an 8-byte h written and read twice
 // (K3a -> K3b -> K4), 12 bytes of pairs written, read and written again.
+//
+// Host side (end of the file): kmc_count_canonical_hash_ex is a list of steps --
+// fetch_offsets, canon_plan (geometry), bind_workspace (canon_carve: the one place
+// the workspace layout is written, also behind the size query), upload_plan,
+// run_front (K1 .. K3b), then run_direct or run_placed (K4 and the output), which
+// share read_result for the error word.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -49,6 +55,7 @@
 #include "kmc_internal.h"
 #include "kmc_scan.h"
 #include "kmc_stream.h"
+#include "kmc_workspace.h"
 
 namespace kmc {
 namespace {
@@ -1733,12 +1740,8 @@ __global__ __launch_bounds__(256) void canon_fallback_kernel(HParams p) {
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-struct HCache {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-};
-std::mutex h_mu;
-std::vector<HCache> h_ws;
+DeviceCache h_ws;  // library-owned workspace
+std::mutex h_mu;   // the settings below
 uint32_t h_claim_cap = kClaimW;
 uint32_t h_sort_cap = kSortCap;
 uint32_t h_sort_cap_big = kSortCapBig;
@@ -1754,8 +1757,6 @@ unsigned long long h_fb_defer[3] = {0, 0, 0};  // lists queued: big instance, ta
 // never written by this call); -1: off
 long long h_stale_queue = -1;
 #endif
-
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // K1 / K3a instances by orientation and key width
 struct WalkCount {
@@ -1857,9 +1858,9 @@ extern "C" KMC_DIAG_API int kmc_diag_canon_sort_cap_big(unsigned cap) {
 #endif
 
 namespace {
-// Geometry and workspace layout of one canonical call, from the host copy of the
-// (biased) record offsets: K1 / K3a chunk split, per-record lists / coarse
-// buckets / workgroups, cnt layouts, list ids, K3b workgroups.
+// Geometry of one canonical call, from the host copy of the (biased) record
+// offsets: K1 / K3a chunk split, per-record lists / coarse buckets / workgroups,
+// cnt layouts, list ids, K3b workgroups.
 struct CanonPlan {
     int64_t c_lo = 0, cpw = 1;
     int G = 1;
@@ -1868,8 +1869,6 @@ struct CanonPlan {
     std::vector<int64_t> cbase, ccbase, lbase;
     std::vector<int2> fsplit;
     int64_t M = 0, Mc = 0, L = 0, windows = 0;
-    size_t o_idx, o_lg, o_cb, o_ccb, o_w0, o_nw, o_lb, o_fs, o_cnt, o_off, o_cntc, o_offc, o_bs, o_ent, o_ls, o_pk,
-        o_pc, o_nd, o_do, o_err, o_dn, o_dl, o_bn, o_bl, o_lrec, o_rst, o_rb, o_fq, o_nfq, o_d2n, o_d2l, total;
 };
 
 void canon_plan(const int64_t *hidx, int64_t n, int k, int cus, CanonPlan &P) {
@@ -1914,49 +1913,261 @@ void canon_plan(const int64_t *hidx, int64_t n, int k, int cus, CanonPlan &P) {
     P.Mc = Mc;
     P.L = L;
     P.windows = windows;
-    const int64_t NF = (int64_t)P.fsplit.size();
-    const int64_t cap_w = std::max<int64_t>(windows, 1);
-    size_t o = 0;
-    P.o_idx = o; o += al256((n + 1) * 8);
-    P.o_lg = o; o += al256(n);
-    P.o_cb = o; o += al256((n + 1) * 8);
-    P.o_ccb = o; o += al256((n + 1) * 8);
-    P.o_w0 = o; o += al256(n * 4);
-    P.o_nw = o; o += al256(n * 4);
-    P.o_lb = o; o += al256((n + 1) * 8);
-    P.o_fs = o; o += al256((size_t)std::max<int64_t>(NF, 1) * sizeof(int2));
-    P.o_cnt = o; o += al256((size_t)std::max<int64_t>(M, 1) * 4);
-    P.o_off = o; o += al256((size_t)(M + 1) * 8);
-    P.o_cntc = o; o += al256((size_t)std::max<int64_t>(Mc, 1) * 4);
-    P.o_offc = o; o += al256((size_t)(Mc + 1) * 8);
-    P.o_bs = o; o += al256((size_t)(scan_tiles(std::max<int64_t>(M, L)) + 1) * 8);
-    P.o_ent = o; o += al256((size_t)cap_w * 8);
-    P.o_ls = o; o += al256((size_t)(L + 1) * 8);
-    P.o_pk = o; o += al256((size_t)cap_w * 8);
-    P.o_pc = o; o += al256((size_t)cap_w * 4);
-    P.o_nd = o; o += al256((size_t)L * 4);
-    P.o_do = o; o += al256((size_t)(L + 1) * 8);
-    P.o_err = o; o += al256(4);
-    P.o_dn = o; o += al256(8);
-    P.o_dl = o; o += al256((size_t)std::max<int64_t>(L, 1) * 24);
-    P.o_bn = o; o += al256(8);
-    P.o_bl = o; o += al256((size_t)std::max<int64_t>(L, 1) * 24);
-    // direct output (round 5)
-    P.o_lrec = o; o += al256((size_t)std::max<int64_t>(L, 1) * 4);
-    P.o_rst = o; o += al256((size_t)n * 8);
-    P.o_rb = o; o += al256((size_t)(n + 1) * 8);
-    // (at most two copies per list: its distinct slots' keys and its results; a
-    // list the table kernel counts has one)
-    P.o_fq = o; o += al256((size_t)std::max<int64_t>(L, 1) * 2 * 32);
-    P.o_nfq = o; o += al256(8);
-    P.o_d2n = o; o += al256(8);
-    P.o_d2l = o; o += al256((size_t)std::max<int64_t>(L, 1) * 24);
-    P.total = o;
 }
 
-int device_cus(int device, int *cus) {
-    hipError_t he = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device);
-    return he == hipSuccess ? 0 : (int)he;
+// The workspace of a call with plan P over n records: every array of it carved
+// from `base` into p (and the scans' block sums into bsum); returns its bytes
+// (base null: only those mean anything).  A new array is added here and nowhere else.
+size_t canon_carve(const CanonPlan &P, int64_t n, void *base, HParams &p, uint64_t *&bsum) {
+    const size_t M = (size_t)P.M, Mc = (size_t)P.Mc, L = (size_t)P.L;
+    const size_t M1 = std::max<size_t>(M, 1), Mc1 = std::max<size_t>(Mc, 1), L1 = std::max<size_t>(L, 1);
+    const size_t cap_w = (size_t)std::max<int64_t>(P.windows, 1);
+    Carver c(base);
+    p.idx = c.take<int64_t>(n + 1);
+    p.lg = c.take<uint8_t>(n);
+    p.cbase = c.take<int64_t>(n + 1);
+    p.ccbase = c.take<int64_t>(n + 1);
+    p.w0 = c.take<int32_t>(n);
+    p.nwg = c.take<int32_t>(n);
+    p.lbase = c.take<int64_t>(n + 1);
+    p.fsplit = c.take<int2>(std::max<size_t>(P.fsplit.size(), 1));
+    p.cnt = c.take<uint32_t>(M1);
+    p.off = c.take<uint64_t>(M + 1);
+    p.cnt_c = c.take<uint32_t>(Mc1);
+    p.off_c = c.take<uint64_t>(Mc + 1);
+    bsum = c.take<uint64_t>((size_t)scan_tiles(std::max<int64_t>(P.M, P.L)) + 1);
+    p.ent = c.take<uint64_t>(cap_w);
+    p.list_start = c.take<uint64_t>(L + 1);
+    p.pk = c.take<uint64_t>(cap_w);
+    p.ent_c = p.pk;  // dead before K4 writes the pairs
+    p.pc = c.take<uint32_t>(cap_w);
+    p.ndist = c.take<uint32_t>(L);
+    p.dist_off = c.take<uint64_t>(L + 1);
+    p.err = c.take<uint32_t>(1);
+    p.ndefer = c.take<unsigned long long>(1);
+    p.defer = c.take<uint64_t>(3 * L1);
+    p.nbig = c.take<unsigned long long>(1);
+    p.big = c.take<uint64_t>(3 * L1);
+    // direct output (round 5)
+    p.lrec = c.take<int32_t>(L1);
+    p.rstate = c.take<unsigned long long>(n);
+    p.rbase = c.take<unsigned long long>(n + 1);
+    // (at most two copies per list: its distinct slots' keys and its results; a
+    // list the table kernel counts has one)
+    p.fq = c.take<uint64_t>(2 * 4 * L1);
+    p.nfq = c.take<unsigned long long>(1);
+    p.ndefer2 = c.take<unsigned long long>(1);
+    p.defer2 = c.take<uint64_t>(3 * L1);
+    p.tq = p.defer;  // the table kernel's first launch
+    p.ntq = p.ndefer;
+    return c.total();
+}
+
+// The record offsets on the host, checked, every one moved up by `mis`.
+int fetch_offsets(const int64_t *indices, int64_t n, int64_t mis, hipStream_t stream, std::vector<int64_t> &hidx) {
+    hidx.resize(n + 1);
+    hipError_t he = hipMemcpyAsync(hidx.data(), indices, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he != hipSuccess) return (int)he;
+    for (int64_t r = 0; r < n; ++r)
+        if (hidx[r + 1] < hidx[r]) return KMC_ERR_INVALID_ARG;
+    for (auto &x : hidx) x += mis;
+    return 0;
+}
+
+// The caller's workspace (checked) or the library's, bound into p.
+int bind_workspace(const CanonPlan &P, int64_t n, int device, void *workspace, size_t workspace_bytes, HParams &p,
+                   uint64_t *&bsum) {
+    const size_t total = canon_carve(P, n, nullptr, p, bsum);
+    if (workspace) {
+        if (workspace_bytes < total) return KMC_ERR_WORKSPACE;
+        // the layout's offsets are 256-byte multiples, and K3b / K4s move whole
+        // 16-byte pieces (and LDS-DMA dwords) of it
+        if (reinterpret_cast<uintptr_t>(workspace) & 255u) return KMC_ERR_ALIGNMENT;
+    } else if (int e = h_ws.get(device, total, &workspace)) {
+        return e;
+    }
+    canon_carve(P, n, workspace, p, bsum);
+    return 0;
+}
+
+// The plan's arrays to the device; the error word and the queue counts to 0.
+int upload_plan(const HParams &p, const CanonPlan &P, const std::vector<int64_t> &hidx, hipStream_t stream) {
+    const int64_t n = p.n, NF = (int64_t)P.fsplit.size();
+    hipError_t he;
+    if ((he = hipMemcpyAsync((void *)p.idx, hidx.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream)) ||
+        (he = hipMemcpyAsync((void *)p.lg, P.lg.data(), n, hipMemcpyHostToDevice, stream)) ||
+        (he = hipMemcpyAsync((void *)p.cbase, P.cbase.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream)) ||
+        (he = hipMemcpyAsync((void *)p.ccbase, P.ccbase.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream)) ||
+        (he = hipMemcpyAsync((void *)p.w0, P.w0.data(), n * 4, hipMemcpyHostToDevice, stream)) ||
+        (he = hipMemcpyAsync((void *)p.nwg, P.nwg.data(), n * 4, hipMemcpyHostToDevice, stream)) ||
+        (he = hipMemcpyAsync((void *)p.lbase, P.lbase.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream)) ||
+        (NF && (he = hipMemcpyAsync((void *)p.fsplit, P.fsplit.data(), NF * sizeof(int2), hipMemcpyHostToDevice,
+                                    stream))))
+        return (int)he;
+    if ((he = hipMemsetAsync(p.err, 0, 4, stream)) || (he = hipMemsetAsync(p.ndefer, 0, 8, stream)) ||
+        (he = hipMemsetAsync(p.nbig, 0, 8, stream)) || (he = hipMemsetAsync(p.ndefer2, 0, 8, stream)))
+        return (int)he;
+#ifdef KMC_DIAG_HOOKS
+    {
+        static unsigned long long stale;  // (static: the async copy reads it after this frame)
+        std::lock_guard<std::mutex> lk(h_mu);
+        if (h_stale_queue >= 0) {
+            stale = (unsigned long long)h_stale_queue;
+            if ((he = hipMemcpyAsync(p.ndefer2, &stale, 8, hipMemcpyHostToDevice, stream))) return (int)he;
+        }
+    }
+#endif
+    return 0;
+}
+
+// The front both back ends share: K1, the two scans, K3a, the list starts, K3b.
+int run_front(const HParams &p, const CanonPlan &P, uint64_t *bsum, hipStream_t stream) {
+    const int64_t n = p.n, NF = (int64_t)P.fsplit.size();
+    hipError_t he;
+    if (p.direct)
+        hipLaunchKernelGGL(canon_direct_setup_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, stream, p);
+    if (P.M > 0) {
+        if ((he = hipMemsetAsync(p.cnt, 0, (size_t)P.M * 4, stream)) ||
+            (he = hipMemsetAsync(p.cnt_c, 0, (size_t)P.Mc * 4, stream)))
+            return (int)he;
+        launch_walk<WalkCount>(p, stream);
+    }
+    excl_scan_u32(p.cnt, P.M, bsum, p.off, stream);
+    excl_scan_u32(p.cnt_c, P.Mc, bsum, p.off_c, stream);
+    launch_walk<WalkCoarse>(p, stream);
+    hipLaunchKernelGGL(canon_list_start_kernel, dim3((unsigned)((P.L + 1 + 255) / 256)), dim3(256), 0, stream, p);
+    if (NF > 0) hipLaunchKernelGGL(canon_fine_kernel, dim3((unsigned)NF), dim3(kWalkBlock), 0, stream, p);
+    return 0;
+}
+
+// A grid of `per_cu` workgroups per CU striding over L lists (at most one per list)
+dim3 list_grid(int64_t L, int per_cu, int cus) {
+    return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(L, (int64_t)per_cu * cus)));
+}
+
+// After the last counting kernel: the launch status, the distinct keys (read from
+// `total`) and the call's error word.
+int read_result(const HParams &p, const void *total, hipStream_t stream, uint64_t *distinct) {
+    hipError_t he;
+    uint32_t err = 0;
+    if ((he = hipGetLastError()) || (he = hipMemcpyAsync(distinct, total, 8, hipMemcpyDeviceToHost, stream)) ||
+        (he = hipMemcpyAsync(&err, p.err, 4, hipMemcpyDeviceToHost, stream)) || (he = hipStreamSynchronize(stream)))
+        return (int)he;
+    if (err & kErrBound) return KMC_ERR_INTERNAL;
+    if (err) return KMC_ERR_INVALID_ARG;  // a record far beyond any genome (see kMaxPasses)
+    return 0;
+}
+
+#ifdef KMC_DIAG_HOOKS
+// What kmc_diag_canon_fallback(_detail) report of a direct-output call: its fallback
+// copies in all and per record, and the lists each queue took.
+int diag_read_back(const HParams &p) {
+    hipError_t he;
+    unsigned long long ne = 0;
+    if ((he = hipMemcpy(&ne, p.nfq, 8, hipMemcpyDeviceToHost))) return (int)he;
+    std::vector<uint64_t> q(4 * ne);
+    if (ne && (he = hipMemcpy(q.data(), p.fq, 32 * ne, hipMemcpyDeviceToHost))) return (int)he;
+    unsigned long long np = 0;
+    std::vector<unsigned long long> per(p.n, 0);
+    for (unsigned long long i = 0; i < ne; ++i) {
+        np += q[4 * i + 3];
+        per[q[4 * i + 1]] += q[4 * i + 3];
+    }
+    unsigned long long dq[3] = {0, 0, 0};
+    if ((he = hipMemcpy(&dq[0], p.nbig, 8, hipMemcpyDeviceToHost)) ||
+        (he = hipMemcpy(&dq[1], p.ndefer, 8, hipMemcpyDeviceToHost)) ||
+        (he = hipMemcpy(&dq[2], p.ndefer2, 8, hipMemcpyDeviceToHost)))
+        return (int)he;
+    std::lock_guard<std::mutex> lk(h_mu);
+    h_fb_entries = ne;
+    h_fb_pairs = np;
+    h_fb_rec.swap(per);
+    for (int j = 0; j < 3; ++j) h_fb_defer[j] = dq[j];
+    return 0;
+}
+#endif
+
+// Back end with direct output (the caller's arrays hold every window): the pairs go
+// to their final place as the lists are counted.
+int run_direct(const HParams &p, const CanonPlan &P, const std::vector<int64_t> &hidx, uint64_t *bsum, int cus,
+               hipStream_t stream, uint64_t *num_distinct) {
+    const int64_t n = p.n, L = P.L;
+    const auto &lbase = P.lbase;
+    // the table kernel: two workgroups per CU (their tables fill the LDS) striding
+    // over the queued lists (count on the device); workgroups beyond it exit at once
+    const dim3 g_big = list_grid(L, 1, cus), g_table = list_grid(L, 1024 / kCountBlock, cus);
+    // the lists by length: the big instance's, in list order (a flag scan), and
+    // the ones too long for it, which the table kernel counts first
+    hipLaunchKernelGGL(canon_classify_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, stream, p);
+    excl_scan_u32(p.ndist, L, bsum, p.dist_off, stream);
+    hipLaunchKernelGGL(canon_big_queue_kernel, dim3((unsigned)((L + 1 + 255) / 256)), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(canon_table_kernel, g_table, dim3(kCountBlock), 0, stream, p);
+    // the common instance one group of records per launch: a group's lists find
+    // the start of their record known (every earlier record complete at the
+    // launch boundary) -- within one launch over every list, workgroups drift
+    // apart by more than a record's share of lists, and half of C4's pairs found
+    // their record's start unknown (scripts/canon_direct_probe.py).  A record
+    // with kGroupLists lists or more is a group of its own; smaller records are
+    // grouped up to that many lists (within such a group some lists take the pk
+    // path).
+    for (int64_t r0 = 0; r0 < n;) {
+        int64_t r1 = r0 + 1;
+        if (lbase[r1] - lbase[r0] < kGroupLists)
+            while (r1 < n && lbase[r1 + 1] - lbase[r0] <= kGroupLists && lbase[r1 + 1] - lbase[r1] < kGroupLists)
+                ++r1;
+        HParams pg = p;
+        pg.l_lo = lbase[r0];
+        pg.l_hi = lbase[r1];
+        // the group's long lists (big instance) first, then the others; a group
+        // whose records are shorter than the common instance's cap has none
+        int64_t wmax = 0;
+        for (int64_t r = r0; r < r1; ++r) wmax = std::max<int64_t>(wmax, hidx[r + 1] - hidx[r] - p.k);
+        if (wmax > (int64_t)p.sort_cap)
+            hipLaunchKernelGGL(canon_sort_big_kernel<true>, g_big, dim3(SortBig::kBlock), 0, stream, pg);
+        hipLaunchKernelGGL(canon_sort_kernel<true>, list_grid(pg.l_hi - pg.l_lo, 2, cus), dim3(kSortBlock), 0, stream,
+                           pg);
+        r0 = r1;
+    }
+    HParams p2 = p;  // the lists both K4s instances handed back (defer2)
+    p2.tq = p.defer2;
+    p2.ntq = p.ndefer2;
+    hipLaunchKernelGGL(canon_table_kernel, g_table, dim3(kCountBlock), 0, stream, p2);
+    hipLaunchKernelGGL(canon_direct_final_kernel, dim3(1), dim3(1024), 0, stream, p);
+    hipLaunchKernelGGL(canon_fallback_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(L, 4096))),
+                       dim3(256), 0, stream, p);
+    uint64_t distinct = 0;
+    if (int e = read_result(p, p.rbase + n, stream, &distinct)) return e;
+    *num_distinct = distinct;
+#ifdef KMC_DIAG_HOOKS
+    if (int e = diag_read_back(p)) return e;
+#endif
+    return KMC_OK;
+}
+
+// Back end through pk: the lists' pairs are counted into pk / pc, the total is
+// checked against the caller's capacity, then canon_place_kernel copies them out.
+int run_placed(const HParams &p, const CanonPlan &P, uint64_t *bsum, int cus, uint64_t capacity, hipStream_t stream,
+               uint64_t *num_distinct) {
+    const int64_t n = p.n, L = P.L;
+    // persistent, two workgroups per CU (64 KB of LDS each), striding over the lists
+    hipLaunchKernelGGL(canon_sort_kernel<false>, list_grid(L, 2, cus), dim3(kSortBlock), 0, stream, p);
+    // the lists it handed to its big instance (workgroups beyond their number exit at
+    // once), before the table kernel, which also takes the big instance's deferrals
+    hipLaunchKernelGGL(canon_sort_big_kernel<false>, list_grid(L, 1, cus), dim3(SortBig::kBlock), 0, stream, p);
+    // (two workgroups per CU: their tables fill the LDS)
+    hipLaunchKernelGGL(canon_table_kernel, list_grid(L, 1024 / kCountBlock, cus), dim3(kCountBlock), 0, stream, p);
+    excl_scan_u32(p.ndist, L, bsum, p.dist_off, stream);
+    hipLaunchKernelGGL(canon_recoff_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, stream, p);
+    uint64_t distinct = 0;
+    if (int e = read_result(p, p.dist_off + L, stream, &distinct)) return e;
+    *num_distinct = distinct;
+    if (distinct > capacity) return KMC_ERR_CAPACITY;
+    if (distinct && (!p.out_keys || !p.out_counts)) return KMC_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(canon_place_kernel, dim3((unsigned)L), dim3(256), 0, stream, p);
+    hipError_t he;
+    if ((he = hipGetLastError()) || (he = hipStreamSynchronize(stream))) return (int)he;
+    return KMC_OK;
 }
 }  // namespace
 
@@ -1973,10 +2184,12 @@ extern "C" size_t kmc_count_canonical_workspace_size(const int64_t *host_indices
     std::vector<int64_t> b(n + 1);
     size_t best = 0;
     CanonPlan P;
+    HParams p{};
+    uint64_t *bsum;
     for (int mis = 0; mis < 16; ++mis) {
         for (int64_t r = 0; r <= n; ++r) b[r] = host_indices[r] + mis;
         canon_plan(b.data(), n, k, cus, P);
-        best = std::max(best, P.total);
+        best = std::max(best, canon_carve(P, n, nullptr, p, bsum));
     }
     return best;
 }
@@ -1998,19 +2211,14 @@ extern "C" int kmc_count_canonical_hash_ex(const char *data, const int64_t *indi
     if (num_seqs == 0) return KMC_OK;
     if (!data || !indices || !rec_offsets) return KMC_ERR_INVALID_ARG;
     const int64_t n = (int64_t)num_seqs;
-    std::vector<int64_t> hidx(n + 1);
-    hipError_t he = hipMemcpyAsync(hidx.data(), indices, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    if (he != hipSuccess) return (int)he;
-    for (int64_t r = 0; r < n; ++r)
-        if (hidx[r + 1] < hidx[r]) return KMC_ERR_INVALID_ARG;
     // any `data` pointer: rounded down to 16 bytes, every offset moved up by the
     // difference (the kernels read whole 16-byte chunks of the aligned buffer; the
     // rounded-down bytes share data's page and lie outside every record)
     const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
-    for (auto &x : hidx) x += (int64_t)mis;
+    std::vector<int64_t> hidx;
+    if (int e = fetch_offsets(indices, n, (int64_t)mis, stream, hidx)) return e;
     int device = 0, cus = 0;
-    if ((he = hipGetDevice(&device))) return (int)he;
+    if (hipError_t he = hipGetDevice(&device)) return (int)he;
     if (int e = device_cus(device, &cus)) return e;
     CanonPlan P;
     canon_plan(hidx.data(), n, k, cus, P);
@@ -2024,228 +2232,25 @@ extern "C" int kmc_count_canonical_hash_ex(const char *data, const int64_t *indi
     p.c_lo = P.c_lo;
     p.G = P.G;
     p.cpw = P.cpw;
-    const int64_t M = P.M, Mc = P.Mc, L = P.L;
-    p.lists = L;
+    p.lists = P.L;
     p.win_cap = (uint64_t)P.windows;
-    const int64_t NF = (int64_t)P.fsplit.size();
-    const size_t total = P.total;
-    const size_t o_idx = P.o_idx, o_lg = P.o_lg, o_cb = P.o_cb, o_ccb = P.o_ccb, o_w0 = P.o_w0, o_nw = P.o_nw,
-                 o_lb = P.o_lb, o_fs = P.o_fs, o_cnt = P.o_cnt, o_off = P.o_off, o_cntc = P.o_cntc,
-                 o_offc = P.o_offc, o_bs = P.o_bs, o_ent = P.o_ent, o_ls = P.o_ls, o_pk = P.o_pk, o_pc = P.o_pc,
-                 o_nd = P.o_nd, o_do = P.o_do, o_err = P.o_err, o_dn = P.o_dn, o_dl = P.o_dl;
-    const auto &lg = P.lg;
-    const auto &w0 = P.w0;
-    const auto &nwg = P.nwg;
-    const auto &cbase = P.cbase;
-    const auto &ccbase = P.ccbase;
-    const auto &lbase = P.lbase;
-    const auto &fsplit = P.fsplit;
-    char *ws;
-    if (workspace) {
-        if (workspace_bytes < total) return KMC_ERR_WORKSPACE;
-        // the layout's offsets are 256-byte multiples, and K3b / K4s move whole
-        // 16-byte pieces (and LDS-DMA dwords) of it
-        if (reinterpret_cast<uintptr_t>(workspace) & 255u) return KMC_ERR_ALIGNMENT;
-        ws = static_cast<char *>(workspace);
-    } else {
-        std::lock_guard<std::mutex> lk(h_mu);
-        if ((int)h_ws.size() <= device) h_ws.resize(device + 1);
-        HCache &c = h_ws[device];
-        if (c.bytes < total) {
-            if (c.ptr && hipFree(c.ptr) != hipSuccess) return KMC_ERR_NOMEM;
-            c.ptr = nullptr;
-            c.bytes = 0;
-            if (hipMalloc(&c.ptr, total) != hipSuccess) return KMC_ERR_NOMEM;
-            c.bytes = total;
-        }
-        ws = static_cast<char *>(c.ptr);
-    }
-    p.idx = reinterpret_cast<int64_t *>(ws + o_idx);
-    p.lg = reinterpret_cast<uint8_t *>(ws + o_lg);
-    p.cbase = reinterpret_cast<int64_t *>(ws + o_cb);
-    p.ccbase = reinterpret_cast<int64_t *>(ws + o_ccb);
-    p.w0 = reinterpret_cast<int32_t *>(ws + o_w0);
-    p.nwg = reinterpret_cast<int32_t *>(ws + o_nw);
-    p.lbase = reinterpret_cast<int64_t *>(ws + o_lb);
-    p.fsplit = reinterpret_cast<int2 *>(ws + o_fs);
-    p.cnt = reinterpret_cast<uint32_t *>(ws + o_cnt);
-    p.off = reinterpret_cast<uint64_t *>(ws + o_off);
-    p.cnt_c = reinterpret_cast<uint32_t *>(ws + o_cntc);
-    p.off_c = reinterpret_cast<uint64_t *>(ws + o_offc);
-    uint64_t *bsum = reinterpret_cast<uint64_t *>(ws + o_bs);
-    p.ent = reinterpret_cast<uint64_t *>(ws + o_ent);
-    p.list_start = reinterpret_cast<uint64_t *>(ws + o_ls);
-    p.pk = reinterpret_cast<uint64_t *>(ws + o_pk);
-    p.ent_c = p.pk;  // dead before K4 writes the pairs
-    p.pc = reinterpret_cast<uint32_t *>(ws + o_pc);
-    p.ndist = reinterpret_cast<uint32_t *>(ws + o_nd);
-    p.dist_off = reinterpret_cast<uint64_t *>(ws + o_do);
-    p.err = reinterpret_cast<uint32_t *>(ws + o_err);
     p.claim_cap = h_claim_cap;
     p.sort_cap = h_sort_cap;
     p.sort_cap_big = h_sort_cap_big;
-    p.nbig = reinterpret_cast<unsigned long long *>(ws + P.o_bn);
-    p.big = reinterpret_cast<uint64_t *>(ws + P.o_bl);
-    p.ndefer = reinterpret_cast<unsigned long long *>(ws + o_dn);
-    p.defer = reinterpret_cast<uint64_t *>(ws + o_dl);
     p.rec_off = rec_offsets;
     p.out_keys = keys;
     p.out_counts = counts;
-    int direct;
     {
         std::lock_guard<std::mutex> lk(h_mu);
-        direct = h_direct;
+        p.direct = h_direct;
     }
     // direct output writes pairs before the total is known: only into arrays that
     // hold every window (the distinct keys are at most that many)
-    direct = direct && keys && counts && capacity >= (uint64_t)P.windows;
-    p.direct = direct;
-    p.lrec = reinterpret_cast<int32_t *>(ws + P.o_lrec);
-    p.rstate = reinterpret_cast<unsigned long long *>(ws + P.o_rst);
-    p.rbase = reinterpret_cast<unsigned long long *>(ws + P.o_rb);
-    p.fq = reinterpret_cast<uint64_t *>(ws + P.o_fq);
-    p.nfq = reinterpret_cast<unsigned long long *>(ws + P.o_nfq);
-    p.defer2 = reinterpret_cast<uint64_t *>(ws + P.o_d2l);
-    p.ndefer2 = reinterpret_cast<unsigned long long *>(ws + P.o_d2n);
-    p.tq = p.defer;
-    p.ntq = p.ndefer;
-    if ((he = hipMemcpyAsync((void *)p.idx, hidx.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream)) ||
-        (he = hipMemcpyAsync((void *)p.lg, lg.data(), n, hipMemcpyHostToDevice, stream)) ||
-        (he = hipMemcpyAsync((void *)p.cbase, cbase.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream)) ||
-        (he = hipMemcpyAsync((void *)p.ccbase, ccbase.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream)) ||
-        (he = hipMemcpyAsync((void *)p.w0, w0.data(), n * 4, hipMemcpyHostToDevice, stream)) ||
-        (he = hipMemcpyAsync((void *)p.nwg, nwg.data(), n * 4, hipMemcpyHostToDevice, stream)) ||
-        (he = hipMemcpyAsync((void *)p.lbase, lbase.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream)) ||
-        (NF && (he = hipMemcpyAsync((void *)p.fsplit, fsplit.data(), NF * sizeof(int2), hipMemcpyHostToDevice,
-                                    stream))))
-        return (int)he;
-    if ((he = hipMemsetAsync(p.err, 0, 4, stream)) || (he = hipMemsetAsync(p.ndefer, 0, 8, stream)) ||
-        (he = hipMemsetAsync(p.nbig, 0, 8, stream)) || (he = hipMemsetAsync(p.ndefer2, 0, 8, stream)))
-        return (int)he;
-#ifdef KMC_DIAG_HOOKS
-    {
-        static unsigned long long stale;  // (static: the async copy reads it after this frame)
-        std::lock_guard<std::mutex> lk(h_mu);
-        if (h_stale_queue >= 0) {
-            stale = (unsigned long long)h_stale_queue;
-            if ((he = hipMemcpyAsync(p.ndefer2, &stale, 8, hipMemcpyHostToDevice, stream))) return (int)he;
-        }
-    }
-#endif
-    if (direct)
-        hipLaunchKernelGGL(canon_direct_setup_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, stream, p);
-    if (M > 0) {
-        if ((he = hipMemsetAsync(p.cnt, 0, (size_t)M * 4, stream)) ||
-            (he = hipMemsetAsync(p.cnt_c, 0, (size_t)Mc * 4, stream)))
-            return (int)he;
-        launch_walk<WalkCount>(p, stream);
-    }
-    excl_scan_u32(p.cnt, M, bsum, p.off, stream);
-    excl_scan_u32(p.cnt_c, Mc, bsum, p.off_c, stream);
-    launch_walk<WalkCoarse>(p, stream);
-    hipLaunchKernelGGL(canon_list_start_kernel, dim3((unsigned)((L + 1 + 255) / 256)), dim3(256), 0, stream, p);
-    if (NF > 0) hipLaunchKernelGGL(canon_fine_kernel, dim3((unsigned)NF), dim3(kWalkBlock), 0, stream, p);
-    const dim3 g_sort((unsigned)std::max<int64_t>(1, std::min<int64_t>(L, 2 * (int64_t)cus)));  // 2 per CU
-    const dim3 g_big((unsigned)std::max<int64_t>(1, std::min<int64_t>(L, (int64_t)cus)));       // 1 per CU
-    // the table kernel: two workgroups per CU (their tables fill the LDS) striding
-    // over the queued lists (count on the device); workgroups beyond it exit at once
-    const dim3 g_table((unsigned)std::max<int64_t>(1, std::min<int64_t>(L, (1024 / kCountBlock) * (int64_t)cus)));
-    if (direct) {
-        // the lists by length: the big instance's, in list order (a flag scan), and
-        // the ones too long for it, which the table kernel counts first
-        hipLaunchKernelGGL(canon_classify_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, stream, p);
-        excl_scan_u32(p.ndist, L, bsum, p.dist_off, stream);
-        hipLaunchKernelGGL(canon_big_queue_kernel, dim3((unsigned)((L + 1 + 255) / 256)), dim3(256), 0, stream, p);
-        hipLaunchKernelGGL(canon_table_kernel, g_table, dim3(kCountBlock), 0, stream, p);
-        // the common instance one group of records per launch: a group's lists find
-        // the start of their record known (every earlier record complete at the
-        // launch boundary) -- within one launch over every list, workgroups drift
-        // apart by more than a record's share of lists, and half of C4's pairs found
-        // their record's start unknown (scripts/canon_direct_probe.py).  A record
-        // with kGroupLists lists or more is a group of its own; smaller records are
-        // grouped up to that many lists (within such a group some lists take the pk
-        // path).
-        for (int64_t r0 = 0; r0 < n;) {
-            int64_t r1 = r0 + 1;
-            if (lbase[r1] - lbase[r0] < kGroupLists)
-                while (r1 < n && lbase[r1 + 1] - lbase[r0] <= kGroupLists && lbase[r1 + 1] - lbase[r1] < kGroupLists)
-                    ++r1;
-            HParams pg = p;
-            pg.l_lo = lbase[r0];
-            pg.l_hi = lbase[r1];
-            // the group's long lists (big instance) first, then the others; a group
-            // whose records are shorter than the common instance's cap has none
-            int64_t wmax = 0;
-            for (int64_t r = r0; r < r1; ++r) wmax = std::max<int64_t>(wmax, hidx[r + 1] - hidx[r] - k);
-            if (wmax > (int64_t)p.sort_cap)
-                hipLaunchKernelGGL(canon_sort_big_kernel<true>, g_big, dim3(SortBig::kBlock), 0, stream, pg);
-            const dim3 gg((unsigned)std::max<int64_t>(1, std::min<int64_t>(pg.l_hi - pg.l_lo, 2 * (int64_t)cus)));
-            hipLaunchKernelGGL(canon_sort_kernel<true>, gg, dim3(kSortBlock), 0, stream, pg);
-            r0 = r1;
-        }
-        HParams p2 = p;  // the lists both K4s instances handed back (defer2)
-        p2.tq = p.defer2;
-        p2.ntq = p.ndefer2;
-        hipLaunchKernelGGL(canon_table_kernel, g_table, dim3(kCountBlock), 0, stream, p2);
-        hipLaunchKernelGGL(canon_direct_final_kernel, dim3(1), dim3(1024), 0, stream, p);
-        hipLaunchKernelGGL(canon_fallback_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(L, 4096))),
-                           dim3(256), 0, stream, p);
-        uint64_t distinct = 0;
-        uint32_t err = 0;
-        if ((he = hipGetLastError()) ||
-            (he = hipMemcpyAsync(&distinct, p.rbase + n, 8, hipMemcpyDeviceToHost, stream)) ||
-            (he = hipMemcpyAsync(&err, p.err, 4, hipMemcpyDeviceToHost, stream)) ||
-            (he = hipStreamSynchronize(stream)))
-            return (int)he;
-        if (err & kErrBound) return KMC_ERR_INTERNAL;
-        if (err) return KMC_ERR_INVALID_ARG;  // a record far beyond any genome (see kMaxPasses)
-        *num_distinct = distinct;
-#ifdef KMC_DIAG_HOOKS
-        {
-            unsigned long long ne = 0;
-            if ((he = hipMemcpy(&ne, p.nfq, 8, hipMemcpyDeviceToHost))) return (int)he;
-            std::vector<uint64_t> q(4 * ne);
-            if (ne && (he = hipMemcpy(q.data(), p.fq, 32 * ne, hipMemcpyDeviceToHost))) return (int)he;
-            unsigned long long np = 0;
-            std::vector<unsigned long long> per(n, 0);
-            for (unsigned long long i = 0; i < ne; ++i) {
-                np += q[4 * i + 3];
-                per[q[4 * i + 1]] += q[4 * i + 3];
-            }
-            unsigned long long dq[3] = {0, 0, 0};
-            if ((he = hipMemcpy(&dq[0], p.nbig, 8, hipMemcpyDeviceToHost)) ||
-                (he = hipMemcpy(&dq[1], p.ndefer, 8, hipMemcpyDeviceToHost)) ||
-                (he = hipMemcpy(&dq[2], p.ndefer2, 8, hipMemcpyDeviceToHost)))
-                return (int)he;
-            std::lock_guard<std::mutex> lk(h_mu);
-            h_fb_entries = ne;
-            h_fb_pairs = np;
-            h_fb_rec.swap(per);
-            for (int j = 0; j < 3; ++j) h_fb_defer[j] = dq[j];
-        }
-#endif
-        return KMC_OK;
-    }
-    // persistent, two workgroups per CU (64 KB of LDS each), striding over the lists
-    hipLaunchKernelGGL(canon_sort_kernel<false>, g_sort, dim3(kSortBlock), 0, stream, p);
-    // the lists it handed to its big instance (workgroups beyond their number exit at
-    // once), before the table kernel, which also takes the big instance's deferrals
-    hipLaunchKernelGGL(canon_sort_big_kernel<false>, g_big, dim3(SortBig::kBlock), 0, stream, p);
-    hipLaunchKernelGGL(canon_table_kernel, g_table, dim3(kCountBlock), 0, stream, p);
-    excl_scan_u32(p.ndist, L, bsum, p.dist_off, stream);
-    hipLaunchKernelGGL(canon_recoff_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, stream, p);
-    uint64_t distinct = 0;
-    uint32_t err = 0;
-    if ((he = hipGetLastError()) ||
-        (he = hipMemcpyAsync(&distinct, p.dist_off + L, 8, hipMemcpyDeviceToHost, stream)) ||
-        (he = hipMemcpyAsync(&err, p.err, 4, hipMemcpyDeviceToHost, stream)) || (he = hipStreamSynchronize(stream)))
-        return (int)he;
-    if (err & kErrBound) return KMC_ERR_INTERNAL;
-    if (err) return KMC_ERR_INVALID_ARG;  // a record far beyond any genome (see kMaxPasses)
-    *num_distinct = distinct;
-    if (distinct > capacity) return KMC_ERR_CAPACITY;
-    if (distinct && (!keys || !counts)) return KMC_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(canon_place_kernel, dim3((unsigned)L), dim3(256), 0, stream, p);
-    if ((he = hipGetLastError()) || (he = hipStreamSynchronize(stream))) return (int)he;
-    return KMC_OK;
+    p.direct = p.direct && keys && counts && capacity >= (uint64_t)P.windows;
+    uint64_t *bsum = nullptr;
+    if (int e = bind_workspace(P, n, device, workspace, workspace_bytes, p, bsum)) return e;
+    if (int e = upload_plan(p, P, hidx, stream)) return e;
+    if (int e = run_front(p, P, bsum, stream)) return e;
+    return p.direct ? run_direct(p, P, hidx, bsum, cus, stream, num_distinct)
+                    : run_placed(p, P, bsum, cus, capacity, stream, num_distinct);
 }

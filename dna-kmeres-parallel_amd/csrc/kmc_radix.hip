@@ -35,12 +35,12 @@
 #include <cmath>
 #include <cstdint>
 #include <mutex>
-#include <vector>
 
 #include "kmc.h"
 #include "kmc_internal.h"
 #include "kmc_scan.h"
 #include "kmc_stream.h"
+#include "kmc_workspace.h"
 
 namespace kmc {
 namespace {
@@ -983,43 +983,40 @@ __global__ __launch_bounds__(256) void radix_invalid_kernel(RParams p) {
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
+// The workspace of a call, carved from `base` (null: only the total means
+// anything).  capv, flag, ovf_cnt and ovf exist in sampled mode only (else null, no
+// bytes); flag takes one 256-byte unit; ent has 16 bytes (8 entries) of slack.
 struct RLayout {
-    size_t cnt, off, bsum, capv, flag, ovf_cnt, ovf, ent, stage, total;
+    uint32_t *cnt;
+    uint64_t *off, *bsum;
+    uint32_t *capv, *flag, *ovf_cnt;
+    unsigned long long *ovf;
+    uint16_t *ent;
+    uint32_t *stage;
+    size_t total;
     int64_t m, nscan;
 };
 
-inline RLayout r_layout(int k, int64_t n, int G, int64_t ent_cap, bool sampled, uint32_t ovf_cap) {
+inline RLayout r_layout(void *base, int k, int64_t n, int G, int64_t ent_cap, bool sampled, uint32_t ovf_cap) {
     RLayout L;
     const int64_t nbk = (int64_t)1 << (2 * k - low_bits(k));
     L.m = n * nbk * G;
     L.nscan = (L.m + kScanTile - 1) / kScanTile;
-    size_t o = 0;
-    L.cnt = o;
-    o += al256((size_t)L.m * 4);
-    L.off = o;
-    o += al256((size_t)(L.m + 1) * 8);
-    L.bsum = o;
-    o += al256((size_t)(L.nscan + 1) * 8);
-    L.capv = o;
-    o += sampled ? al256((size_t)L.m * 4) : 0;
-    L.flag = o;
-    o += sampled ? 256 : 0;
-    L.ovf_cnt = o;
-    o += sampled ? al256((size_t)G * 4) : 0;
-    L.ovf = o;
-    o += sampled ? al256((size_t)G * ovf_cap * 8) : 0;
-    L.ent = o;
-    o += al256((size_t)ent_cap * 2 + 16);
-    L.stage = o;
-    o += al256((size_t)n * ((size_t)1 << (2 * k)) * 4);
-    L.total = o;
+    Carver c(base);
+    L.cnt = c.take<uint32_t>((size_t)L.m);
+    L.off = c.take<uint64_t>((size_t)(L.m + 1));
+    L.bsum = c.take<uint64_t>((size_t)(L.nscan + 1));
+    L.capv = c.take_if<uint32_t>(sampled, (size_t)L.m);
+    L.flag = c.take_if<uint32_t>(sampled, 1);
+    L.ovf_cnt = c.take_if<uint32_t>(sampled, (size_t)G);
+    L.ovf = c.take_if<unsigned long long>(sampled, (size_t)G * ovf_cap);
+    L.ent = c.take<uint16_t>((size_t)ent_cap + 8);
+    L.stage = c.take<uint32_t>((size_t)n * ((size_t)1 << (2 * k)));
+    L.total = c.total();
     return L;
 }
 
-std::mutex r_mu;
-std::vector<int> r_cus;  // CUs per device
+std::mutex r_mu;  // the two settings below
 
 // Partition offsets (kmc_diag_radix_mode): 0 = auto, 1 = exact (R1 count + scan),
 // 2 = sampled (regions sized from a 1-in-16 tile sample, exact rerun on overflow);
@@ -1034,32 +1031,15 @@ float g_cap_scale = 1.0f;
 // 25 600 lists of ~120 K entries: +0.6 ms, more than its R1 saving).
 constexpr double kSampledMinPerList = 256.0 * 1024.0;
 
-int r_grid(int device, int &G) {
-    std::lock_guard<std::mutex> lk(r_mu);
-    if ((int)r_cus.size() <= device) r_cus.resize(device + 1, 0);
-    if (r_cus[device] == 0) {
-        int v = 0;
-        hipError_t e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device);
-        if (e != hipSuccess) return (int)e;
-        r_cus[device] = v;
-    }
-    G = r_cus[device];  // one 16-wave workgroup per CU: fewer open lists than more, smaller groups
-    return 0;
-}
-
-struct RCache {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-};
-std::vector<RCache> r_ws;
+DeviceCache r_ws;  // library-owned workspace
 
 template <int K>
 int run_radix(const kmc_dense_args *a, int64_t ibias, hipStream_t st, bool size_only, size_t *size_out) {
     int device = 0;
     hipError_t he = hipGetDevice(&device);
     if (he != hipSuccess) return (int)he;
-    int G = 0;
-    int e = r_grid(device, G);
+    int G = 0;  // one 16-wave workgroup per CU: fewer open lists than more, smaller groups
+    int e = device_cus(device, &G);
     if (e) return e;
     const int64_t wl = (int64_t)a->win_lo, wh = (int64_t)a->win_hi;
     const int64_t tiles = wh > wl ? ((wh + kTile - 1) >> kTileShift) - (wl >> kTileShift) : 0;
@@ -1083,31 +1063,18 @@ int run_radix(const kmc_dense_args *a, int64_t ibias, hipStream_t st, bool size_
                                     : (int64_t)win;
     // overflow lists: 1/32 of the windows in all (past that, the exact rerun)
     const uint32_t ovf_cap = (uint32_t)std::min<double>(std::max<double>(4096.0, win / 32.0 / G), 1 << 30);
-    const RLayout L = r_layout(K, n, G, ent_cap, sampled, ovf_cap);
+    const size_t total = r_layout(nullptr, K, n, G, ent_cap, sampled, ovf_cap).total;
     if (size_only) {
-        *size_out = L.total;
+        *size_out = total;
         return 0;
     }
     void *ws = a->workspace;
     if (ws == nullptr) {
-        std::lock_guard<std::mutex> lk(r_mu);
-        if ((int)r_ws.size() <= device) r_ws.resize(device + 1);
-        RCache &c = r_ws[device];
-        if (c.bytes < L.total) {
-            if (c.ptr) {
-                he = hipFree(c.ptr);
-                if (he != hipSuccess) return (int)he;
-            }
-            c.ptr = nullptr;
-            c.bytes = 0;
-            if (hipMalloc(&c.ptr, L.total) != hipSuccess) return KMC_ERR_NOMEM;
-            c.bytes = L.total;
-        }
-        ws = c.ptr;
-    } else if (a->workspace_bytes < L.total) {
+        if ((e = r_ws.get(device, total, &ws))) return e;
+    } else if (a->workspace_bytes < total) {
         return KMC_ERR_WORKSPACE;
     }
-    char *base = static_cast<char *>(ws);
+    const RLayout L = r_layout(ws, K, n, G, ent_cap, sampled, ovf_cap);
     RParams p;
     p.data = a->data;
     p.indices = a->indices;
@@ -1120,10 +1087,10 @@ int run_radix(const kmc_dense_args *a, int64_t ibias, hipStream_t st, bool size_
     p.derive = 0;
     p.G = G;
     p.nbk = 1 << (2 * K - low_bits(K));
-    p.cnt = reinterpret_cast<uint32_t *>(base + L.cnt);
-    p.off = reinterpret_cast<uint64_t *>(base + L.off);
-    p.ent = reinterpret_cast<uint16_t *>(base + L.ent);
-    p.stage = reinterpret_cast<uint32_t *>(base + L.stage);
+    p.cnt = L.cnt;
+    p.off = L.off;
+    p.ent = L.ent;
+    p.stage = L.stage;
     p.sum = a->sum;
     p.ld = a->sum_ld ? (int64_t)a->sum_ld : n;
     p.invalid = a->invalid;
@@ -1136,7 +1103,7 @@ int run_radix(const kmc_dense_args *a, int64_t ibias, hipStream_t st, bool size_
     p.ent_cap = (uint64_t)ent_cap;
     p.cap_scale = cap_scale;
     p.status = reinterpret_cast<uint32_t *>(a->status);
-    uint64_t *bsum = reinterpret_cast<uint64_t *>(base + L.bsum);
+    uint64_t *bsum = L.bsum;
     const int64_t nbins = (int64_t)1 << (2 * K);
     const unsigned hist_grid = (unsigned)std::min<int64_t>(n * p.nbk, kMaxGridX);
 
@@ -1149,10 +1116,10 @@ int run_radix(const kmc_dense_args *a, int64_t ibias, hipStream_t st, bool size_
         // overflowed (or they exceed ent_cap) the gated exact path reruns R1 + scan +
         // R3 on the device (no host sync); R4 reads (off, cnt) regions either way
         RParams ps = p;
-        ps.capv = reinterpret_cast<uint32_t *>(base + L.capv);
-        ps.flag = reinterpret_cast<uint32_t *>(base + L.flag);
-        ps.ovf = reinterpret_cast<unsigned long long *>(base + L.ovf);
-        ps.ovf_cnt = reinterpret_cast<uint32_t *>(base + L.ovf_cnt);
+        ps.capv = L.capv;
+        ps.flag = L.flag;
+        ps.ovf = L.ovf;
+        ps.ovf_cnt = L.ovf_cnt;
         ps.ovf_cap = ovf_cap;
         he = hipMemsetAsync(ps.flag, 0, sizeof(uint32_t), st);
         if (he == hipSuccess) he = hipMemsetAsync(ps.ovf_cnt, 0, (size_t)G * 4, st);

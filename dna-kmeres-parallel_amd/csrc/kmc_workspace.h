@@ -1,0 +1,93 @@
+// kmc_workspace.h — host-side workspace plumbing shared by the .hip translation
+// units (no kernels, no device code): the 256-byte rounding of every layout, the
+// carver that lays a workspace out, the per-device grow-only scratch buffer, and
+// the cached CU count of a device.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <mutex>
+#include <vector>
+
+#include "kmc.h"
+
+namespace kmc {
+
+inline size_t round256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Lays a workspace out as consecutive arrays, each rounded up to 256 bytes.  A
+// layout is written once, as a run of take() calls: over the workspace they bind
+// the pointers, over no base (address 0: integer arithmetic, no pointer is formed
+// from null and offset) the same calls give total(), the size to ask for.
+class Carver {
+public:
+    explicit Carver(void *base = nullptr) : at_(reinterpret_cast<uintptr_t>(base)), base_(at_) {}
+    template <class T>
+    T *take(size_t count) {
+        T *p = reinterpret_cast<T *>(at_);
+        at_ += round256(count * sizeof(T));
+        return p;
+    }
+    // an array only some modes have: no bytes and a null pointer in the others
+    template <class T>
+    T *take_if(bool on, size_t count) {
+        return on ? take<T>(count) : nullptr;
+    }
+    size_t total() const { return at_ - base_; }
+
+private:
+    uintptr_t at_, base_;
+};
+
+// A library-owned scratch buffer per device that only grows: a larger request
+// frees the buffer and allocates anew.  Every subsystem keeps its own instance
+// (calls of different subsystems on different streams never share a buffer).  The
+// lock covers the lookup and the growth, not the caller's launches.
+class DeviceCache {
+public:
+    int get(int device, size_t need, void **out) {
+        std::lock_guard<std::mutex> lk(mu_);
+        if ((int)buf_.size() <= device) buf_.resize(device + 1);
+        Buf &c = buf_[device];
+        if (c.bytes < need) {
+            if (c.ptr) {
+                const hipError_t e = hipFree(c.ptr);
+                if (e != hipSuccess) return (int)e;
+                c.ptr = nullptr;
+                c.bytes = 0;
+            }
+            if (hipMalloc(&c.ptr, need) != hipSuccess) return KMC_ERR_NOMEM;
+            c.bytes = need;
+        }
+        *out = c.ptr;
+        return 0;
+    }
+
+private:
+    struct Buf {
+        void *ptr = nullptr;
+        size_t bytes = 0;
+    };
+    std::mutex mu_;
+    std::vector<Buf> buf_;
+};
+
+// Compute units of `device`, asked of the runtime once per device and process
+// (one table for every translation unit: an inline function's statics are shared).
+inline int device_cus(int device, int *cus) {
+    static std::mutex mu;
+    static std::vector<int> known;
+    std::lock_guard<std::mutex> lk(mu);
+    if ((int)known.size() <= device) known.resize(device + 1, 0);
+    if (known[device] == 0) {
+        int v = 0;
+        const hipError_t e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device);
+        if (e != hipSuccess) return (int)e;
+        known[device] = v;
+    }
+    *cus = known[device];
+    return 0;
+}
+
+}  // namespace kmc
