@@ -27,6 +27,7 @@
 #include <cstdint>
 
 #include "kmc.h"
+#include "kmc_dist_common.h"
 #include "kmc_workspace.h"
 
 namespace kmc {
@@ -46,21 +47,6 @@ struct DParams {
     float *out;
     unsigned long long *acc;  // [npairs] when split, else null
 };
-
-// packed upper triangle, row-major: getIdxTriangularMatrixRowMajor(i+1, j-i, n)
-// (kernels.h:46-48) = n*i - i*(i-1)/2 + (j - i) - (i + 1)
-__device__ __forceinline__ int64_t tri_index(int64_t i, int64_t j, int64_t n) {
-    return n * i - (i * (i - 1)) / 2 + (j - i) - (i + 1);
-}
-
-// The CPU formula, main.cu:614: 1 - (float)sum / (minLength - k + 1), the long
-// denominator converted to float by the usual arithmetic conversions.
-__device__ __forceinline__ float distance_of(uint64_t s, int64_t li, int64_t lj, int k) {
-    const int64_t m = li < lj ? li : lj;
-    return 1.0f - (float)s / (float)(m - k + 1);
-}
-
-__device__ __forceinline__ int64_t rec_len(const int64_t *idx, int64_t s) { return idx[s + 1] - idx[s] - 1; }
 
 // TT records per tile side; each thread owns TM x TN pairs and every Z-th code
 // of a chunk (TT/TM * TT/TN * Z = 256 threads).
@@ -145,21 +131,6 @@ __global__ __launch_bounds__(256) void pair_min_kernel(DParams p) {
             else
                 p.out[q] = distance_of(s, rec_len(p.indices, i), rec_len(p.indices, j), p.k);
         }
-    }
-}
-
-// split path: acc[pair] -> out[pair]
-__global__ __launch_bounds__(256) void pair_finish_kernel(DParams p) {
-    const int64_t npairs = p.n * (p.n - 1) / 2;
-    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < npairs; q += (int64_t)gridDim.x * 256) {
-        // invert q = tri_index(i, j): row i starts at n*i - i*(i+1)/2 (found by search from a float guess)
-        const double nn = (double)p.n;
-        int64_t i = (int64_t)((2 * nn - 1 - sqrt((2 * nn - 1) * (2 * nn - 1) - 8.0 * (double)q)) / 2);
-        if (i < 0) i = 0;
-        while (i > 0 && p.n * i - i * (i + 1) / 2 > q) --i;
-        while (p.n * (i + 1) - (i + 1) * (i + 2) / 2 <= q) ++i;
-        const int64_t j = q - (p.n * i - i * (i + 1) / 2) + i + 1;
-        p.out[q] = distance_of(p.acc[q], rec_len(p.indices, i), rec_len(p.indices, j), p.k);
     }
 }
 
@@ -272,12 +243,7 @@ extern "C" int kmc_pair_distances(const int32_t *sum, uint64_t sum_ld, const int
         hipLaunchKernelGGL((pair_min_kernel<16, 1, 4>), grid, dim3(256), 0, stream, p);
     else
         hipLaunchKernelGGL((pair_min_kernel<64, 4, 4>), grid, dim3(256), 0, stream, p);
-    if (p.acc) {
-        const int64_t npairs = n * (n - 1) / 2;
-        int64_t blocks = (npairs + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(pair_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
-    }
+    if (p.acc) launch_pair_finish(p.acc, indices, n, k, out, stream);
     return (int)hipGetLastError();
 }
 

@@ -15,7 +15,8 @@
 // and the step-1 / step-2 / total event timers the reference prints.  Extras:
 // a histogram dump (--counts, F3 of SURVEY.md §8(f)), k up to 13 (the reference
 // kernel is k = 3 only), multi-GPU counting over RCCL (--gpus), canonical k <= 31
-// counting (--canonical).  GPU only: there is no CPU counting path here.
+// counting (--canonical), and with it step 2 on the sparse counts (--distances:
+// kmc_pair_distances_sparse).  GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +46,7 @@ struct Options {
     bool canonical = false;
     bool softmask = false;
     bool distances = true;
+    bool canon_distances = false;
     bool quiet = false;
     bool host_loader = false;
 };
@@ -73,6 +75,9 @@ void usage(FILE *f) {
             "                    and one minKmeres2_hip per record (k = %d, int32 offsets)\n"
             "  --canonical       canonical k-mers (k <= %d) instead of the dense histogram; with\n"
             "                    --counts writes 'record<TAB>kmer<TAB>count' lines\n"
+            "  --distances       with --canonical: step 2 on the canonical counts\n"
+            "                    (kmc_pair_distances_sparse), written to both CSVs in --out\n"
+            "                    (without --canonical the dense path writes them anyway)\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
@@ -109,6 +114,8 @@ int parse(int argc, char **argv, Options &o) {
             o.counts_path = next("--counts");
         } else if (a == "--no-distances") {
             o.distances = false;
+        } else if (a == "--distances") {
+            o.canon_distances = true;
         } else if (a == "--gpus") {
             o.gpus = atoi(next("--gpus"));
         } else if (a == "--dropin") {
@@ -278,6 +285,27 @@ int run(const Options &o) {
                 for (uint64_t i = off[s]; i < off[s + 1]; ++i)
                     fprintf(f, "%" PRIu64 "\t%s\t%u\n", s, canon_kmer(keys[i], k).c_str(), cnt[i]);
             if (fclose(f) != 0) return 1;
+        }
+        if (o.canon_distances) {
+            // step 2 on the sparse lists: both CSVs hold the one vector (exact integer sums)
+            const uint64_t npairs = n * (n > 0 ? n - 1 : 0) / 2;
+            std::vector<float> mins(npairs);
+            if (npairs > 0) {
+                float *d_mins = nullptr;
+                HIPCHK(hipMalloc(&d_mins, npairs * sizeof(float)));
+                HIPCHK(hipEventRecord(ev[4], st));
+                KMCCHK(kmc_pair_distances_sparse(d_keys, d_cnt, d_off, distinct, d_idx, n, k, d_mins, nullptr, 0, st));
+                HIPCHK(hipEventRecord(ev[5], st));
+                HIPCHK(hipEventSynchronize(ev[5]));
+                if (!o.quiet) {
+                    const float t2 = ms_between(ev[4], ev[5]);
+                    printf("Elapsed parallel step 2 timer: %g ms, %g secs\n", t2, t2 / 1000);
+                }
+                HIPCHK(hipMemcpy(mins.data(), d_mins, npairs * sizeof(float), hipMemcpyDeviceToHost));
+                HIPCHK(hipFree(d_mins));
+            }
+            if (write_csv(o.out_dir + "/parallel_results.csv", mins)) return 1;
+            if (write_csv(o.out_dir + "/sequential_results.csv", mins)) return 1;
         }
         HIPCHK(hipFree(d_keys));
         HIPCHK(hipFree(d_cnt));

@@ -176,6 +176,9 @@ def _load(path):
     L.kmc_pair_distances_workspace_size.restype = ctypes.c_size_t
     L.kmc_pair_distances_workspace_size.argtypes = [_U64, ctypes.c_int, ctypes.c_int]
     L.kmc_pair_distances.argtypes = [_P, _U64, _P, _U64, ctypes.c_int, _P, _P, ctypes.c_size_t, _P]
+    L.kmc_pair_distances_sparse_workspace_size.restype = ctypes.c_size_t
+    L.kmc_pair_distances_sparse_workspace_size.argtypes = [_U64, _U64, ctypes.c_int]
+    L.kmc_pair_distances_sparse.argtypes = [_P, _P, _P, _U64, _P, _U64, ctypes.c_int, _P, _P, ctypes.c_size_t, _P]
     L.minKmeres2_hip.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.kmc_count_canonical_hash.argtypes = [_P, _P, _U64, ctypes.c_int, ctypes.c_uint, _P, _P, _U64, _P,
                                            ctypes.POINTER(_U64), _P]
@@ -355,6 +358,31 @@ def canonical_workspace_size(indices_host, k, device=0):
     """kmc_count_canonical_workspace_size for host int64 offsets (num_seqs + 1)."""
     idx = np.ascontiguousarray(indices_host, dtype=np.int64)
     return int(lib().kmc_count_canonical_workspace_size(idx.ctypes.data_as(_P), idx.size - 1, k, device))
+
+
+def pair_distances_sparse_workspace_size(num_seqs, num_entries, device=0):
+    return int(lib().kmc_pair_distances_sparse_workspace_size(num_seqs, num_entries, device))
+
+
+def pair_distances_sparse(keys, counts, rec_offsets, indices, k, num_entries=None, out=None, workspace=None,
+                          stream=None):
+    """All-pairs k-mer distance from per-record (key, count) lists
+    (kmc_pair_distances_sparse): `keys` (64-bit), `counts` (32-bit) and `rec_offsets`
+    (64-bit, n + 1) as count_canonical returns them, `indices` the device int64
+    record offsets.  Returns float32 [n(n-1)/2], packed upper triangle."""
+    import torch
+    n = int(indices.numel() - 1)
+    if num_entries is None:
+        num_entries = keys.numel()
+    if out is None:
+        out = torch.empty(max(n * (n - 1) // 2, 0), dtype=torch.float32, device=indices.device)
+    ws_ptr, ws_bytes = None, 0
+    if workspace is not None:
+        ws_ptr, ws_bytes = _dptr(workspace), workspace.numel() * workspace.element_size()
+    rc = lib().kmc_pair_distances_sparse(_dptr(keys), _dptr(counts), _dptr(rec_offsets), int(num_entries),
+                                         _dptr(indices), n, k, _dptr(out), ws_ptr, ws_bytes, _stream(stream))
+    _check(rc, "kmc_pair_distances_sparse")
+    return out
 
 
 def min_kmeres2(sums, mins, num_seqs, current_seq, indexes, stream=None):

@@ -287,6 +287,40 @@ KMC_API int kmc_count_canonical_hash_ex(const char *data, const int64_t *indices
                                         size_t workspace_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* Pairwise distance from the sparse per-record lists of kmc_count_canonical_hash[_ex]
+ * (step 2 for k <= 31, where no 4^k x num_seqs matrix exists): for every i < j
+ *     d(i,j) = 1 - (float)S_ij / (float)(min(len_i, len_j) - k + 1)
+ *     S_ij   = sum over the keys present in both records of min(count_i, count_j)
+ * with len_s, the float expression and the packed upper triangle of
+ * kmc_pair_distances; S_ij is summed exactly in 64-bit integers, so when the entries
+ * are the non-zero bins of a dense matrix the result is kmc_pair_distances' bit for bit.
+ *   keys, counts   device, num_entries elements: record s owns the entries
+ *                  [rec_offsets[s], rec_offsets[s+1]), in any order, keys distinct
+ *                  within the record (a repeated key: unspecified result, no stray
+ *                  access); keys are opaque 64-bit values, counts taken as unsigned
+ *   rec_offsets    device uint64[num_seqs + 1]; values are clamped to num_entries, so
+ *                  keys/counts are never read at or beyond num_entries whatever it holds
+ *   num_entries    the host value kmc_count_canonical_hash returned in *num_distinct
+ *   indices        device int64[num_seqs + 1] record offsets (len_s only)
+ *   out            device float[num_seqs*(num_seqs-1)/2]
+ *   workspace      device scratch of kmc_pair_distances_sparse_workspace_size() bytes
+ *                  (8 B per pair + 16 B per entry + the partition tables; it depends on
+ *                  the device's CU count), or NULL for a library-owned buffer under the
+ *                  rule of kmc_pair_distances' (NULL-workspace calls on a device must
+ *                  not overlap); KMC_ERR_WORKSPACE when smaller than that size
+ * Asynchronous on `stream`, no host read-back.  k in 1..KMC_CANON_MAX_K
+ * (KMC_ERR_UNSUPPORTED_K); num_seqs < 2: KMC_OK, nothing written; num_seqs at most
+ * KMC_SPARSE_MAX_SEQS (the record id is packed into 32 bits beside the count) and
+ * num_entries at most 2^40, KMC_ERR_INVALID_ARG above, as for null rec_offsets,
+ * indices or out, or null keys or counts with num_entries > 0.  The size query
+ * returns 0 on bad arguments. */
+#define KMC_SPARSE_MAX_SEQS 2147483648ull
+KMC_API size_t kmc_pair_distances_sparse_workspace_size(uint64_t num_seqs, uint64_t num_entries, int device);
+KMC_API int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *counts, const uint64_t *rec_offsets,
+                                      uint64_t num_entries, const int64_t *indices, uint64_t num_seqs, int k,
+                                      float *out, void *workspace, size_t workspace_bytes, hipStream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* Tracing (the reference times step 1 with cudaEvents, main.cu:262-300): when set,
  * every following dense count call on this host thread records `before` right
  * before its histogram kernel and `after` right after it, on the call's stream,
