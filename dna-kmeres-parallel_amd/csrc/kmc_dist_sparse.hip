@@ -63,6 +63,7 @@
 #include "kmc_dist_common.h"
 #include "kmc_internal.h"
 #include "kmc_scan.h"
+#include "kmc_walk.h"
 #include "kmc_workspace.h"
 
 namespace kmc {
@@ -109,46 +110,7 @@ __device__ __forceinline__ uint64_t mix_key(uint64_t key) { return splitmix64_at
 
 __device__ __forceinline__ int bucket_of(uint64_t h, int lgB) { return lgB ? (int)(h >> (64 - lgB)) : 0; }
 
-// rec_offsets[s] clamped to the entry count; s in [0, n]
-__device__ __forceinline__ int64_t off_c(const SParams &p, int64_t s) {
-    const uint64_t v = p.rec_off[s];
-    return v < (uint64_t)p.E ? (int64_t)v : p.E;
-}
-
-// largest s in [lo, hi] with off_c(s) <= e, lo - 1 if none (0 <= lo, hi <= n: any
-// offsets, sorted or not, keep every read inside rec_offsets[0..n])
-__device__ __forceinline__ int64_t find_rec(const SParams &p, int64_t e, int64_t lo, int64_t hi) {
-    int64_t a = lo, b = hi + 1;
-    while (a < b) {
-        const int64_t m = a + (b - a) / 2;
-        if (off_c(p, m) <= e)
-            a = m + 1;
-        else
-            b = m;
-    }
-    return a - 1;
-}
-
-// the record window of a workgroup's entry range, found once per range
-__device__ __forceinline__ void range_window(const SParams &p, int64_t e0, int64_t e1, int64_t *win) {
-    if (threadIdx.x == 0) {
-        int64_t lo = 0, hi = 0;
-        if (e0 < e1) {
-            lo = find_rec(p, e0, 0, p.n);
-            hi = find_rec(p, e1 - 1, 0, p.n);
-            if (lo < 0) lo = 0;
-            if (hi < lo) hi = lo;
-        }
-        win[0] = lo;
-        win[1] = hi;
-    }
-}
-
-// record of entry e, or -1 when no record claims it
-__device__ __forceinline__ int64_t rec_of(const SParams &p, int64_t e, const int64_t *win) {
-    const int64_t r = find_rec(p, e, win[0], win[1]);
-    return (r >= 0 && r < p.n) ? r : -1;
-}
+// the walk itself (off_c, find_rec, range_window, rec_of over rec_off, E, n): kmc_walk.h
 
 __global__ __launch_bounds__(kWalkBlock) void sparse_count_kernel(SParams p) {
     __shared__ uint32_t hist[kMaxBuckets];

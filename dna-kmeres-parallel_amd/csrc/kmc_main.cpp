@@ -16,7 +16,8 @@
 // a histogram dump (--counts, F3 of SURVEY.md §8(f)), k up to 13 (the reference
 // kernel is k = 3 only), multi-GPU counting over RCCL (--gpus), canonical k <= 31
 // counting (--canonical), and with it step 2 on the sparse counts (--distances:
-// kmc_pair_distances_sparse).  GPU only: there is no CPU counting path here.
+// kmc_pair_distances_sparse) or on MinHash sketches of them (--sketch:
+// kmc_sketch_from_counts + kmc_sketch_distances -> sketch_results.csv).  GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -49,6 +50,9 @@ struct Options {
     bool canon_distances = false;
     bool quiet = false;
     bool host_loader = false;
+    long sketch = 0;     // --sketch S: sketch size (0: none)
+    long min_count = 1;  // --min-count C
+    bool min_count_set = false;
 };
 
 void usage(FILE *f) {
@@ -78,12 +82,18 @@ void usage(FILE *f) {
             "  --distances       with --canonical: step 2 on the canonical counts\n"
             "                    (kmc_pair_distances_sparse), written to both CSVs in --out\n"
             "                    (without --canonical the dense path writes them anyway)\n"
+            "  --sketch S        with --canonical: bottom-S MinHash sketch of every record's k-mers\n"
+            "                    (kmc_sketch_from_counts, seed %llu, S in 1..%d) and the Mash distances\n"
+            "                    of the sketches (kmc_sketch_distances), written to sketch_results.csv\n"
+            "                    in --out; combines with --distances and --counts\n"
+            "  --min-count C     with --canonical --sketch: only k-mers seen at least C times in their\n"
+            "                    record are sketched (default 1: all)\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
             "  -q                quiet (no progress lines)\n",
             KMC_DROPIN_K, KMC_DENSE_MAX_K, KMC_CANON_MAX_K, KMC_MAX_SEQS_REFERENCE, KMC_MAX_SEQS_REFERENCE + 1,
-            KMC_DROPIN_K, KMC_CANON_MAX_K);
+            KMC_DROPIN_K, KMC_CANON_MAX_K, (unsigned long long)KMC_SKETCH_DEFAULT_SEED, KMC_SKETCH_MAX_SIZE);
 }
 
 int parse(int argc, char **argv, Options &o) {
@@ -122,6 +132,15 @@ int parse(int argc, char **argv, Options &o) {
             o.dropin = true;
         } else if (a == "--canonical") {
             o.canonical = true;
+        } else if (a == "--sketch") {
+            o.sketch = atol(next("--sketch"));
+            if (o.sketch < 1 || o.sketch > KMC_SKETCH_MAX_SIZE)
+                return fprintf(stderr, "kmc: --sketch must be in 1..%d\n", KMC_SKETCH_MAX_SIZE), 2;
+        } else if (a == "--min-count") {
+            o.min_count = atol(next("--min-count"));
+            o.min_count_set = true;
+            if (o.min_count < 0 || o.min_count > (long)UINT32_MAX)
+                return fprintf(stderr, "kmc: --min-count out of range\n"), 2;
         } else if (a == "--softmask") {
             o.softmask = true;
         } else if (a == "--host-loader") {
@@ -141,6 +160,14 @@ int parse(int argc, char **argv, Options &o) {
         return fprintf(stderr, "kmc: --dropin is the k = %d reference launch\n", KMC_DROPIN_K), 2;
     if (o.canonical ? (o.k < 1 || o.k > KMC_CANON_MAX_K) : (o.k < 1 || o.k > KMC_DENSE_MAX_K))
         return fprintf(stderr, "kmc: k = %d out of range\n", o.k), 2;
+    if ((o.sketch > 0 || o.min_count_set) && !o.canonical) {
+        fprintf(stderr, "kmc: --sketch and --min-count need --canonical\n");
+        return usage(stderr), 2;
+    }
+    if (o.min_count_set && o.sketch == 0) {
+        fprintf(stderr, "kmc: --min-count filters what --sketch takes\n");
+        return usage(stderr), 2;
+    }
     if (o.gpus < 1) return fprintf(stderr, "kmc: --gpus must be >= 1\n"), 2;
     if (o.gpus > 1 && (o.dropin || o.canonical))
         return fprintf(stderr, "kmc: --gpus > 1 is for the dense path\n"), 2;
@@ -306,6 +333,34 @@ int run(const Options &o) {
             }
             if (write_csv(o.out_dir + "/parallel_results.csv", mins)) return 1;
             if (write_csv(o.out_dir + "/sequential_results.csv", mins)) return 1;
+        }
+        if (o.sketch > 0) {
+            // sketches of the canonical lists and their Mash distances
+            const uint32_t s = (uint32_t)o.sketch;
+            const uint64_t npairs = n * (n > 0 ? n - 1 : 0) / 2;
+            std::vector<float> dist(npairs);
+            uint64_t *d_sk = nullptr;
+            uint32_t *d_sz = nullptr;
+            float *d_out = nullptr;
+            HIPCHK(hipMalloc(&d_sk, (n * s > 0 ? n * s : 1) * sizeof(uint64_t)));
+            HIPCHK(hipMalloc(&d_sz, (n > 0 ? n : 1) * sizeof(uint32_t)));
+            HIPCHK(hipMalloc(&d_out, (npairs > 0 ? npairs : 1) * sizeof(float)));
+            HIPCHK(hipEventRecord(ev[0], st));
+            KMCCHK(kmc_sketch_from_counts(d_keys, d_cnt, d_off, distinct, n, s, KMC_SKETCH_DEFAULT_SEED,
+                                          (uint32_t)o.min_count, d_sk, d_sz, nullptr, 0, st));
+            HIPCHK(hipEventRecord(ev[1], st));
+            KMCCHK(kmc_sketch_distances(d_sk, d_sz, n, s, k, d_out, nullptr, nullptr, st));
+            HIPCHK(hipEventRecord(ev[4], st));
+            HIPCHK(hipEventSynchronize(ev[4]));
+            if (!o.quiet) {
+                printf("Sketch (s=%u): %.3f ms\n", s, ms_between(ev[0], ev[1]));
+                printf("Sketch distances: %.3f ms\n", ms_between(ev[1], ev[4]));
+            }
+            if (npairs > 0) HIPCHK(hipMemcpy(dist.data(), d_out, npairs * sizeof(float), hipMemcpyDeviceToHost));
+            HIPCHK(hipFree(d_sk));
+            HIPCHK(hipFree(d_sz));
+            HIPCHK(hipFree(d_out));
+            if (write_csv(o.out_dir + "/sketch_results.csv", dist)) return 1;
         }
         HIPCHK(hipFree(d_keys));
         HIPCHK(hipFree(d_cnt));

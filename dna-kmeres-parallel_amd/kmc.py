@@ -179,6 +179,11 @@ def _load(path):
     L.kmc_pair_distances_sparse_workspace_size.restype = ctypes.c_size_t
     L.kmc_pair_distances_sparse_workspace_size.argtypes = [_U64, _U64, ctypes.c_int]
     L.kmc_pair_distances_sparse.argtypes = [_P, _P, _P, _U64, _P, _U64, ctypes.c_int, _P, _P, ctypes.c_size_t, _P]
+    L.kmc_sketch_workspace_size.restype = ctypes.c_size_t
+    L.kmc_sketch_workspace_size.argtypes = [_U64, _U64, ctypes.c_uint32, ctypes.c_int]
+    L.kmc_sketch_from_counts.argtypes = [_P, _P, _P, _U64, _U64, ctypes.c_uint32, _U64, ctypes.c_uint32, _P, _P, _P,
+                                         ctypes.c_size_t, _P]
+    L.kmc_sketch_distances.argtypes = [_P, _P, _U64, ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P]
     L.minKmeres2_hip.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.kmc_count_canonical_hash.argtypes = [_P, _P, _U64, ctypes.c_int, ctypes.c_uint, _P, _P, _U64, _P,
                                            ctypes.POINTER(_U64), _P]
@@ -383,6 +388,54 @@ def pair_distances_sparse(keys, counts, rec_offsets, indices, k, num_entries=Non
                                          _dptr(indices), n, k, _dptr(out), ws_ptr, ws_bytes, _stream(stream))
     _check(rc, "kmc_pair_distances_sparse")
     return out
+
+
+SKETCH_MAX_SIZE = 16384
+SKETCH_DEFAULT_SEED = 42
+
+
+def sketch_workspace_size(num_seqs, num_entries, sketch_size, device=0):
+    return int(lib().kmc_sketch_workspace_size(num_seqs, num_entries, sketch_size, device))
+
+
+def sketch_from_counts(keys, counts, rec_offsets, sketch_size, seed=SKETCH_DEFAULT_SEED, min_count=1,
+                       workspace=None, num_entries=None, stream=None):
+    """Bottom-s MinHash sketches (kmc_sketch_from_counts) of per-record lists as
+    count_canonical returns them (`counts` may be None while min_count <= 1).
+    Returns (sketches int64 [n, s]: uint64 hashes ascending, then all-ones fill;
+    sizes int32 [n])."""
+    import torch
+    n = int(rec_offsets.numel() - 1)
+    s = int(sketch_size)
+    if num_entries is None:
+        num_entries = keys.numel()
+    sk = torch.empty((max(n, 0), max(s, 0)), dtype=torch.int64, device=rec_offsets.device)
+    sizes = torch.empty(max(n, 0), dtype=torch.int32, device=rec_offsets.device)
+    ws_ptr, ws_bytes = None, 0
+    if workspace is not None:
+        ws_ptr, ws_bytes = _dptr(workspace), workspace.numel() * workspace.element_size()
+    rc = lib().kmc_sketch_from_counts(_dptr(keys), _dptr(counts), _dptr(rec_offsets), int(num_entries), n, s,
+                                      int(seed) & _M64, int(min_count), _dptr(sk), _dptr(sizes), ws_ptr, ws_bytes,
+                                      _stream(stream))
+    _check(rc, "kmc_sketch_from_counts")
+    return sk, sizes
+
+
+def sketch_distances(sketches, sizes, k, with_counts=False, stream=None):
+    """All-pairs Mash distance (kmc_sketch_distances) of sketch rows [n, s] and their
+    sizes [n].  Returns float32 [n(n-1)/2], packed upper triangle; with_counts:
+    (out, shared, denom), the two integer counts as int32 tensors."""
+    import torch
+    sketches = sketches.contiguous()
+    n, s = int(sketches.shape[0]), int(sketches.shape[1])
+    npairs = max(n * (n - 1) // 2, 0)
+    out = torch.empty(npairs, dtype=torch.float32, device=sketches.device)
+    sh = torch.empty(npairs, dtype=torch.int32, device=sketches.device) if with_counts else None
+    dn = torch.empty(npairs, dtype=torch.int32, device=sketches.device) if with_counts else None
+    rc = lib().kmc_sketch_distances(_dptr(sketches), _dptr(sizes), n, s, k, _dptr(out), _dptr(sh), _dptr(dn),
+                                    _stream(stream))
+    _check(rc, "kmc_sketch_distances")
+    return (out, sh, dn) if with_counts else out
 
 
 def min_kmeres2(sums, mins, num_seqs, current_seq, indexes, stream=None):

@@ -321,6 +321,68 @@ KMC_API int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *coun
                                       float *out, void *workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* MinHash sketches and Mash distances (no reference counterpart): the distance
+ * path for collections whose distinct k-mers do not fit, or whose n x n step over
+ * every k-mer costs too much.  A record is reduced to its sketch_size smallest
+ * distinct key hashes; distances come from those sorted lists alone, and sketches
+ * made in separate calls (with one seed and sketch_size) may be concatenated.
+ *
+ * kmc_sketch_from_counts: sketches of the per-record lists of
+ * kmc_count_canonical_hash[_ex], with the list conventions of
+ * kmc_pair_distances_sparse (record r owns [rec_offsets[r], rec_offsets[r+1]), any
+ * order; offsets are clamped to num_entries and only compared against, nothing is
+ * read at or beyond num_entries; keys are opaque 64-bit values, distinct within a
+ * record: a repeated key gives an unspecified result and no stray access).
+ *   min_count     an entry takes part iff counts[e] >= min_count; 0 and 1 both mean
+ *                 every entry, and counts may then be NULL
+ *   hash          h(key) = splitmix64 output 0 of the stream seeded with key ^ seed:
+ *                     z = (key ^ seed) + 0x9E3779B97F4A7C15            (mod 2^64)
+ *                     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *                     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *                     h = z ^ (z >> 31)
+ *                 a bijection of the key, so distinct keys have distinct hashes
+ *   sketch_sizes  device uint32[num_seqs]: min(sketch_size, participating entries of r)
+ *   sketches      device uint64[num_seqs * sketch_size]: row r holds the sketch_sizes[r]
+ *                 smallest hashes of record r, ascending, then UINT64_MAX to the end
+ *                 of the row (a real hash may equal UINT64_MAX: sketch_sizes tells)
+ *   workspace     device scratch of kmc_sketch_workspace_size() bytes (about 2 KB per
+ *                 record), or NULL for a library-owned buffer under the rule of
+ *                 kmc_pair_distances' (NULL-workspace calls on a device must not
+ *                 overlap); KMC_ERR_WORKSPACE when smaller than that size
+ * Exact for any content (a radix select over the 64 hash bits: no capacity, no
+ * unlucky hash).  Asynchronous on `stream`, no host read-back; the work launched
+ * depends on the host arguments only.  KMC_ERR_INVALID_ARG: sketch_size 0 or above
+ * KMC_SKETCH_MAX_SIZE, num_entries above 2^40, null rec_offsets, sketches or
+ * sketch_sizes, null keys with num_entries > 0, null counts with min_count > 1.
+ * num_seqs == 0: KMC_OK.  The size query returns 0 on bad arguments.
+ *
+ * kmc_sketch_distances: for every i < j, with A and B the first sketch_sizes[i] and
+ * sketch_sizes[j] values (sizes clamped to sketch_size) of rows i and j, assumed
+ * ascending, U the min(sketch_size, |A u B|) smallest values of A u B, denom = |U|
+ * and shared = |U n A n B| (Mash's merge rule):
+ *     denom == 0       NaN
+ *     shared == 0      1.0f
+ *     shared == denom  +0.0f
+ *     otherwise        J = shared / denom, d = -log(2J / (1 + J)) / k in double,
+ *                      capped at 1.0, rounded to float
+ * written to out[] in the packed upper triangle of kmc_pair_distances; shared and
+ * denom (device uint32, same packing) receive the integer counts when non-NULL.
+ * No workspace; asynchronous on `stream`.  k in 1..KMC_CANON_MAX_K
+ * (KMC_ERR_UNSUPPORTED_K); num_seqs < 2: KMC_OK, nothing written; null sketches,
+ * sketch_sizes or out, or a sketch_size outside 1..KMC_SKETCH_MAX_SIZE:
+ * KMC_ERR_INVALID_ARG. */
+#define KMC_SKETCH_MAX_SIZE 16384
+#define KMC_SKETCH_DEFAULT_SEED 42ull
+KMC_API size_t kmc_sketch_workspace_size(uint64_t num_seqs, uint64_t num_entries, uint32_t sketch_size, int device);
+KMC_API int kmc_sketch_from_counts(const uint64_t *keys, const uint32_t *counts, const uint64_t *rec_offsets,
+                                   uint64_t num_entries, uint64_t num_seqs, uint32_t sketch_size, uint64_t seed,
+                                   uint32_t min_count, uint64_t *sketches, uint32_t *sketch_sizes,
+                                   void *workspace, size_t workspace_bytes, hipStream_t stream);
+KMC_API int kmc_sketch_distances(const uint64_t *sketches, const uint32_t *sketch_sizes, uint64_t num_seqs,
+                                 uint32_t sketch_size, int k, float *out, uint32_t *shared, uint32_t *denom,
+                                 hipStream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* Tracing (the reference times step 1 with cudaEvents, main.cu:262-300): when set,
  * every following dense count call on this host thread records `before` right
  * before its histogram kernel and `after` right after it, on the call's stream,

@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""sketchbench.py — times kmc_sketch_from_counts, kmc_sketch_distances and
+kmc_pair_distances_sparse on the same canonical lists (HIP events, warm-up, median
+of --runs) and writes one JSON line per (input, sketch size) to --out
+(profiles/pr_sketch.jsonl).
+
+Inputs (synthetic, generated on the device):
+  iid          8 x 50 Mbase independent records, k = 31
+  copies_1pct  record 0 and 7 copies of it with 1 % substitutions, k = 31; the Mash
+               distance of (0, i) is recorded next to the 0.01 substitution rate
+  many         4096 x 100 kbase independent records, k = 21: the regime the sketch is
+               for (the exact path leaves its LDS pair matrix above 64 records)
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "dna-kmeres-parallel_amd"))
+
+import torch  # noqa: E402
+
+import kmc  # noqa: E402
+
+
+def timed(fn, runs, warmup=2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(runs):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms), "runs": runs}
+
+
+def make_input(name, records, record_len, dev):
+    data = torch.empty(records * (record_len + 1), dtype=torch.uint8, device=dev)
+    kmc.synth_fill(data, records, record_len, 0x5EED0008)
+    if name == "copies_1pct":
+        g = torch.Generator(device=dev)
+        g.manual_seed(1)
+        rows = data.view(records, record_len + 1)
+        lut = torch.tensor([65, 67, 71, 84], dtype=torch.uint8, device=dev)  # ACGT
+        code = torch.zeros(256, dtype=torch.int64, device=dev)
+        code[lut.long()] = torch.arange(4, device=dev)
+        base = rows[0, :record_len].clone()
+        for r in range(1, records):
+            hit = torch.rand(record_len, device=dev, generator=g) < 0.01
+            step = torch.randint(1, 4, (record_len,), device=dev, generator=g)
+            sub = lut[(code[base.long()] + step) % 4]  # always another base
+            rows[r, :record_len] = torch.where(hit, sub, base)
+    idx = torch.from_numpy(kmc.synth_indices(records, record_len)).to(dev)
+    return data, idx
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(HERE), "profiles", "pr_sketch.jsonl"))
+    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--inputs", default="iid,copies_1pct,many")
+    ap.add_argument("--sizes", default="1000,10000")
+    ap.add_argument("--scale", type=float, default=1.0, help="scales the record lengths (a quick rehearsal: 0.01)")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    shapes = {"iid": (8, 50_000_000, 31), "copies_1pct": (8, 50_000_000, 31), "many": (4096, 100_000, 21)}
+    with open(args.out, "w") as out:
+        for name in args.inputs.split(","):
+            records, record_len, k = shapes[name]
+            record_len = max(int(record_len * args.scale), k + 1)
+            data, idx = make_input(name, records, record_len, dev)
+            keys, counts, off = kmc.count_canonical(data, idx, k)
+            torch.cuda.synchronize()
+            del data
+            exact = timed(lambda: kmc.pair_distances_sparse(keys, counts, off, idx, k), args.runs)
+            exact_d = kmc.pair_distances_sparse(keys, counts, off, idx, k)[:7].cpu().tolist()
+            for s in (int(x) for x in args.sizes.split(",")):
+                sk, sz = kmc.sketch_from_counts(keys, counts, off, s)
+                # 8.4e6 pairs at s = 10000 run from global memory for about a second: fewer runs
+                druns = 3 if records > 1000 and s > 2048 else args.runs
+                rec = {
+                    "input": name, "records": records, "record_len": record_len, "k": k, "sketch_size": s,
+                    "entries": int(keys.numel()), "digit_bits": 8,
+                    "workspace_bytes": kmc.sketch_workspace_size(records, keys.numel(), s),
+                    "kmc_sketch_from_counts": timed(lambda: kmc.sketch_from_counts(keys, counts, off, s), args.runs),
+                    "kmc_sketch_distances": timed(lambda: kmc.sketch_distances(sk, sz, k), druns, warmup=1),
+                    "kmc_pair_distances_sparse": exact,
+                    "exact_dist_first7": exact_d,
+                }
+                d, sh, dn = kmc.sketch_distances(sk, sz, k, with_counts=True)
+                torch.cuda.synchronize()
+                rec["mash_dist_first7"] = d[:7].cpu().tolist()
+                rec["shared_first7"] = sh[:7].cpu().tolist()
+                rec["denom_first7"] = dn[:7].cpu().tolist()
+                if name == "copies_1pct":
+                    rec["substitution_rate"] = 0.01
+                out.write(json.dumps(rec) + "\n")
+                out.flush()
+                print(json.dumps(rec), flush=True)
+            del keys, counts, off
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
