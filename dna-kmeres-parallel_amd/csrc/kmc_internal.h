@@ -34,4 +34,8 @@ __host__ __device__ inline uint64_t splitmix64_at(uint64_t seed, uint64_t n) {
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
+
+// The MinHash value of a k-mer key (kmc_sketch.hip, kmc_sketch_seq.hip): a
+// bijection of the 64-bit words, so distinct keys have distinct hashes.
+__host__ __device__ inline uint64_t sketch_hash(uint64_t key, uint64_t seed) { return splitmix64_at(key ^ seed, 0); }
 }  // namespace kmc

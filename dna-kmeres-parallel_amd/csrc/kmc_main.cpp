@@ -17,7 +17,8 @@
 // kernel is k = 3 only), multi-GPU counting over RCCL (--gpus), canonical k <= 31
 // counting (--canonical), and with it step 2 on the sparse counts (--distances:
 // kmc_pair_distances_sparse) or on MinHash sketches of them (--sketch:
-// kmc_sketch_from_counts + kmc_sketch_distances -> sketch_results.csv).  GPU only: there is no CPU counting path here.
+// kmc_sketch_from_counts + kmc_sketch_distances -> sketch_results.csv; --sketch-direct:
+// kmc_sketch_from_sequences instead, no canonical count).  GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -53,6 +54,7 @@ struct Options {
     long sketch = 0;     // --sketch S: sketch size (0: none)
     long min_count = 1;  // --min-count C
     bool min_count_set = false;
+    bool sketch_direct = false;  // --sketch-direct: kmc_sketch_from_sequences, no canonical count
 };
 
 void usage(FILE *f) {
@@ -88,6 +90,9 @@ void usage(FILE *f) {
             "                    in --out; combines with --distances and --counts\n"
             "  --min-count C     with --canonical --sketch: only k-mers seen at least C times in their\n"
             "                    record are sketched (default 1: all)\n"
+            "  --sketch-direct   with --canonical --sketch: sketch straight from the records\n"
+            "                    (kmc_sketch_from_sequences: one pass, no canonical count, the same\n"
+            "                    sketch_results.csv); not with --min-count above 1, --counts, --distances\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
@@ -136,6 +141,8 @@ int parse(int argc, char **argv, Options &o) {
             o.sketch = atol(next("--sketch"));
             if (o.sketch < 1 || o.sketch > KMC_SKETCH_MAX_SIZE)
                 return fprintf(stderr, "kmc: --sketch must be in 1..%d\n", KMC_SKETCH_MAX_SIZE), 2;
+        } else if (a == "--sketch-direct") {
+            o.sketch_direct = true;
         } else if (a == "--min-count") {
             o.min_count = atol(next("--min-count"));
             o.min_count_set = true;
@@ -166,6 +173,14 @@ int parse(int argc, char **argv, Options &o) {
     }
     if (o.min_count_set && o.sketch == 0) {
         fprintf(stderr, "kmc: --min-count filters what --sketch takes\n");
+        return usage(stderr), 2;
+    }
+    if (o.sketch_direct && !(o.canonical && o.sketch > 0)) {
+        fprintf(stderr, "kmc: --sketch-direct needs --canonical --sketch S\n");
+        return usage(stderr), 2;
+    }
+    if (o.sketch_direct && (o.min_count > 1 || !o.counts_path.empty() || o.canon_distances)) {
+        fprintf(stderr, "kmc: --sketch-direct never counts: not with --min-count above 1, --counts or --distances\n");
         return usage(stderr), 2;
     }
     if (o.gpus < 1) return fprintf(stderr, "kmc: --gpus must be >= 1\n"), 2;
@@ -237,6 +252,36 @@ float ms_between(hipEvent_t a, hipEvent_t b) {
     return ms;
 }
 
+// --sketch: the rows of every record (make_rows: from the canonical lists or, with
+// --sketch-direct, from the record buffer), their Mash distances, sketch_results.csv
+template <class MakeRows>
+int sketch_step(const Options &o, MakeRows make_rows, uint64_t n, hipStream_t st, hipEvent_t *ev) {
+    const uint32_t s = (uint32_t)o.sketch;
+    const uint64_t npairs = n * (n > 0 ? n - 1 : 0) / 2;
+    std::vector<float> dist(npairs);
+    uint64_t *d_sk = nullptr;
+    uint32_t *d_sz = nullptr;
+    float *d_out = nullptr;
+    HIPCHK(hipMalloc(&d_sk, (n * s > 0 ? n * s : 1) * sizeof(uint64_t)));
+    HIPCHK(hipMalloc(&d_sz, (n > 0 ? n : 1) * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&d_out, (npairs > 0 ? npairs : 1) * sizeof(float)));
+    HIPCHK(hipEventRecord(ev[0], st));
+    KMCCHK(make_rows(s, d_sk, d_sz));
+    HIPCHK(hipEventRecord(ev[1], st));
+    KMCCHK(kmc_sketch_distances(d_sk, d_sz, n, s, o.k, d_out, nullptr, nullptr, st));
+    HIPCHK(hipEventRecord(ev[4], st));
+    HIPCHK(hipEventSynchronize(ev[4]));
+    if (!o.quiet) {
+        printf("Sketch (s=%u): %.3f ms\n", s, ms_between(ev[0], ev[1]));
+        printf("Sketch distances: %.3f ms\n", ms_between(ev[1], ev[4]));
+    }
+    if (npairs > 0) HIPCHK(hipMemcpy(dist.data(), d_out, npairs * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipFree(d_sk));
+    HIPCHK(hipFree(d_sz));
+    HIPCHK(hipFree(d_out));
+    return write_csv(o.out_dir + "/sketch_results.csv", dist) ? 1 : 0;
+}
+
 int run(const Options &o) {
     const int k = o.k;
     int ndev = 0;
@@ -280,6 +325,19 @@ int run(const Options &o) {
         printf("%" PRIu64 " sequences read .\n", n);
         printf("Load (%s parse, file to device): %.1f ms\n", host ? "host" : "GPU",
                std::chrono::duration<double, std::milli>(tl1 - tl0).count());
+    }
+    if (o.canonical && o.sketch_direct) {
+        // sketches straight from the record buffer: the canonical counter never runs
+        const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
+        if (int e = sketch_step(o, [&](uint32_t s, uint64_t *d_sk, uint32_t *d_sz) {
+                return kmc_sketch_from_sequences(d_data, d_idx, n, bytes, k, flags, s, KMC_SKETCH_DEFAULT_SEED, d_sk,
+                                                 d_sz, nullptr, 0, st);
+            }, n, st, ev))
+            return e;
+        HIPCHK(hipFree(d_data));
+        HIPCHK(hipFree(d_idx));
+        if (fa) kmc_fasta_free(fa);
+        return 0;
     }
     if (o.canonical) {
         const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
@@ -336,31 +394,11 @@ int run(const Options &o) {
         }
         if (o.sketch > 0) {
             // sketches of the canonical lists and their Mash distances
-            const uint32_t s = (uint32_t)o.sketch;
-            const uint64_t npairs = n * (n > 0 ? n - 1 : 0) / 2;
-            std::vector<float> dist(npairs);
-            uint64_t *d_sk = nullptr;
-            uint32_t *d_sz = nullptr;
-            float *d_out = nullptr;
-            HIPCHK(hipMalloc(&d_sk, (n * s > 0 ? n * s : 1) * sizeof(uint64_t)));
-            HIPCHK(hipMalloc(&d_sz, (n > 0 ? n : 1) * sizeof(uint32_t)));
-            HIPCHK(hipMalloc(&d_out, (npairs > 0 ? npairs : 1) * sizeof(float)));
-            HIPCHK(hipEventRecord(ev[0], st));
-            KMCCHK(kmc_sketch_from_counts(d_keys, d_cnt, d_off, distinct, n, s, KMC_SKETCH_DEFAULT_SEED,
-                                          (uint32_t)o.min_count, d_sk, d_sz, nullptr, 0, st));
-            HIPCHK(hipEventRecord(ev[1], st));
-            KMCCHK(kmc_sketch_distances(d_sk, d_sz, n, s, k, d_out, nullptr, nullptr, st));
-            HIPCHK(hipEventRecord(ev[4], st));
-            HIPCHK(hipEventSynchronize(ev[4]));
-            if (!o.quiet) {
-                printf("Sketch (s=%u): %.3f ms\n", s, ms_between(ev[0], ev[1]));
-                printf("Sketch distances: %.3f ms\n", ms_between(ev[1], ev[4]));
-            }
-            if (npairs > 0) HIPCHK(hipMemcpy(dist.data(), d_out, npairs * sizeof(float), hipMemcpyDeviceToHost));
-            HIPCHK(hipFree(d_sk));
-            HIPCHK(hipFree(d_sz));
-            HIPCHK(hipFree(d_out));
-            if (write_csv(o.out_dir + "/sketch_results.csv", dist)) return 1;
+            if (int e = sketch_step(o, [&](uint32_t s, uint64_t *d_sk, uint32_t *d_sz) {
+                    return kmc_sketch_from_counts(d_keys, d_cnt, d_off, distinct, n, s, KMC_SKETCH_DEFAULT_SEED,
+                                                  (uint32_t)o.min_count, d_sk, d_sz, nullptr, 0, st);
+                }, n, st, ev))
+                return e;
         }
         HIPCHK(hipFree(d_keys));
         HIPCHK(hipFree(d_cnt));

@@ -117,7 +117,7 @@ __device__ __forceinline__ bool takes_part(const KParams &p, int64_t e) {
     return p.min_count <= 1 || p.counts[e] >= p.min_count;
 }
 
-__device__ __forceinline__ uint64_t hash_of(const KParams &p, uint64_t key) { return splitmix64_at(key ^ p.seed, 0); }
+__device__ __forceinline__ uint64_t hash_of(const KParams &p, uint64_t key) { return sketch_hash(key, p.seed); }
 
 // One digit level: bins of bits [shift, shift + kDigitBits) of the hashes that agree
 // with thr[record] above them (FIRST: the top digit, every participating hash).

@@ -1,0 +1,506 @@
+// kmc_sketch_seq.hip — bottom-s MinHash sketches straight from the record buffer:
+// kmc_sketch_from_sequences writes the rows and sizes kmc_sketch_from_counts
+// writes for the lists of kmc_count_canonical_hash, without those lists.  The bases
+// are walked once (kmc_canon_walk.h, the canonical counter's walk), every valid
+// window's key is hashed (sketch_hash) and a workgroup keeps the s smallest
+// distinct hashes of the record piece it is in as a sorted set in LDS.  Exact for
+// any content: there is no table, no capacity and no retry.  Asynchronous, no host
+// read-back; the launches depend on the host arguments only.
+//
+//   prep    widx[r] = clamp(indices[r], 0, data_bytes) + (data & 15): the offsets
+//           over the 16-byte aligned buffer, as the canonical counter's host does
+//   walk    G workgroups; workgroup w walks cpw = ceil(chunks / G) 16-byte chunks of
+//           [widx[0], widx[n]) (both read on the device), record piece by piece.
+//           A valid window with hash h is a candidate iff the set is not full or
+//           h < T (T: the set's largest value once it holds s), and h is not in the
+//           set (a binary search, so a repeated key is staged once per merge at
+//           most and low-complexity input costs searches, not merges).  Candidates
+//           are appended to a staging buffer of kStage values through an LDS
+//           counter; when it is full it is sorted (bitonic) and merged into the
+//           set: every staged value not equal to its predecessor nor in the set is
+//           kept, set values move up by the kept values below them, kept values
+//           land behind the set values below them, positions >= s fall off.  Lanes
+//           whose candidates did not fit filter them against the new T and append
+//           again.  After N random windows about s / N of the windows are
+//           candidates, so merges become rare and the walk's VALU work bounds the
+//           kernel.  A record wholly inside the range goes to its output row; of a
+//           record that crosses the range's start or end the set goes to the
+//           workgroup's slot 2w (crosses the start) or 2w + 1 (starts here) of
+//           `part`, its size to `psize`.
+//   fill    a record of no window gets size 0 and a row of UINT64_MAX (256 threads
+//           per record, no LDS); a record in one range was written by the walk
+//   merge   one workgroup per cut between two ranges (G - 1): at most one record
+//           has windows on both sides of a cut, and the workgroup of the first cut
+//           it crosses folds its partial sets -- slot 2w0 + 1, then 2w for
+//           w0 < w <= w1, the ranges follow from widx alone -- with the same merge,
+//           kStage values at a time, and writes the row, its tail and its size.
+// Which slots a record has is a function of widx and the geometry, and every slot
+// read was written by this call's walk: nothing in the workspace is accumulated
+// into, and nothing a former call left there is read.
+//
+// Constants, shipped / under -DKMC_DIAG_HOOKS (libkmc_diag.so: a few thousand bases
+// pass through many ranges, merges and partial sets; no new symbol):
+//   kBlock      threads of a workgroup                     1024 / 64
+//   kStage      staged candidates per merge (= kBlock)     1024 / 64
+//   kMinChunks  16-byte chunks per range, at least         1024 / 16  (16 KB / 256 B)
+//   kWgPerCu    ranges per CU at most                      1 / 2
+// LDS: 8 s' + 12 kStage bytes and a few words; s' = 1024 / 4096 / 16384 for
+// s <= 1024 / 4096 / 16384: 20 / 44 / 140 KB shipped.
+// Workspace: 8 (n + 1) B of offsets + G (8 + 16 s) B of partial sets,
+// G = min(kWgPerCu * CUs, ceil((data_bytes / 16 + 3) / kMinChunks)).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "kmc.h"
+#include "kmc_canon_walk.h"
+#include "kmc_internal.h"
+#include "kmc_workspace.h"
+
+namespace kmc {
+namespace {
+
+#ifdef KMC_DIAG_HOOKS
+constexpr int kBlock = 64;
+constexpr int64_t kMinChunks = 16;
+constexpr int kWgPerCu = 2;
+#else
+constexpr int kBlock = 1024;
+constexpr int64_t kMinChunks = 1024;
+constexpr int kWgPerCu = 1;
+#endif
+constexpr int kStage = kBlock;
+constexpr int kWaves = kBlock / 64;
+constexpr uint64_t kFill = ~0ull;
+constexpr uint64_t kMaxSeqs = 1ull << 40;
+
+struct SArgs {
+    const char *data;        // rounded down to 16 bytes
+    const int64_t *indices;  // the caller's
+    int64_t *widx;           // [n + 1] offsets over `data`
+    int64_t n;
+    int64_t data_bytes, mis;
+    int k;
+    uint32_t flags;
+    int G;
+    uint32_t s;
+    uint64_t seed;
+    uint64_t *part;   // [2 G][s]
+    uint32_t *psize;  // [2 G]
+    uint64_t *sketches;
+    uint32_t *sizes;
+};
+
+// The walk's view (kmc_canon_walk.h) with the geometry of this call
+struct Walk {
+    const char *data;
+    const int64_t *idx;
+    int64_t n, lo, hi;
+    int k;
+    uint32_t flags;
+    int64_t c_lo, cpw;
+};
+
+__device__ __forceinline__ Walk make_walk(const SArgs &a) {
+    Walk W;
+    W.data = a.data;
+    W.idx = a.widx;
+    W.n = a.n;
+    W.lo = a.widx[0];
+    W.hi = a.widx[a.n];
+    if (W.hi < W.lo) W.hi = W.lo;
+    W.k = a.k;
+    W.flags = a.flags;
+    W.c_lo = W.lo >> 4;
+    const int64_t chunks = W.hi > W.lo ? ((W.hi + 15) >> 4) - W.c_lo : 0;
+    const int64_t cpw = (chunks + a.G - 1) / a.G;
+    W.cpw = cpw > 1 ? cpw : 1;
+    return W;
+}
+
+struct HashOf {
+    uint64_t seed;
+    __device__ __forceinline__ unsigned long long operator()(uint64_t key) const { return sketch_hash(key, seed); }
+};
+
+__global__ __launch_bounds__(256) void sketch_seq_prep_kernel(SArgs a) {
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r <= a.n; r += (int64_t)gridDim.x * 256) {
+        int64_t x = a.indices[r];
+        x = x < 0 ? 0 : (x > a.data_bytes ? a.data_bytes : x);
+        a.widx[r] = x + a.mis;
+    }
+}
+
+template <int CAP>
+struct SetLds {
+    uint64_t set[CAP];        // ascending, distinct; the first m are valid
+    uint64_t stage[kStage];
+    uint32_t kp[kStage + 1];  // kept staged values before each staged value; [c]: all of them
+    uint32_t wsum[kWaves];
+    uint32_t ctr[3];          // staged counts of the walk's rounds, in rotation
+    int64_t first;
+};
+static_assert(sizeof(SetLds<KMC_SKETCH_MAX_SIZE>) <= 160 * 1024, "the set and its staging buffer fit the CU's LDS");
+
+// first index in a[0, n) whose value is not below v
+__device__ __forceinline__ int lower_bound(const uint64_t *a, int n, uint64_t v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < v)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ bool in_set(const uint64_t *set, int m, uint64_t v) {
+    const int i = lower_bound(set, m, v);
+    return i < m && set[i] == v;
+}
+
+// Merges stage[0, c) (any order, repeats allowed, written before the caller's last
+// barrier) into set[0, m): returns the new m = min(s, distinct values of both).
+// Every thread of the workgroup calls it with the same arguments.
+template <int CAP>
+__device__ __forceinline__ int merge_stage(SetLds<CAP> &L, int m, int s, int c) {
+    constexpr int R = CAP / kBlock < 1 ? 1 : (CAP / kBlock > 4 ? 4 : CAP / kBlock);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int P = 1;
+    while (P < c) P <<= 1;
+    if (tid >= c && tid < P) L.stage[tid] = kFill;
+    lds_barrier();
+    for (int kk = 2; kk <= P; kk <<= 1) {
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            if (tid < (P >> 1)) {
+                const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1));
+                const int l = i | j;
+                const uint64_t x = L.stage[i], y = L.stage[l];
+                const bool up = (i & kk) == 0;
+                if ((x > y) == up) {
+                    L.stage[i] = y;
+                    L.stage[l] = x;
+                }
+            }
+            lds_barrier();
+        }
+    }
+    // staged value tid: kept unless it repeats its predecessor or is in the set
+    uint64_t v = 0;
+    int lb = 0;
+    bool keep = false;
+    if (tid < c) {
+        v = L.stage[tid];
+        lb = lower_bound(L.set, m, v);
+        keep = !(tid > 0 && L.stage[tid - 1] == v) && !(lb < m && L.set[lb] == v);
+    }
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) L.wsum[wave] = (uint32_t)__popcll(bal);
+    lds_barrier();
+    uint32_t before = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)), kept = 0;
+#pragma unroll
+    for (int q = 0; q < kWaves; ++q) {
+        const uint32_t t = L.wsum[q];
+        if (q < wave) before += t;
+        kept += t;
+    }
+    if (kept == 0) {
+        lds_barrier();  // wsum is free again
+        return m;
+    }
+    if (tid < c) L.kp[tid] = before;
+    if (tid == 0) L.kp[c] = kept;
+    lds_barrier();
+    // set values move up by the kept values below them: from the top down in runs of
+    // R * kBlock, read then written, so that no value is overwritten before it is read
+    for (int hi = m; hi > 0; hi -= R * kBlock) {
+        const int lo = hi - R * kBlock > 0 ? hi - R * kBlock : 0;
+        uint64_t x[R];
+        int np[R];
+#pragma unroll
+        for (int t = 0; t < R; ++t) {
+            const int i = lo + t * kBlock + tid;
+            np[t] = -1;
+            x[t] = 0;
+            if (i < hi) {
+                x[t] = L.set[i];
+                const int up = (int)L.kp[lower_bound(L.stage, c, x[t])];
+                if (up > 0 && i + up < s) np[t] = i + up;
+            }
+        }
+        lds_barrier();
+#pragma unroll
+        for (int t = 0; t < R; ++t)
+            if (np[t] >= 0) L.set[np[t]] = x[t];
+        lds_barrier();
+    }
+    if (keep && lb + (int)before < s) L.set[lb + (int)before] = v;
+    lds_barrier();
+    const int total = m + (int)kept;
+    return total < s ? total : s;
+}
+
+template <bool FWD, bool BIGK, int CAP>
+__global__ __launch_bounds__(kBlock) void sketch_seq_walk_kernel(SArgs a) {
+    __shared__ SetLds<CAP> L;
+    const Walk W = make_walk(a);
+    const int tid = threadIdx.x, s = (int)a.s, w = blockIdx.x;
+    const HashOf hf{a.seed};
+    if (tid < 3) L.ctr[tid] = 0u;
+    int ci = 0;  // the counter of the next round (the one after it is zero already)
+    __syncthreads();
+    for_each_piece(W, &L.first, [&](int64_t r, int64_t ps, int64_t pe, int64_t rend) {
+        int m = 0;
+        uint32_t staged = 0;  // values in the staging buffer (workgroup-uniform)
+        uint64_t T = kFill;
+        const int64_t c0 = ps >> 4, c1 = ((pe - 1) >> 4) + 1;
+        ChunkRaw nx = chunk_raw(W, (c0 + tid) << 4);
+        for (int64_t cb = c0; cb < c1; cb += kBlock) {
+            const int64_t c = cb + tid;
+            unsigned long long h[16];
+            const ChunkRaw cr = nx;
+            nx = chunk_raw(W, (c + kBlock) << 4);  // next round's chunk
+            uint32_t pend = chunk_keys<FWD, BIGK>(W, cr, c << 4, ps, pe, rend, hf, h);  // (past the piece: 0)
+            for (;;) {
+                const bool full = m == s;
+                uint32_t cm = 0u;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) cm |= (uint32_t)(!full || h[j] < T) << j;
+                pend &= cm;
+                if (pend) {
+#pragma unroll
+                    for (int j = 0; j < 16; ++j)
+                        if (((pend >> j) & 1u) && in_set(L.set, m, h[j])) pend &= ~(1u << j);
+                }
+                const uint32_t cnt = (uint32_t)__popc(pend);
+                if (cnt) {
+                    uint32_t at = staged + __hip_atomic_fetch_add(&L.ctr[ci], cnt, __ATOMIC_RELAXED,
+                                                                  __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        if ((pend >> j) & 1u) {
+                            if (at < (uint32_t)kStage) {
+                                L.stage[at] = h[j];
+                                pend &= ~(1u << j);
+                            }
+                            ++at;
+                        }
+                    }
+                }
+                lds_barrier();
+                const uint32_t total = staged + L.ctr[ci];
+                // the counter of the round before: every thread has read it (it passed this
+                // barrier), and its next adds come after the next barrier
+                if (tid == 0) L.ctr[(ci + 2) % 3] = 0u;
+                ci = (ci + 1) % 3;
+                if (total < (uint32_t)kStage) {
+                    staged = total;
+                    break;
+                }
+                m = merge_stage(L, m, s, kStage);
+                T = m == s ? L.set[s - 1] : kFill;
+                staged = 0;
+                if (total == (uint32_t)kStage) break;  // (else some lanes still hold candidates)
+            }
+        }
+        if (staged) m = merge_stage(L, m, s, (int)staged);
+        const int64_t ra = W.idx[r];
+        const int64_t nw = rend - ra - W.k > 0 ? rend - ra - W.k : 0;
+        if (ps == ra && pe == ra + nw) {  // the whole record: its row
+            uint64_t *row = a.sketches + r * (int64_t)s;
+            for (int i = tid; i < s; i += kBlock) row[i] = i < m ? L.set[i] : kFill;
+            if (tid == 0) a.sizes[r] = (uint32_t)m;
+        } else {  // a partial set: crosses this range's start (slot 2w) or only its end (2w + 1)
+            const int64_t slot = 2 * (int64_t)w + (ps == ra ? 1 : 0);
+            uint64_t *dst = a.part + slot * (int64_t)s;
+            for (int i = tid; i < m; i += kBlock) dst[i] = L.set[i];
+            if (tid == 0) a.psize[slot] = (uint32_t)m;
+        }
+        lds_barrier();  // the set is read out before the next piece's merges
+    });
+}
+
+// The records of no window: size 0 and a row of UINT64_MAX (no LDS; the walk never
+// meets them, and neither does the merge).
+__global__ __launch_bounds__(256) void sketch_seq_fill_kernel(SArgs a) {
+    const Walk W = make_walk(a);
+    const int s = (int)a.s;
+    for (int64_t r = blockIdx.x; r < a.n; r += gridDim.x) {
+        const int64_t ra = W.idx[r], re = W.idx[r + 1];
+        const int64_t nw = re - ra - W.k > 0 ? re - ra - W.k : 0;
+        const int64_t ps = ra > W.lo ? ra : W.lo, pe = ra + nw < W.hi ? ra + nw : W.hi;
+        if (ps < pe) continue;
+        uint64_t *row = a.sketches + r * (int64_t)s;
+        for (int i = threadIdx.x; i < s; i += 256) row[i] = kFill;
+        if (threadIdx.x == 0) a.sizes[r] = 0u;
+    }
+}
+
+// One workgroup per cut between two ranges (G - 1 of them): the record whose windows
+// lie on both sides of cut b, if there is one and b is the first cut it crosses (a
+// record over several cuts belongs to the first), has its partial sets folded.
+template <int CAP>
+__global__ __launch_bounds__(kBlock) void sketch_seq_merge_kernel(SArgs a) {
+    __shared__ SetLds<CAP> L;
+    const Walk W = make_walk(a);
+    const int tid = threadIdx.x, s = (int)a.s;
+    const int64_t b = blockIdx.x;
+    const int64_t cut = (W.c_lo + (b + 1) * W.cpw) << 4;  // first byte of range b + 1
+    if (cut <= W.lo || cut >= W.hi) return;
+    if (tid == 0) {  // last record r with idx[r] < cut: the only one that can have windows on both sides
+        int64_t lo = 0, hi = a.n - 1;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (W.idx[mid] < cut) lo = mid; else hi = mid - 1;
+        }
+        L.first = lo;
+    }
+    __syncthreads();
+    const int64_t r = L.first;
+    const int64_t ra = W.idx[r], re = W.idx[r + 1];
+    const int64_t nw = re - ra - W.k > 0 ? re - ra - W.k : 0;
+    const int64_t ps = ra > W.lo ? ra : W.lo, pe = ra + nw < W.hi ? ra + nw : W.hi;
+    if (ps >= cut || pe <= cut) return;  // no window before the cut, or none from it on
+    int64_t w0 = ((ps >> 4) - W.c_lo) / W.cpw, w1 = (((pe - 1) >> 4) - W.c_lo) / W.cpw;
+    if (w0 != b) return;  // an earlier cut's workgroup has the record
+    // (guard) the slots of this launch only
+    w0 = w0 < 0 ? 0 : (w0 > a.G - 1 ? a.G - 1 : w0);
+    w1 = w1 < w0 ? w0 : (w1 > a.G - 1 ? a.G - 1 : w1);
+    int m = 0;
+    uint64_t T = kFill;
+    for (int64_t w = w0; w <= w1; ++w) {
+        const int64_t slot = 2 * w + (w == w0 ? 1 : 0);
+        const uint64_t *src = a.part + slot * (int64_t)s;
+        uint32_t pm = a.psize[slot];
+        if (pm > a.s) pm = a.s;
+        for (int c0 = 0; c0 < (int)pm; c0 += kStage) {
+            if (m == s && src[c0] >= T) break;  // ascending: nothing below T is left
+            const int c = (int)pm - c0 < kStage ? (int)pm - c0 : kStage;
+            if (tid < c) L.stage[tid] = src[c0 + tid];
+            lds_barrier();
+            m = merge_stage(L, m, s, c);
+            T = m == s ? L.set[s - 1] : kFill;
+        }
+    }
+    uint64_t *row = a.sketches + r * (int64_t)s;
+    for (int i = tid; i < s; i += kBlock) row[i] = i < m ? L.set[i] : kFill;
+    if (tid == 0) a.sizes[r] = (uint32_t)m;
+}
+
+// ---------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------
+struct SLayout {
+    int64_t *widx;
+    uint32_t *psize;
+    uint64_t *part;
+    size_t bytes;
+};
+
+// walking workgroups: one range of at least kMinChunks chunks each over the chunks
+// data_bytes can hold (for any alignment of `data`), kWgPerCu per CU at most
+inline int walk_groups(uint64_t data_bytes, int cus) {
+    const uint64_t chunks = data_bytes / 16 + 3;
+    const uint64_t cap = (uint64_t)kWgPerCu * (uint64_t)(cus > 0 ? cus : 1);
+    uint64_t g = (chunks + kMinChunks - 1) / kMinChunks;
+    if (g > cap) g = cap;
+    return (int)(g < 1 ? 1 : g);
+}
+
+// the one layout behind the size query (base = null) and the bind
+inline SLayout layout(void *base, int64_t n, int G, uint32_t s) {
+    Carver c(base);
+    SLayout L;
+    L.widx = c.take<int64_t>((size_t)n + 1);
+    L.psize = c.take<uint32_t>(2 * (size_t)G);
+    L.part = c.take<uint64_t>(2 * (size_t)G * s);
+    L.bytes = c.total();
+    return L;
+}
+
+inline bool seq_args_ok(uint64_t num_seqs, uint64_t data_bytes, uint32_t sketch_size) {
+    return sketch_size >= 1 && sketch_size <= KMC_SKETCH_MAX_SIZE && num_seqs <= kMaxSeqs && data_bytes < (1ull << 62);
+}
+
+template <int CAP>
+void launch_seq(const SArgs &a, unsigned rec_grid, hipStream_t st) {
+    const bool fwd = a.flags & KMC_CANON_FORWARD, big = a.k >= 16;
+    const dim3 g((unsigned)a.G), b(kBlock);
+    if (fwd) {
+        if (big) hipLaunchKernelGGL((sketch_seq_walk_kernel<true, true, CAP>), g, b, 0, st, a);
+        else hipLaunchKernelGGL((sketch_seq_walk_kernel<true, false, CAP>), g, b, 0, st, a);
+    } else {
+        if (big) hipLaunchKernelGGL((sketch_seq_walk_kernel<false, true, CAP>), g, b, 0, st, a);
+        else hipLaunchKernelGGL((sketch_seq_walk_kernel<false, false, CAP>), g, b, 0, st, a);
+    }
+    hipLaunchKernelGGL(sketch_seq_fill_kernel, dim3(rec_grid), dim3(256), 0, st, a);
+    if (a.G > 1) hipLaunchKernelGGL((sketch_seq_merge_kernel<CAP>), dim3((unsigned)a.G - 1), b, 0, st, a);
+}
+
+DeviceCache q_ws;  // library-owned workspace
+
+}  // namespace
+}  // namespace kmc
+
+using namespace kmc;
+
+extern "C" size_t kmc_sketch_from_sequences_workspace_size(uint64_t num_seqs, uint64_t data_bytes, uint32_t sketch_size,
+                                                           int device) {
+    if (!seq_args_ok(num_seqs, data_bytes, sketch_size) || num_seqs == 0 || device < 0) return 0;
+    int cus = 0;  // (the arguments are checked before any HIP call)
+    if (device_cus(device, &cus)) return 0;
+    return layout(nullptr, (int64_t)num_seqs, walk_groups(data_bytes, cus), sketch_size).bytes;
+}
+
+extern "C" int kmc_sketch_from_sequences(const char *data, const int64_t *indices, uint64_t num_seqs,
+                                         uint64_t data_bytes, int k, unsigned flags, uint32_t sketch_size,
+                                         uint64_t seed, uint64_t *sketches, uint32_t *sketch_sizes, void *workspace,
+                                         size_t workspace_bytes, hipStream_t stream) {
+    if (k < 1 || k > KMC_CANON_MAX_K) return KMC_ERR_UNSUPPORTED_K;
+    if (!seq_args_ok(num_seqs, data_bytes, sketch_size)) return KMC_ERR_INVALID_ARG;
+    if (flags & ~(KMC_CANON_SOFTMASK | KMC_CANON_FORWARD)) return KMC_ERR_INVALID_ARG;
+    if (num_seqs == 0) return KMC_OK;
+    if (!indices || !sketches || !sketch_sizes) return KMC_ERR_INVALID_ARG;
+    if (data_bytes > 0 && !data) return KMC_ERR_INVALID_ARG;
+    int device = 0, cus = 0;
+    if (hipError_t he = hipGetDevice(&device)) return (int)he;
+    if (int e = device_cus(device, &cus)) return e;
+    const int64_t n = (int64_t)num_seqs;
+    const int G = walk_groups(data_bytes, cus);
+    const size_t need = layout(nullptr, n, G, sketch_size).bytes;
+    void *ws = workspace;
+    if (ws == nullptr) {
+        if (int e = q_ws.get(device, need, &ws)) return e;
+    } else {
+        if (workspace_bytes < need) return KMC_ERR_WORKSPACE;
+        if (reinterpret_cast<uintptr_t>(ws) & 7u) return KMC_ERR_ALIGNMENT;
+    }
+    const SLayout L = layout(ws, n, G, sketch_size);
+    // any `data` pointer: rounded down to 16 bytes, every offset moved up by the
+    // difference (kmc_count_canonical_hash's rule, applied on the device by prep)
+    const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
+    SArgs a;
+    a.data = data - mis;
+    a.indices = indices;
+    a.widx = L.widx;
+    a.n = n;
+    a.data_bytes = (int64_t)data_bytes;
+    a.mis = (int64_t)mis;
+    a.k = k;
+    a.flags = flags;
+    a.G = G;
+    a.s = sketch_size;
+    a.seed = seed;
+    a.part = L.part;
+    a.psize = L.psize;
+    a.sketches = sketches;
+    a.sizes = sketch_sizes;
+    const int64_t pg = (n + 1 + 255) / 256;
+    hipLaunchKernelGGL(sketch_seq_prep_kernel, dim3((unsigned)(pg < 4096 ? pg : 4096)), dim3(256), 0, stream, a);
+    const unsigned rec_grid = (unsigned)(n < kMaxGridX ? n : kMaxGridX);
+    if (sketch_size <= 1024) launch_seq<1024>(a, rec_grid, stream);
+    else if (sketch_size <= 4096) launch_seq<4096>(a, rec_grid, stream);
+    else launch_seq<KMC_SKETCH_MAX_SIZE>(a, rec_grid, stream);
+    return (int)hipGetLastError();
+}

@@ -184,6 +184,10 @@ def _load(path):
     L.kmc_sketch_from_counts.argtypes = [_P, _P, _P, _U64, _U64, ctypes.c_uint32, _U64, ctypes.c_uint32, _P, _P, _P,
                                          ctypes.c_size_t, _P]
     L.kmc_sketch_distances.argtypes = [_P, _P, _U64, ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P]
+    L.kmc_sketch_from_sequences_workspace_size.restype = ctypes.c_size_t
+    L.kmc_sketch_from_sequences_workspace_size.argtypes = [_U64, _U64, ctypes.c_uint32, ctypes.c_int]
+    L.kmc_sketch_from_sequences.argtypes = [_P, _P, _U64, _U64, ctypes.c_int, ctypes.c_uint, ctypes.c_uint32, _U64,
+                                            _P, _P, _P, ctypes.c_size_t, _P]
     L.minKmeres2_hip.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.kmc_count_canonical_hash.argtypes = [_P, _P, _U64, ctypes.c_int, ctypes.c_uint, _P, _P, _U64, _P,
                                            ctypes.POINTER(_U64), _P]
@@ -418,6 +422,32 @@ def sketch_from_counts(keys, counts, rec_offsets, sketch_size, seed=SKETCH_DEFAU
                                       int(seed) & _M64, int(min_count), _dptr(sk), _dptr(sizes), ws_ptr, ws_bytes,
                                       _stream(stream))
     _check(rc, "kmc_sketch_from_counts")
+    return sk, sizes
+
+
+def sketch_from_sequences_workspace_size(num_seqs, data_bytes, sketch_size, device=0):
+    return int(lib().kmc_sketch_from_sequences_workspace_size(num_seqs, data_bytes, sketch_size, device))
+
+
+def sketch_from_sequences(data, indices, k, sketch_size, flags=0, seed=SKETCH_DEFAULT_SEED, data_bytes=None,
+                          workspace=None, stream=None):
+    """Bottom-s MinHash sketches straight from the record buffer
+    (kmc_sketch_from_sequences): the rows and sizes sketch_from_counts gives for
+    count_canonical's lists of the same data, indices, k and flags, in one pass and
+    without those lists.  Returns (sketches int64 [n, s], sizes int32 [n])."""
+    import torch
+    n = int(indices.numel() - 1)
+    s = int(sketch_size)
+    if data_bytes is None:
+        data_bytes = data.numel()
+    sk = torch.empty((max(n, 0), max(s, 0)), dtype=torch.int64, device=indices.device)
+    sizes = torch.empty(max(n, 0), dtype=torch.int32, device=indices.device)
+    ws_ptr, ws_bytes = None, 0
+    if workspace is not None:
+        ws_ptr, ws_bytes = _dptr(workspace), workspace.numel() * workspace.element_size()
+    rc = lib().kmc_sketch_from_sequences(_dptr(data), _dptr(indices), n, int(data_bytes), k, flags, s,
+                                         int(seed) & _M64, _dptr(sk), _dptr(sizes), ws_ptr, ws_bytes, _stream(stream))
+    _check(rc, "kmc_sketch_from_sequences")
     return sk, sizes
 
 

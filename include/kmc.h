@@ -370,7 +370,35 @@ KMC_API int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *coun
  * No workspace; asynchronous on `stream`.  k in 1..KMC_CANON_MAX_K
  * (KMC_ERR_UNSUPPORTED_K); num_seqs < 2: KMC_OK, nothing written; null sketches,
  * sketch_sizes or out, or a sketch_size outside 1..KMC_SKETCH_MAX_SIZE:
- * KMC_ERR_INVALID_ARG. */
+ * KMC_ERR_INVALID_ARG.
+ *
+ * kmc_sketch_from_sequences: the same rows and sizes straight from the record
+ * buffer, without the canonical count: bit for bit what kmc_sketch_from_counts
+ * (min_count <= 1) writes for the lists kmc_count_canonical_hash returns for the
+ * same data, indices, k, flags, seed and sketch_size, so rows of both entry points
+ * may be concatenated.  One pass over the bases; a workgroup keeps the sketch_size
+ * smallest distinct hashes of the record it is in as a sorted set in LDS.  Exact
+ * for any content (repeats, low complexity, fewer distinct k-mers than
+ * sketch_size, records of no window): no capacity and no retry.  There is no
+ * min_count: that filter needs the counts.
+ *   data, indices, num_seqs, data_bytes  as kmc_count_dense: data a device pointer of
+ *                 any alignment readable for [0, data_bytes), indices device
+ *                 int64[num_seqs + 1] (offsets are clamped to [0, data_bytes])
+ *   k, flags      windows, record rules, keys and flags of kmc_count_canonical_hash,
+ *                 k in 1..KMC_CANON_MAX_K (KMC_ERR_UNSUPPORTED_K)
+ *   workspace     device scratch of kmc_sketch_from_sequences_workspace_size() bytes,
+ *                 8-byte aligned (KMC_ERR_ALIGNMENT), or NULL for a library-owned
+ *                 buffer under kmc_pair_distances' rule; KMC_ERR_WORKSPACE when
+ *                 smaller.  8 (num_seqs + 1) bytes of offsets and G (16 sketch_size
+ *                 + 8) bytes of partial sets (each array rounded up to 256 bytes),
+ *                 G = min(CUs, ceil((data_bytes / 16 + 3) / 1024)) walking
+ *                 workgroups: it does not grow with the number of windows, and
+ *                 grows with data_bytes only until G has reached the CU count.
+ * Asynchronous on `stream`, no host read-back; the work launched depends on the
+ * host arguments only.  KMC_ERR_INVALID_ARG: sketch_size 0 or above
+ * KMC_SKETCH_MAX_SIZE, unknown flag bits, num_seqs above 2^40, null indices,
+ * sketches or sketch_sizes, null data with data_bytes > 0.  num_seqs == 0: KMC_OK.
+ * The size query returns 0 on bad arguments (and needs no device for those). */
 #define KMC_SKETCH_MAX_SIZE 16384
 #define KMC_SKETCH_DEFAULT_SEED 42ull
 KMC_API size_t kmc_sketch_workspace_size(uint64_t num_seqs, uint64_t num_entries, uint32_t sketch_size, int device);
@@ -381,6 +409,12 @@ KMC_API int kmc_sketch_from_counts(const uint64_t *keys, const uint32_t *counts,
 KMC_API int kmc_sketch_distances(const uint64_t *sketches, const uint32_t *sketch_sizes, uint64_t num_seqs,
                                  uint32_t sketch_size, int k, float *out, uint32_t *shared, uint32_t *denom,
                                  hipStream_t stream);
+KMC_API size_t kmc_sketch_from_sequences_workspace_size(uint64_t num_seqs, uint64_t data_bytes,
+                                                        uint32_t sketch_size, int device);
+KMC_API int kmc_sketch_from_sequences(const char *data, const int64_t *indices, uint64_t num_seqs,
+                                      uint64_t data_bytes, int k, unsigned flags, uint32_t sketch_size,
+                                      uint64_t seed, uint64_t *sketches, uint32_t *sketch_sizes,
+                                      void *workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Tracing (the reference times step 1 with cudaEvents, main.cu:262-300): when set,

@@ -2,7 +2,10 @@
 """sketchbench.py — times kmc_sketch_from_counts, kmc_sketch_distances and
 kmc_pair_distances_sparse on the same canonical lists (HIP events, warm-up, median
 of --runs) and writes one JSON line per (input, sketch size) to --out
-(profiles/pr_sketch.jsonl).
+(profiles/pr_sketch.jsonl).  With --direct: kmc_sketch_from_sequences beside the
+two-step path kmc_count_canonical_hash + kmc_sketch_from_counts on the same inputs
+(rows asserted equal, both workspace sizes), and on one all-A record
+(profiles/pr_sketch_direct.jsonl).
 
 Inputs (synthetic, generated on the device):
   iid          8 x 50 Mbase independent records, k = 31
@@ -42,6 +45,22 @@ def timed(fn, runs, warmup=2):
     return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms), "runs": runs}
 
 
+def timed_wall(fn, runs, warmup=1):
+    """Host clock from an idle device to an idle device: what a caller waits for.
+    The measure for a path that synchronises and allocates inside (count_canonical)."""
+    import time
+    for _ in range(warmup):
+        fn()
+    ms = []
+    for _ in range(runs):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms), "runs": runs}
+
+
 def make_input(name, records, record_len, dev):
     data = torch.empty(records * (record_len + 1), dtype=torch.uint8, device=dev)
     kmc.synth_fill(data, records, record_len, 0x5EED0008)
@@ -62,6 +81,62 @@ def make_input(name, records, record_len, dev):
     return data, idx
 
 
+def direct_main(args, dev, shapes):
+    """--direct: the one-pass sketcher against the two-step path, in this process and
+    on this device.  The baseline is the two-step path as a caller runs it
+    (count_canonical reads the distinct total back; its output arrays hold 12 bytes
+    per input byte), timed as a whole and with the sketch stage alone."""
+    with open(args.out, "w") as out:
+        for name in args.inputs.split(","):
+            records, record_len, k = shapes[name]
+            record_len = max(int(record_len * args.scale), k + 1)
+            data, idx = make_input(name, records, record_len, dev)
+            idx_host = idx.cpu().numpy()
+            keys, counts, off = kmc.count_canonical(data, idx, k)
+            torch.cuda.synchronize()
+            for s in (int(x) for x in args.sizes.split(",")):
+                two = kmc.sketch_from_counts(keys, counts, off, s)
+                one = kmc.sketch_from_sequences(data, idx, k, s)
+                torch.cuda.synchronize()
+                assert torch.equal(one[0], two[0]) and torch.equal(one[1], two[1]), (name, s)
+                rec = {
+                    "input": name, "records": records, "record_len": record_len, "k": k, "sketch_size": s,
+                    "entries": int(keys.numel()), "rows_equal": True,
+                    "workspace_bytes_direct": kmc.sketch_from_sequences_workspace_size(records, data.numel(), s),
+                    "workspace_bytes_two_step": kmc.canonical_workspace_size(idx_host, k)
+                    + kmc.sketch_workspace_size(records, keys.numel(), s),
+                    "list_bytes_two_step": 12 * int(data.numel()),
+                    "kmc_sketch_from_sequences": timed(lambda: kmc.sketch_from_sequences(data, idx, k, s), args.runs),
+                    "kmc_sketch_from_counts": timed(lambda: kmc.sketch_from_counts(keys, counts, off, s), args.runs),
+                    # host clock, idle to idle, for the path that synchronises inside and for each half
+                    "two_step_wall": timed_wall(lambda: kmc.sketch_from_counts(*kmc.count_canonical(data, idx, k), s),
+                                                max(args.runs // 2, 3)),
+                    "count_canonical_wall": timed_wall(lambda: kmc.count_canonical(data, idx, k),
+                                                       max(args.runs // 2, 3)),
+                    "sketch_from_sequences_wall": timed_wall(lambda: kmc.sketch_from_sequences(data, idx, k, s),
+                                                             args.runs),
+                }
+                out.write(json.dumps(rec) + "\n")
+                out.flush()
+                print(json.dumps(rec), flush=True)
+            del keys, counts, off, data
+            torch.cuda.empty_cache()
+        # the degenerate record: one key, so the set never fills and every window passes
+        # the threshold; each is found in the set by a binary search and is not staged
+        n_a = max(int(50_000_000 * args.scale), 64)
+        data = torch.full((n_a + 1,), 65, dtype=torch.uint8, device=dev)
+        data[n_a] = 0
+        idx = torch.tensor([0, n_a + 1], dtype=torch.int64, device=dev)
+        for s in (int(x) for x in args.sizes.split(",")):
+            sk, sz = kmc.sketch_from_sequences(data, idx, 31, s)
+            torch.cuda.synchronize()
+            assert int(sz[0]) == 1 and int(sk[0, 1]) == -1  # the key of poly-A (= poly-T) alone, then the fill
+            rec = {"input": "all_a", "records": 1, "record_len": n_a, "k": 31, "sketch_size": s,
+                   "kmc_sketch_from_sequences": timed(lambda: kmc.sketch_from_sequences(data, idx, 31, s), args.runs)}
+            out.write(json.dumps(rec) + "\n")
+            print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(HERE), "profiles", "pr_sketch.jsonl"))
@@ -69,9 +144,14 @@ def main():
     ap.add_argument("--inputs", default="iid,copies_1pct,many")
     ap.add_argument("--sizes", default="1000,10000")
     ap.add_argument("--scale", type=float, default=1.0, help="scales the record lengths (a quick rehearsal: 0.01)")
+    ap.add_argument("--direct", action="store_true",
+                    help="time kmc_sketch_from_sequences beside kmc_count_canonical_hash + kmc_sketch_from_counts "
+                         "(rows asserted equal) and on all_a; --out profiles/pr_sketch_direct.jsonl")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     shapes = {"iid": (8, 50_000_000, 31), "copies_1pct": (8, 50_000_000, 31), "many": (4096, 100_000, 21)}
+    if args.direct:
+        return direct_main(args, dev, shapes)
     with open(args.out, "w") as out:
         for name in args.inputs.split(","):
             records, record_len, k = shapes[name]
