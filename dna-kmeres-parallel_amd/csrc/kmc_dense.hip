@@ -845,13 +845,8 @@ int run_dense(const Request &q, hipStream_t st) {
     Plan pl;
     int e = make_plan<K, Idx>(device, derive, wl, wh, pl);
     if (e) return e;
-    void *ws = q.ws;
-    if (ws == nullptr) {
-        e = g_ws.get(device, pl.ws_bytes, &ws);
-        if (e) return e;
-    } else if (q.ws_bytes < pl.ws_bytes) {
-        return KMC_ERR_WORKSPACE;
-    }
+    void *ws = nullptr;
+    if ((e = bind_workspace(g_ws, device, pl.ws_bytes, q.ws, q.ws_bytes, 0, &ws))) return e;
     const WsLayout L = ws_layout(ws, K, pl.G, pl.spill_cap);
     Params p;
     p.data = q.data;

@@ -216,13 +216,7 @@ extern "C" int kmc_pair_distances(const int32_t *sum, uint64_t sum_ld, const int
     const Plan P = plan_for(n, k, cus);
     if (P.tiles > 65535) return KMC_ERR_INVALID_ARG;
     void *ws = workspace;
-    if (P.ws) {
-        if (ws == nullptr) {
-            if ((e = d_ws.get(device, P.ws, &ws))) return e;
-        } else if (workspace_bytes < P.ws) {
-            return KMC_ERR_WORKSPACE;
-        }
-    }
+    if (P.ws && (e = bind_workspace(d_ws, device, P.ws, workspace, workspace_bytes, 0, &ws))) return e;
     DParams p;
     p.sum = sum;
     p.ld = sum_ld ? (int64_t)sum_ld : n;

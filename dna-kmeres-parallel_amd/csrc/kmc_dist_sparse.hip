@@ -339,12 +339,8 @@ extern "C" int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *c
     const int64_t n = (int64_t)num_seqs, E = (int64_t)num_entries;
     const SPlan P = plan_for(E, cus);
     const size_t need = layout(nullptr, n, E, P).bytes;
-    void *ws = workspace;
-    if (ws == nullptr) {
-        if ((e = s_ws.get(device, need, &ws))) return e;
-    } else if (workspace_bytes < need) {
-        return KMC_ERR_WORKSPACE;
-    }
+    void *ws = nullptr;
+    if ((e = bind_workspace(s_ws, device, need, workspace, workspace_bytes, 0, &ws))) return e;
     const SLayout L = layout(ws, n, E, P);
     SParams p;
     p.keys = keys;

@@ -40,7 +40,7 @@
 // (K3a -> K3b -> K4), 12 bytes of pairs written, read and written again.
 //
 // Host side (end of the file): kmc_count_canonical_hash_ex is a list of steps --
-// fetch_offsets, canon_plan (geometry), bind_workspace (canon_carve: the one place
+// fetch_offsets, canon_plan (geometry), bind_canon_workspace (canon_carve: the one place
 // the workspace layout is written, also behind the size query), upload_plan,
 // run_front (K1 .. K3b), then run_direct or run_placed (K4 and the output), which
 // share read_result for the error word.
@@ -1822,17 +1822,12 @@ int fetch_offsets(const int64_t *indices, int64_t n, int64_t mis, hipStream_t st
 }
 
 // The caller's workspace (checked) or the library's, bound into p.
-int bind_workspace(const CanonPlan &P, int64_t n, int device, void *workspace, size_t workspace_bytes, HParams &p,
-                   uint64_t *&bsum) {
+int bind_canon_workspace(const CanonPlan &P, int64_t n, int device, void *workspace, size_t workspace_bytes,
+                         HParams &p, uint64_t *&bsum) {
     const size_t total = canon_carve(P, n, nullptr, p, bsum);
-    if (workspace) {
-        if (workspace_bytes < total) return KMC_ERR_WORKSPACE;
-        // the layout's offsets are 256-byte multiples, and K3b / K4s move whole
-        // 16-byte pieces (and LDS-DMA dwords) of it
-        if (reinterpret_cast<uintptr_t>(workspace) & 255u) return KMC_ERR_ALIGNMENT;
-    } else if (int e = h_ws.get(device, total, &workspace)) {
-        return e;
-    }
+    // 256: the layout's offsets are 256-byte multiples, and K3b / K4s move whole
+    // 16-byte pieces (and LDS-DMA dwords) of it
+    if (int e = bind_workspace(h_ws, device, total, workspace, workspace_bytes, 256, &workspace)) return e;
     canon_carve(P, n, workspace, p, bsum);
     return 0;
 }
@@ -2094,7 +2089,7 @@ extern "C" int kmc_count_canonical_hash_ex(const char *data, const int64_t *indi
     // hold every window (the distinct keys are at most that many)
     p.direct = p.direct && keys && counts && capacity >= (uint64_t)P.windows;
     uint64_t *bsum = nullptr;
-    if (int e = bind_workspace(P, n, device, workspace, workspace_bytes, p, bsum)) return e;
+    if (int e = bind_canon_workspace(P, n, device, workspace, workspace_bytes, p, bsum)) return e;
     if (int e = upload_plan(p, P, hidx, stream)) return e;
     if (int e = run_front(p, P, bsum, stream)) return e;
     return p.direct ? run_direct(p, P, hidx, bsum, cus, stream, num_distinct)

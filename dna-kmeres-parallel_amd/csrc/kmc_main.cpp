@@ -27,8 +27,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "kmc.h"
@@ -252,259 +254,287 @@ float ms_between(hipEvent_t a, hipEvent_t b) {
     return ms;
 }
 
-// --sketch: the rows of every record (make_rows: from the canonical lists or, with
-// --sketch-direct, from the record buffer), their Mash distances, sketch_results.csv
-template <class MakeRows>
-int sketch_step(const Options &o, MakeRows make_rows, uint64_t n, hipStream_t st, hipEvent_t *ev) {
-    const uint32_t s = (uint32_t)o.sketch;
-    const uint64_t npairs = n * (n > 0 ? n - 1 : 0) / 2;
-    std::vector<float> dist(npairs);
-    uint64_t *d_sk = nullptr;
-    uint32_t *d_sz = nullptr;
-    float *d_out = nullptr;
-    HIPCHK(hipMalloc(&d_sk, (n * s > 0 ? n * s : 1) * sizeof(uint64_t)));
-    HIPCHK(hipMalloc(&d_sz, (n > 0 ? n : 1) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_out, (npairs > 0 ? npairs : 1) * sizeof(float)));
-    HIPCHK(hipEventRecord(ev[0], st));
-    KMCCHK(make_rows(s, d_sk, d_sz));
-    HIPCHK(hipEventRecord(ev[1], st));
-    KMCCHK(kmc_sketch_distances(d_sk, d_sz, n, s, o.k, d_out, nullptr, nullptr, st));
-    HIPCHK(hipEventRecord(ev[4], st));
-    HIPCHK(hipEventSynchronize(ev[4]));
-    if (!o.quiet) {
-        printf("Sketch (s=%u): %.3f ms\n", s, ms_between(ev[0], ev[1]));
-        printf("Sketch distances: %.3f ms\n", ms_between(ev[1], ev[4]));
-    }
-    if (npairs > 0) HIPCHK(hipMemcpy(dist.data(), d_out, npairs * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipFree(d_sk));
-    HIPCHK(hipFree(d_sz));
-    HIPCHK(hipFree(d_out));
-    return write_csv(o.out_dir + "/sketch_results.csv", dist) ? 1 : 0;
+// Move-only owners: every path out of run(), failing or not, releases what it acquired.
+// A release's own error is ignored: it must not turn a finished run into a failure.
+struct DevFree { void operator()(void *p) const { (void)hipFree(p); } };
+struct StreamDestroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+struct EventDestroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+struct FastaFree { void operator()(kmc_fasta *f) const { kmc_fasta_free(f); } };
+template <class T>
+using DevBuf = std::unique_ptr<T, DevFree>;
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
+using Fasta = std::unique_ptr<kmc_fasta, FastaFree>;
+
+// max(count, 1) elements: an empty input still gets a pointer the entry points take
+template <class T>
+hipError_t dev_alloc(DevBuf<T> &b, uint64_t count) {
+    T *p = nullptr;
+    const hipError_t e = hipMalloc(&p, std::max<uint64_t>(count, 1) * sizeof(T));
+    b.reset(p);
+    return e;
 }
 
-int run(const Options &o) {
-    const int k = o.k;
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev < 1) return fprintf(stderr, "kmc: no HIP device\n"), 1;
-    if (o.gpus > ndev) return fprintf(stderr, "kmc: --gpus %d but %d device(s)\n", o.gpus, ndev), 1;
-    HIPCHK(hipSetDevice(0));
-    hipStream_t st = nullptr;
-    HIPCHK(hipStreamCreate(&st));
-    hipEvent_t ev[6];
-    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+// null where it cannot be created: the hipEventRecord that follows reports that
+Event make_event() {
+    hipEvent_t e = nullptr;
+    return Event(hipEventCreate(&e) == hipSuccess ? e : nullptr);
+}
 
-    // the record buffer, resident on device 0 for steps 1 and 2: parsed on the GPU
-    // from the raw file bytes, or parsed on the host and copied
-    kmc_fasta *fa = nullptr;
-    char *d_data = nullptr;
-    int64_t *d_idx = nullptr;
-    uint64_t n = 0, bytes = 0;
+// the record buffer, resident on device 0 for steps 1 and 2
+struct Records {
+    Fasta fa;  // the host loader's copy (kmc_count_multi reads it); none after the GPU parse
+    DevBuf<char> data;
+    DevBuf<int64_t> idx;
     std::vector<int64_t> hidx;
+    uint64_t n = 0, bytes = 0;
+};
+
+// parsed on the GPU from the raw file bytes, or parsed on the host and copied
+int load(const Options &o, hipStream_t st, Records &r) {
     const bool host = o.host_loader || o.gpus > 1;
     const auto tl0 = std::chrono::steady_clock::now();
     if (host) {
+        kmc_fasta *fa = nullptr;
         KMCCHK(kmc_fasta_load(o.input.c_str(), o.dialect, o.max_seqs, &fa));
-        n = kmc_fasta_num_seqs(fa);
-        bytes = kmc_fasta_data_bytes(fa);
-        hidx.assign(kmc_fasta_indices(fa), kmc_fasta_indices(fa) + n + 1);
-        HIPCHK(hipMalloc(&d_data, bytes + 16));
-        HIPCHK(hipMalloc(&d_idx, (n + 1) * sizeof(int64_t)));
-        if (bytes) HIPCHK(hipMemcpyAsync(d_data, kmc_fasta_data(fa), bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_idx, hidx.data(), (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        r.fa.reset(fa);
+        r.n = kmc_fasta_num_seqs(fa);
+        r.bytes = kmc_fasta_data_bytes(fa);
+        r.hidx.assign(kmc_fasta_indices(fa), kmc_fasta_indices(fa) + r.n + 1);
+        HIPCHK(dev_alloc(r.data, r.bytes + 16));
+        HIPCHK(dev_alloc(r.idx, r.n + 1));
+        if (r.bytes) HIPCHK(hipMemcpyAsync(r.data.get(), kmc_fasta_data(fa), r.bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(r.idx.get(), r.hidx.data(), (r.n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
     } else {
-        KMCCHK(kmc_fasta_load_device(o.input.c_str(), o.dialect, o.max_seqs, &d_data, &bytes, &d_idx, &n, st));
-        hidx.resize(n + 1);
-        HIPCHK(hipMemcpy(hidx.data(), d_idx, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+        char *d_data = nullptr;
+        int64_t *d_idx = nullptr;
+        KMCCHK(kmc_fasta_load_device(o.input.c_str(), o.dialect, o.max_seqs, &d_data, &r.bytes, &d_idx, &r.n, st));
+        r.data.reset(d_data);
+        r.idx.reset(d_idx);
+        r.hidx.resize(r.n + 1);
+        HIPCHK(hipMemcpy(r.hidx.data(), d_idx, (r.n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
     }
     const auto tl1 = std::chrono::steady_clock::now();
     if (!o.quiet) {
-        printf("K = %d\n", k);
-        printf("Size all seqs:%" PRIu64 "\n", bytes);  // main.cu:166-167
-        printf("%" PRIu64 " sequences read .\n", n);
+        printf("K = %d\n", o.k);
+        printf("Size all seqs:%" PRIu64 "\n", r.bytes);  // main.cu:166-167
+        printf("%" PRIu64 " sequences read .\n", r.n);
         printf("Load (%s parse, file to device): %.1f ms\n", host ? "host" : "GPU",
                std::chrono::duration<double, std::milli>(tl1 - tl0).count());
     }
-    if (o.canonical && o.sketch_direct) {
-        // sketches straight from the record buffer: the canonical counter never runs
-        const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
-        if (int e = sketch_step(o, [&](uint32_t s, uint64_t *d_sk, uint32_t *d_sz) {
-                return kmc_sketch_from_sequences(d_data, d_idx, n, bytes, k, flags, s, KMC_SKETCH_DEFAULT_SEED, d_sk,
-                                                 d_sz, nullptr, 0, st);
-            }, n, st, ev))
-            return e;
-        HIPCHK(hipFree(d_data));
-        HIPCHK(hipFree(d_idx));
-        if (fa) kmc_fasta_free(fa);
-        return 0;
-    }
-    if (o.canonical) {
-        const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
-        const uint64_t cap = bytes > 0 ? bytes : 1;
-        uint64_t *d_keys = nullptr, *d_off = nullptr;
-        uint32_t *d_cnt = nullptr;
-        HIPCHK(hipMalloc(&d_keys, cap * 8));
-        HIPCHK(hipMalloc(&d_cnt, cap * 4));
-        HIPCHK(hipMalloc(&d_off, (n + 1) * 8));
-        uint64_t distinct = 0;
-        HIPCHK(hipEventRecord(ev[2], st));
-        KMCCHK(kmc_count_canonical_hash(d_data, d_idx, n, k, flags, d_keys, d_cnt, cap, d_off, &distinct, st));
-        HIPCHK(hipEventRecord(ev[3], st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (!o.quiet) {
-            printf("Canonical k=%d: %" PRIu64 " distinct (record, k-mer) pairs, %.3f ms\n", k, distinct,
-                   ms_between(ev[2], ev[3]));
-        }
-        if (!o.counts_path.empty()) {
-            std::vector<uint64_t> keys(distinct), off(n + 1);
-            std::vector<uint32_t> cnt(distinct);
-            if (distinct) {
-                HIPCHK(hipMemcpy(keys.data(), d_keys, distinct * 8, hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(cnt.data(), d_cnt, distinct * 4, hipMemcpyDeviceToHost));
-            }
-            HIPCHK(hipMemcpy(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost));
-            FILE *f = fopen(o.counts_path.c_str(), "w");
-            if (!f) return fprintf(stderr, "kmc: cannot write %s\n", o.counts_path.c_str()), 1;
-            for (uint64_t s = 0; s < n; ++s)
-                for (uint64_t i = off[s]; i < off[s + 1]; ++i)
-                    fprintf(f, "%" PRIu64 "\t%s\t%u\n", s, canon_kmer(keys[i], k).c_str(), cnt[i]);
-            if (fclose(f) != 0) return 1;
-        }
-        if (o.canon_distances) {
-            // step 2 on the sparse lists: both CSVs hold the one vector (exact integer sums)
-            const uint64_t npairs = n * (n > 0 ? n - 1 : 0) / 2;
-            std::vector<float> mins(npairs);
-            if (npairs > 0) {
-                float *d_mins = nullptr;
-                HIPCHK(hipMalloc(&d_mins, npairs * sizeof(float)));
-                HIPCHK(hipEventRecord(ev[4], st));
-                KMCCHK(kmc_pair_distances_sparse(d_keys, d_cnt, d_off, distinct, d_idx, n, k, d_mins, nullptr, 0, st));
-                HIPCHK(hipEventRecord(ev[5], st));
-                HIPCHK(hipEventSynchronize(ev[5]));
-                if (!o.quiet) {
-                    const float t2 = ms_between(ev[4], ev[5]);
-                    printf("Elapsed parallel step 2 timer: %g ms, %g secs\n", t2, t2 / 1000);
-                }
-                HIPCHK(hipMemcpy(mins.data(), d_mins, npairs * sizeof(float), hipMemcpyDeviceToHost));
-                HIPCHK(hipFree(d_mins));
-            }
-            if (write_csv(o.out_dir + "/parallel_results.csv", mins)) return 1;
-            if (write_csv(o.out_dir + "/sequential_results.csv", mins)) return 1;
-        }
-        if (o.sketch > 0) {
-            // sketches of the canonical lists and their Mash distances
-            if (int e = sketch_step(o, [&](uint32_t s, uint64_t *d_sk, uint32_t *d_sz) {
-                    return kmc_sketch_from_counts(d_keys, d_cnt, d_off, distinct, n, s, KMC_SKETCH_DEFAULT_SEED,
-                                                  (uint32_t)o.min_count, d_sk, d_sz, nullptr, 0, st);
-                }, n, st, ev))
-                return e;
-        }
-        HIPCHK(hipFree(d_keys));
-        HIPCHK(hipFree(d_cnt));
-        HIPCHK(hipFree(d_off));
-        HIPCHK(hipFree(d_data));
-        HIPCHK(hipFree(d_idx));
-        if (fa) kmc_fasta_free(fa);
-        return 0;
-    }
+    return 0;
+}
 
-    const uint64_t nb = 1ull << (2 * k);
-    int32_t *d_sum = nullptr;
-    HIPCHK(hipMalloc(&d_sum, (nb * n > 0 ? nb * n : 1) * sizeof(int32_t)));
-    int *d_idx32 = nullptr;
+// Step 2 of every mode: `enqueue` puts the n(n-1)/2 distances (a device vector) on st and
+// returns its status; `out` gets them.  Unless -q, `report` prints the mode's timer lines
+// from the events around that work.  Without a pair nothing runs or prints, unless `even_empty`.
+template <class Enqueue, class Report>
+int step2(const Options &o, uint64_t n, hipStream_t st, bool even_empty, std::vector<float> &out, Enqueue enqueue,
+          Report report) {
+    const uint64_t npairs = n * (n > 0 ? n - 1 : 0) / 2;
+    out.assign(npairs, 0.f);
+    if (npairs == 0 && !even_empty) return 0;
+    DevBuf<float> d_out;
+    Event t0 = make_event(), t1 = make_event();
+    HIPCHK(dev_alloc(d_out, npairs));
+    HIPCHK(hipEventRecord(t0.get(), st));
+    KMCCHK(enqueue(d_out.get()));
+    HIPCHK(hipEventRecord(t1.get(), st));
+    HIPCHK(hipEventSynchronize(t1.get()));
+    if (!o.quiet) report(t0.get(), t1.get());
+    if (npairs > 0) HIPCHK(hipMemcpy(out.data(), d_out.get(), npairs * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// --sketch: the rows of every record (make_rows: from the canonical lists or, with
+// --sketch-direct, from the record buffer), their Mash distances, sketch_results.csv
+template <class MakeRows>
+int sketch_step(const Options &o, MakeRows make_rows, uint64_t n, hipStream_t st) {
+    const uint32_t s = (uint32_t)o.sketch;
+    DevBuf<uint64_t> d_sk;
+    DevBuf<uint32_t> d_sz;
+    Event r0 = make_event(), r1 = make_event();
+    HIPCHK(dev_alloc(d_sk, n * s));
+    HIPCHK(dev_alloc(d_sz, n));
+    HIPCHK(hipEventRecord(r0.get(), st));
+    KMCCHK(make_rows(s, d_sk.get(), d_sz.get()));
+    HIPCHK(hipEventRecord(r1.get(), st));
+    const auto distances = [&](float *d_out) {
+        return kmc_sketch_distances(d_sk.get(), d_sz.get(), n, s, o.k, d_out, nullptr, nullptr, st);
+    };
+    const auto timers = [&](hipEvent_t t0, hipEvent_t t1) {
+        printf("Sketch (s=%u): %.3f ms\n", s, ms_between(r0.get(), r1.get()));
+        printf("Sketch distances: %.3f ms\n", ms_between(t0, t1));
+    };
+    std::vector<float> dist;
+    if (int e = step2(o, n, st, true, dist, distances, timers)) return e;
+    return write_csv(o.out_dir + "/sketch_results.csv", dist) ? 1 : 0;
+}
+
+// --canonical --sketch S --sketch-direct: the canonical counter never runs
+int run_sketch_direct(const Options &o, const Records &r, hipStream_t st) {
+    const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
+    return sketch_step(o, [&](uint32_t s, uint64_t *d_sk, uint32_t *d_sz) {
+        return kmc_sketch_from_sequences(r.data.get(), r.idx.get(), r.n, r.bytes, o.k, flags, s,
+                                         KMC_SKETCH_DEFAULT_SEED, d_sk, d_sz, nullptr, 0, st);
+    }, r.n, st);
+}
+
+// --canonical: the sparse counts, then their dump, step 2 on them and their sketches
+int run_canonical(const Options &o, const Records &r, hipStream_t st) {
+    const int k = o.k;
+    const uint64_t n = r.n, cap = r.bytes > 0 ? r.bytes : 1;
+    const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
+    DevBuf<uint64_t> d_keys, d_off;
+    DevBuf<uint32_t> d_cnt;
+    Event c0 = make_event(), c1 = make_event();
+    HIPCHK(dev_alloc(d_keys, cap));
+    HIPCHK(dev_alloc(d_cnt, cap));
+    HIPCHK(dev_alloc(d_off, n + 1));
+    uint64_t distinct = 0;
+    HIPCHK(hipEventRecord(c0.get(), st));
+    KMCCHK(kmc_count_canonical_hash(r.data.get(), r.idx.get(), n, k, flags, d_keys.get(), d_cnt.get(), cap,
+                                    d_off.get(), &distinct, st));
+    HIPCHK(hipEventRecord(c1.get(), st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!o.quiet) {
+        printf("Canonical k=%d: %" PRIu64 " distinct (record, k-mer) pairs, %.3f ms\n", k, distinct,
+               ms_between(c0.get(), c1.get()));
+    }
+    if (!o.counts_path.empty()) {
+        std::vector<uint64_t> keys(distinct), off(n + 1);
+        std::vector<uint32_t> cnt(distinct);
+        if (distinct) {
+            HIPCHK(hipMemcpy(keys.data(), d_keys.get(), distinct * 8, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(cnt.data(), d_cnt.get(), distinct * 4, hipMemcpyDeviceToHost));
+        }
+        HIPCHK(hipMemcpy(off.data(), d_off.get(), (n + 1) * 8, hipMemcpyDeviceToHost));
+        FILE *f = fopen(o.counts_path.c_str(), "w");
+        if (!f) return fprintf(stderr, "kmc: cannot write %s\n", o.counts_path.c_str()), 1;
+        for (uint64_t s = 0; s < n; ++s)
+            for (uint64_t i = off[s]; i < off[s + 1]; ++i)
+                fprintf(f, "%" PRIu64 "\t%s\t%u\n", s, canon_kmer(keys[i], k).c_str(), cnt[i]);
+        if (fclose(f) != 0) return 1;
+    }
+    if (o.canon_distances) {
+        // step 2 on the sparse lists: both CSVs hold the one vector (exact integer sums)
+        const auto sparse = [&](float *d_mins) {
+            return kmc_pair_distances_sparse(d_keys.get(), d_cnt.get(), d_off.get(), distinct, r.idx.get(), n, k,
+                                             d_mins, nullptr, 0, st);
+        };
+        const auto timer = [](hipEvent_t t0, hipEvent_t t1) {
+            const float t2 = ms_between(t0, t1);
+            printf("Elapsed parallel step 2 timer: %g ms, %g secs\n", t2, t2 / 1000);
+        };
+        std::vector<float> mins;
+        if (int e = step2(o, n, st, false, mins, sparse, timer)) return e;
+        if (write_csv(o.out_dir + "/parallel_results.csv", mins)) return 1;
+        if (write_csv(o.out_dir + "/sequential_results.csv", mins)) return 1;
+    }
+    if (o.sketch == 0) return 0;
+    // sketches of the canonical lists and their Mash distances
+    return sketch_step(o, [&](uint32_t s, uint64_t *d_sk, uint32_t *d_sz) {
+        return kmc_sketch_from_counts(d_keys.get(), d_cnt.get(), d_off.get(), distinct, n, s, KMC_SKETCH_DEFAULT_SEED,
+                                      (uint32_t)o.min_count, d_sk, d_sz, nullptr, 0, st);
+    }, n, st);
+}
+
+// the dense histogram (k <= 13) and step 2 on it: the reference's flow
+int run_dense(const Options &o, const Records &r, hipStream_t st) {
+    const int k = o.k;
+    const uint64_t n = r.n, nb = 1ull << (2 * k);
+    DevBuf<int32_t> d_sum;
+    DevBuf<int> d_idx32;
+    Event s0 = make_event(), s1 = make_event();
+    HIPCHK(dev_alloc(d_sum, nb * n));
     if (o.dropin) {
-        if (bytes > (uint64_t)INT32_MAX) return fprintf(stderr, "kmc: --dropin needs < 2 GiB of sequence\n"), 1;
-        std::vector<int> i32(hidx.begin(), hidx.end());
-        HIPCHK(hipMalloc(&d_idx32, (n + 1) * sizeof(int)));
-        HIPCHK(hipMemcpy(d_idx32, i32.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice));
+        if (r.bytes > (uint64_t)INT32_MAX) return fprintf(stderr, "kmc: --dropin needs < 2 GiB of sequence\n"), 1;
+        std::vector<int> i32(r.hidx.begin(), r.hidx.end());
+        HIPCHK(dev_alloc(d_idx32, n + 1));
+        HIPCHK(hipMemcpy(d_idx32.get(), i32.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice));
     }
 
     // step 1 (main.cu:287-300)
-    HIPCHK(hipEventRecord(ev[2], st));
+    HIPCHK(hipEventRecord(s0.get(), st));
     std::vector<int32_t> hsum;
     if (o.dropin) {
-        KMCCHK(sumKmereCoincidencesGlobalMemory_hip(d_data, d_idx32, (unsigned)n, d_sum, st));
+        KMCCHK(sumKmereCoincidencesGlobalMemory_hip(r.data.get(), d_idx32.get(), (unsigned)n, d_sum.get(), st));
     } else if (o.gpus > 1) {
         // host-buffer multi-GPU count (shards + RCCL all-reduce), result on the host
         hsum.assign(nb * n, 0);
-        KMCCHK(kmc_count_multi(kmc_fasta_data(fa), hidx.data(), n, bytes, k, o.gpus, nullptr, hsum.data(), nullptr));
+        KMCCHK(kmc_count_multi(kmc_fasta_data(r.fa.get()), r.hidx.data(), n, r.bytes, k, o.gpus, nullptr, hsum.data(),
+                               nullptr));
         if (!hsum.empty())
-            HIPCHK(hipMemcpyAsync(d_sum, hsum.data(), hsum.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_sum.get(), hsum.data(), hsum.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     } else {
-        KMCCHK(kmc_count_dense(d_data, d_idx, n, bytes, k, d_sum, nullptr, nullptr, 0, st));
+        KMCCHK(kmc_count_dense(r.data.get(), r.idx.get(), n, r.bytes, k, d_sum.get(), nullptr, nullptr, 0, st));
     }
-    HIPCHK(hipEventRecord(ev[3], st));
-    HIPCHK(hipEventSynchronize(ev[3]));
+    HIPCHK(hipEventRecord(s1.get(), st));
+    HIPCHK(hipEventSynchronize(s1.get()));
     if (o.gpus <= 1) {  // the deferred status of the (asynchronous) count on this device
         int dev = 0;
         HIPCHK(hipGetDevice(&dev));
         KMCCHK(kmc_dense_status(dev));
     }
-    const float t1 = ms_between(ev[2], ev[3]);
+    const float ms1 = ms_between(s0.get(), s1.get());
     if (!o.quiet) {
-        printf("Elapsed parallel timer step 1: %g ms, %g secs\n", t1, t1 / 1000);  // main.cu:300
+        printf("Elapsed parallel timer step 1: %g ms, %g secs\n", ms1, ms1 / 1000);  // main.cu:300
     }
 
-    // step 2 (main.cu:326-344)
-    std::vector<float> mins, seq;
-    const uint64_t npairs = n * (n > 0 ? n - 1 : 0) / 2;
-    if (o.distances && npairs > 0) {
-        float *d_mins = nullptr;
-        HIPCHK(hipMalloc(&d_mins, npairs * sizeof(float)));
-        HIPCHK(hipMemsetAsync(d_mins, 0, npairs * sizeof(float), st));
-        HIPCHK(hipEventRecord(ev[4], st));
-        if (o.dropin) {
-            for (uint64_t i = 0; i < n; ++i) {
-                KMCCHK(minKmeres2_hip(d_sum, d_mins, (int)n, (int)i, d_idx32, st));
-                HIPCHK(hipStreamSynchronize(st));  // main.cu:328
-            }
-        } else {
-            KMCCHK(kmc_pair_distances(d_sum, n, d_idx, n, k, d_mins, nullptr, 0, st));
-        }
-        HIPCHK(hipEventRecord(ev[5], st));
-        HIPCHK(hipEventSynchronize(ev[5]));
-        const float t2 = ms_between(ev[4], ev[5]);
-        if (!o.quiet) {
-            printf("Elapsed parallel step 2 timer: %g ms, %g secs\n", t2, t2 / 1000);  // main.cu:344
-            const float tt = ms_between(ev[2], ev[5]);
-            printf("Total time elapsed parallel: %g ms, %g secs\n", tt, tt / 1000);  // main.cu:350
-        }
-        mins.resize(npairs);
-        HIPCHK(hipMemcpy(mins.data(), d_mins, npairs * sizeof(float), hipMemcpyDeviceToHost));
-        if (o.dropin) {
-            // the CPU path's distances (exact integer sums) for sequential_results.csv
-            KMCCHK(kmc_pair_distances(d_sum, n, d_idx, n, k, d_mins, nullptr, 0, st));
-            seq.resize(npairs);
-            HIPCHK(hipMemcpy(seq.data(), d_mins, npairs * sizeof(float), hipMemcpyDeviceToHost));
-        }
-        HIPCHK(hipFree(d_mins));
-    }
     if (o.distances) {
-        // the reference writes both files for diffing (main.cu:178, 194-202, 216, 351-358):
-        // sequential_results.csv holds sequentialKmerCount2's distances (exact integer
-        // sums, here kmc_pair_distances), parallel_results.csv the GPU path's (the
-        // same numbers, or minKmeres2's float sums with --dropin)
+        // step 2 (main.cu:326-344).  The reference writes both files for diffing (main.cu:178,
+        // 194-202, 216, 351-358): sequential_results.csv holds the CPU path's exact integer sums
+        // (`exact`), parallel_results.csv the GPU path's (the same, or `reference`'s float sums)
+        const auto exact = [&](float *d_mins) {
+            return kmc_pair_distances(d_sum.get(), n, r.idx.get(), n, k, d_mins, nullptr, 0, st);
+        };
+        const auto reference = [&](float *d_mins) {  // --dropin: one launch per record
+            int e = hipMemsetAsync(d_mins, 0, n * (n - 1) / 2 * sizeof(float), st);
+            for (uint64_t i = 0; i < n && !e; ++i) {
+                e = minKmeres2_hip(d_sum.get(), d_mins, (int)n, (int)i, d_idx32.get(), st);
+                if (!e) e = hipStreamSynchronize(st);  // main.cu:328
+            }
+            return e;
+        };
+        const auto timers = [&](hipEvent_t t0, hipEvent_t t1) {
+            const float t2 = ms_between(t0, t1), tt = ms_between(s0.get(), t1);
+            printf("Elapsed parallel step 2 timer: %g ms, %g secs\n", t2, t2 / 1000);  // main.cu:344
+            printf("Total time elapsed parallel: %g ms, %g secs\n", tt, tt / 1000);    // main.cu:350
+        };
+        std::vector<float> mins, seq;
+        const int e2 = o.dropin ? step2(o, n, st, false, mins, reference, timers)
+                                : step2(o, n, st, false, mins, exact, timers);
+        if (e2) return e2;
+        if (o.dropin)  // untimed
+            if (int e = step2(o, n, st, false, seq, exact, [](hipEvent_t, hipEvent_t) {})) return e;
         if (write_csv(o.out_dir + "/parallel_results.csv", mins)) return 1;
         if (write_csv(o.out_dir + "/sequential_results.csv", o.dropin ? seq : mins)) return 1;
     }
     if (!o.counts_path.empty()) {
         if (hsum.empty() && nb * n > 0) {
             hsum.resize(nb * n);
-            HIPCHK(hipMemcpy(hsum.data(), d_sum, hsum.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hsum.data(), d_sum.get(), hsum.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
         if (write_counts(o.counts_path, hsum, n, k)) return 1;
     }
-    HIPCHK(hipFree(d_sum));
-    if (d_idx32) HIPCHK(hipFree(d_idx32));
-    HIPCHK(hipFree(d_data));
-    HIPCHK(hipFree(d_idx));
-    for (auto &e : ev) HIPCHK(hipEventDestroy(e));
-    HIPCHK(hipStreamDestroy(st));
-    if (fa) kmc_fasta_free(fa);
     return 0;
 }
 
+int run(const Options &o) {
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (ndev < 1) return fprintf(stderr, "kmc: no HIP device\n"), 1;
+    if (o.gpus > ndev) return fprintf(stderr, "kmc: --gpus %d but %d device(s)\n", o.gpus, ndev), 1;
+    HIPCHK(hipSetDevice(0));
+    hipStream_t s = nullptr;
+    HIPCHK(hipStreamCreate(&s));
+    const Stream st(s);
+    Records r;  // (after the stream: released before it)
+    if (int e = load(o, s, r)) return e;
+    if (!o.canonical) return run_dense(o, r, s);
+    return o.sketch_direct ? run_sketch_direct(o, r, s) : run_canonical(o, r, s);
+}
 
 // `kmc synth OUT.fa RECORDS LENGTH [SEED]`: the SURVEY.md §8(d) benchmark input as a
 // FASTA file: records of LENGTH bases in 80 columns, '>r%04d' headers, records

@@ -1068,12 +1068,8 @@ int run_radix(const kmc_dense_args *a, int64_t ibias, hipStream_t st, bool size_
         *size_out = total;
         return 0;
     }
-    void *ws = a->workspace;
-    if (ws == nullptr) {
-        if ((e = r_ws.get(device, total, &ws))) return e;
-    } else if (a->workspace_bytes < total) {
-        return KMC_ERR_WORKSPACE;
-    }
+    void *ws = nullptr;
+    if ((e = bind_workspace(r_ws, device, total, a->workspace, a->workspace_bytes, 0, &ws))) return e;
     const RLayout L = r_layout(ws, K, n, G, ent_cap, sampled, ovf_cap);
     RParams p;
     p.data = a->data;

@@ -430,12 +430,8 @@ extern "C" int kmc_sketch_from_counts(const uint64_t *keys, const uint32_t *coun
     if (e) return e;
     const int64_t n = (int64_t)num_seqs, E = (int64_t)num_entries;
     const size_t need = layout(nullptr, n).bytes;
-    void *ws = workspace;
-    if (ws == nullptr) {
-        if ((e = s_ws.get(device, need, &ws))) return e;
-    } else if (workspace_bytes < need) {
-        return KMC_ERR_WORKSPACE;
-    }
+    void *ws = nullptr;
+    if ((e = bind_workspace(s_ws, device, need, workspace, workspace_bytes, 0, &ws))) return e;
     const KLayout L = layout(ws, n);
     int64_t g = (E + kWalkPer - 1) / kWalkPer;
     if (g > 2LL * cus) g = 2LL * cus;

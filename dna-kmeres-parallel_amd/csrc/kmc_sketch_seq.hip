@@ -469,13 +469,8 @@ extern "C" int kmc_sketch_from_sequences(const char *data, const int64_t *indice
     const int64_t n = (int64_t)num_seqs;
     const int G = walk_groups(data_bytes, cus);
     const size_t need = layout(nullptr, n, G, sketch_size).bytes;
-    void *ws = workspace;
-    if (ws == nullptr) {
-        if (int e = q_ws.get(device, need, &ws)) return e;
-    } else {
-        if (workspace_bytes < need) return KMC_ERR_WORKSPACE;
-        if (reinterpret_cast<uintptr_t>(ws) & 7u) return KMC_ERR_ALIGNMENT;
-    }
+    void *ws = nullptr;
+    if (int e = bind_workspace(q_ws, device, need, workspace, workspace_bytes, 8, &ws)) return e;
     const SLayout L = layout(ws, n, G, sketch_size);
     // any `data` pointer: rounded down to 16 bytes, every offset moved up by the
     // difference (kmc_count_canonical_hash's rule, applied on the device by prep)

@@ -1,7 +1,7 @@
 // kmc_workspace.h — host-side workspace plumbing shared by the .hip translation
 // units (no kernels, no device code): the 256-byte rounding of every layout, the
-// carver that lays a workspace out, the per-device grow-only scratch buffer, and
-// the cached CU count of a device.
+// carver that lays a workspace out, the per-device grow-only scratch buffer, the
+// choice between it and a caller's workspace, and the cached CU count of a device.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -72,6 +72,17 @@ private:
     std::mutex mu_;
     std::vector<Buf> buf_;
 };
+
+// The workspace of one call, `need` bytes: the caller's when it gave one (size checked first,
+// then `align`, a power of two, or 0 for any pointer), else `cache`'s buffer on `device`.
+inline int bind_workspace(DeviceCache &cache, int device, size_t need, void *caller, size_t caller_bytes,
+                          size_t align, void **out) {
+    if (caller == nullptr) return cache.get(device, need, out);
+    if (caller_bytes < need) return KMC_ERR_WORKSPACE;
+    if (align && (reinterpret_cast<uintptr_t>(caller) & (align - 1))) return KMC_ERR_ALIGNMENT;
+    *out = caller;
+    return 0;
+}
 
 // Compute units of `device`, asked of the runtime once per device and process
 // (one table for every translation unit: an inline function's statics are shared).

@@ -228,6 +228,20 @@ def _dptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _ws(workspace):
+    """(pointer, bytes) of a caller's workspace tensor; None: (None, 0), the library's own."""
+    if workspace is None:
+        return None, 0
+    return _dptr(workspace), workspace.numel() * workspace.element_size()
+
+
+def _sketch_out(n, s, device):
+    """Uninitialised (sketches int64 [n, s], sizes int32 [n]) of the sketch entry points."""
+    import torch
+    return (torch.empty((max(n, 0), max(s, 0)), dtype=torch.int64, device=device),
+            torch.empty(max(n, 0), dtype=torch.int32, device=device))
+
+
 def dropin_count(data, indices, num_seqs=None, out=None, stream=None):
     """Exact drop-in of the reference launch (k = 3): returns int32 sum[4^3 * n]
     in the reference layout sum[s + n*code] (flat, like the reference)."""
@@ -254,11 +268,8 @@ def count_dense(data, indices, k, data_bytes=None, invalid=False, workspace=None
     if out is None:
         out = torch.empty((nb, n), dtype=torch.int32, device=data.device)
     inv = torch.empty(n, dtype=torch.int32, device=data.device) if invalid else None
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        ws_ptr, ws_bytes = _dptr(workspace), workspace.numel() * workspace.element_size()
     rc = lib().kmc_count_dense(_dptr(data), _dptr(indices), n, data_bytes, k, _dptr(out), _dptr(inv),
-                               ws_ptr, ws_bytes, _stream(stream))
+                               *_ws(workspace), _stream(stream))
     _check(rc, "kmc_count_dense")
     return out, inv
 
@@ -281,9 +292,7 @@ def dense_args(data, indices, k, out, read=(0, None), win=(0, None), ld=0, inval
     a.read_hi = read[1] if read[1] is not None else data_offset + data.numel()
     a.win_lo = win[0]
     a.win_hi = win[1] if win[1] is not None else data_offset + data.numel()
-    if workspace is not None:
-        a.workspace = ctypes.c_void_p(workspace.data_ptr())
-        a.workspace_bytes = workspace.numel() * workspace.element_size()
+    a.workspace, a.workspace_bytes = _ws(workspace)
     a.status = _dptr(status)
     return a
 
@@ -322,10 +331,7 @@ def pair_distances(counts, indices, k, num_seqs=None, ld=0, out=None, workspace=
     n = int(num_seqs if num_seqs is not None else indices.numel() - 1)
     if out is None:
         out = torch.empty(max(n * (n - 1) // 2, 0), dtype=torch.float32, device=counts.device)
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        ws_ptr, ws_bytes = _dptr(workspace), workspace.numel() * workspace.element_size()
-    rc = lib().kmc_pair_distances(_dptr(counts), ld, _dptr(indices), n, k, _dptr(out), ws_ptr, ws_bytes,
+    rc = lib().kmc_pair_distances(_dptr(counts), ld, _dptr(indices), n, k, _dptr(out), *_ws(workspace),
                                   _stream(stream))
     _check(rc, "kmc_pair_distances")
     return out
@@ -350,14 +356,9 @@ def count_canonical(data, indices, k, flags=0, capacity=None, workspace=None, st
     counts = torch.empty(capacity, dtype=torch.int32, device=data.device)
     off = torch.zeros(max(n + 1, 1), dtype=torch.int64, device=data.device)
     tot = _U64(0)
-    if workspace is None:
-        rc = lib().kmc_count_canonical_hash(_dptr(data), _dptr(indices), n, k, flags, _dptr(keys), _dptr(counts),
-                                            capacity, _dptr(off), ctypes.byref(tot), _stream(stream))
-    else:
-        rc = lib().kmc_count_canonical_hash_ex(_dptr(data), _dptr(indices), n, k, flags, _dptr(keys),
-                                               _dptr(counts), capacity, _dptr(off), ctypes.byref(tot),
-                                               _dptr(workspace), workspace.numel() * workspace.element_size(),
-                                               _stream(stream))
+    # (kmc_count_canonical_hash is this call with no workspace)
+    rc = lib().kmc_count_canonical_hash_ex(_dptr(data), _dptr(indices), n, k, flags, _dptr(keys), _dptr(counts),
+                                           capacity, _dptr(off), ctypes.byref(tot), *_ws(workspace), _stream(stream))
     _check(rc, "kmc_count_canonical_hash")
     t = int(tot.value)
     return keys[:t], counts[:t], off
@@ -385,11 +386,8 @@ def pair_distances_sparse(keys, counts, rec_offsets, indices, k, num_entries=Non
         num_entries = keys.numel()
     if out is None:
         out = torch.empty(max(n * (n - 1) // 2, 0), dtype=torch.float32, device=indices.device)
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        ws_ptr, ws_bytes = _dptr(workspace), workspace.numel() * workspace.element_size()
     rc = lib().kmc_pair_distances_sparse(_dptr(keys), _dptr(counts), _dptr(rec_offsets), int(num_entries),
-                                         _dptr(indices), n, k, _dptr(out), ws_ptr, ws_bytes, _stream(stream))
+                                         _dptr(indices), n, k, _dptr(out), *_ws(workspace), _stream(stream))
     _check(rc, "kmc_pair_distances_sparse")
     return out
 
@@ -408,18 +406,13 @@ def sketch_from_counts(keys, counts, rec_offsets, sketch_size, seed=SKETCH_DEFAU
     count_canonical returns them (`counts` may be None while min_count <= 1).
     Returns (sketches int64 [n, s]: uint64 hashes ascending, then all-ones fill;
     sizes int32 [n])."""
-    import torch
     n = int(rec_offsets.numel() - 1)
     s = int(sketch_size)
     if num_entries is None:
         num_entries = keys.numel()
-    sk = torch.empty((max(n, 0), max(s, 0)), dtype=torch.int64, device=rec_offsets.device)
-    sizes = torch.empty(max(n, 0), dtype=torch.int32, device=rec_offsets.device)
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        ws_ptr, ws_bytes = _dptr(workspace), workspace.numel() * workspace.element_size()
+    sk, sizes = _sketch_out(n, s, rec_offsets.device)
     rc = lib().kmc_sketch_from_counts(_dptr(keys), _dptr(counts), _dptr(rec_offsets), int(num_entries), n, s,
-                                      int(seed) & _M64, int(min_count), _dptr(sk), _dptr(sizes), ws_ptr, ws_bytes,
+                                      int(seed) & _M64, int(min_count), _dptr(sk), _dptr(sizes), *_ws(workspace),
                                       _stream(stream))
     _check(rc, "kmc_sketch_from_counts")
     return sk, sizes
@@ -435,18 +428,14 @@ def sketch_from_sequences(data, indices, k, sketch_size, flags=0, seed=SKETCH_DE
     (kmc_sketch_from_sequences): the rows and sizes sketch_from_counts gives for
     count_canonical's lists of the same data, indices, k and flags, in one pass and
     without those lists.  Returns (sketches int64 [n, s], sizes int32 [n])."""
-    import torch
     n = int(indices.numel() - 1)
     s = int(sketch_size)
     if data_bytes is None:
         data_bytes = data.numel()
-    sk = torch.empty((max(n, 0), max(s, 0)), dtype=torch.int64, device=indices.device)
-    sizes = torch.empty(max(n, 0), dtype=torch.int32, device=indices.device)
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        ws_ptr, ws_bytes = _dptr(workspace), workspace.numel() * workspace.element_size()
+    sk, sizes = _sketch_out(n, s, indices.device)
     rc = lib().kmc_sketch_from_sequences(_dptr(data), _dptr(indices), n, int(data_bytes), k, flags, s,
-                                         int(seed) & _M64, _dptr(sk), _dptr(sizes), ws_ptr, ws_bytes, _stream(stream))
+                                         int(seed) & _M64, _dptr(sk), _dptr(sizes), *_ws(workspace),
+                                         _stream(stream))
     _check(rc, "kmc_sketch_from_sequences")
     return sk, sizes
 

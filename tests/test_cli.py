@@ -148,3 +148,57 @@ def test_cli_canonical_dump_equals_oracle(cuda, oracle, tmp_path, k):
             kmer = "".join("ACGT"[(key >> (2 * (k - 1 - p))) & 3] for p in range(k))
             exp[(s, kmer)] = int(counts[i])
     assert got == exp
+
+
+def first_lines(stdout, prefixes):
+    """Index of the first stdout line that starts with each prefix (None: absent)."""
+    lines = stdout.splitlines()
+    return [next((i for i, l in enumerate(lines) if l.startswith(p)), None) for p in prefixes]
+
+
+@pytest.mark.gpu
+def test_cli_canonical_prints_its_steps_in_order(cuda, tmp_path):
+    base = ["--canonical", "-k", 21, "--sketch", 16, "--out", tmp_path]
+    r = run(base + ["--distances", fixture_path("random")])
+    assert r.returncode == 0, r.stderr
+    at = first_lines(r.stdout, ("Canonical k=21:", "Elapsed parallel step 2 timer:", "Sketch (s=16):",
+                                "Sketch distances:"))
+    assert None not in at and at == sorted(at), r.stdout
+    assert "Total time elapsed parallel:" not in r.stdout  # the dense path's line
+    assert "Elapsed parallel timer step 1:" not in r.stdout
+    r = run(base + ["--sketch-direct", fixture_path("random")])
+    assert r.returncode == 0, r.stderr
+    at = first_lines(r.stdout, ("Sketch (s=16):", "Sketch distances:"))
+    assert None not in at and at == sorted(at), r.stdout
+    assert "Canonical" not in r.stdout and "step 2" not in r.stdout
+
+
+# one mode per exit of the driver: dense, canonical with step 2, sketches without the counter
+MODES = [["-k", 4], ["--canonical", "--distances"], ["--canonical", "--sketch", 16, "--sketch-direct"]]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES, ids=lambda m: " ".join(str(a) for a in m))
+def test_cli_unwritable_out_dir_exits_1(cuda, tmp_path, mode):
+    r = run(mode + ["--out", tmp_path / "absent", fixture_path("odd")])
+    assert r.returncode == 1, r.stderr
+    assert "kmc: cannot write" in r.stderr
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES + [["--dropin"]], ids=lambda m: " ".join(str(a) for a in m))
+def test_cli_one_record_writes_empty_csvs(cuda, tmp_path, mode):
+    """n = 1: no pair, no step 2 launch and no step 2 line, the CSVs are written empty
+    (the sketch step prints its two timers all the same)."""
+    fa = tmp_path / "one.fa"
+    fa.write_text(">only\nACGTTGCAACGGTTAACCGTAGCTAGGATC\nGGATCCATTGACCA\n")
+    r = run(mode + ["--out", tmp_path, fa])
+    assert r.returncode == 0, r.stderr
+    assert "1 sequences read ." in r.stdout
+    assert "step 2" not in r.stdout and "Total time elapsed parallel:" not in r.stdout
+    sketch = "--sketch" in mode
+    assert ("Sketch (s=16):" in r.stdout and "Sketch distances:" in r.stdout) == sketch
+    names = ["sketch_results.csv"] if sketch else ["parallel_results.csv", "sequential_results.csv"]
+    assert sorted(p.name for p in tmp_path.iterdir() if p.suffix == ".csv") == names
+    for name in names:
+        assert (tmp_path / name).read_bytes() == b""
