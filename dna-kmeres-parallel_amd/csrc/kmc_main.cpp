@@ -18,7 +18,8 @@
 // counting (--canonical), and with it step 2 on the sparse counts (--distances:
 // kmc_pair_distances_sparse) or on MinHash sketches of them (--sketch:
 // kmc_sketch_from_counts + kmc_sketch_distances -> sketch_results.csv; --sketch-direct:
-// kmc_sketch_from_sequences instead, no canonical count).  GPU only: there is no CPU counting path here.
+// kmc_sketch_from_sequences instead, no canonical count; --per-file: one sketch per input file,
+// kmc_sketch_from_sequences_grouped).  GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -57,11 +58,15 @@ struct Options {
     long min_count = 1;  // --min-count C
     bool min_count_set = false;
     bool sketch_direct = false;  // --sketch-direct: kmc_sketch_from_sequences, no canonical count
+    bool per_file = false;       // --per-file: one sketch per input file (kmc_sketch_from_sequences_grouped)
+    bool max_seqs_set = false;
+    std::vector<std::string> more_inputs;  // the input files after the first
 };
 
 void usage(FILE *f) {
     fprintf(f,
             "usage: kmc [options] <input.fasta>\n"
+            "       kmc --canonical --sketch S --sketch-direct --per-file [options] <a.fasta> <b.fasta> ...\n"
             "       kmc synth OUT.fa RECORDS LENGTH [SEED]   (benchmark input, SURVEY.md 8(d))\n"
             "  -k K              k-mer length (default %d, the reference's K); dense path 1..%d,\n"
             "                    --canonical 1..%d\n"
@@ -95,6 +100,11 @@ void usage(FILE *f) {
             "  --sketch-direct   with --canonical --sketch: sketch straight from the records\n"
             "                    (kmc_sketch_from_sequences: one pass, no canonical count, the same\n"
             "                    sketch_results.csv); not with --min-count above 1, --counts, --distances\n"
+            "  --per-file        with --canonical --sketch S --sketch-direct: one or more input files,\n"
+            "                    each sketched as one genome: the union of the k-mers of all its records\n"
+            "                    (kmc_sketch_from_sequences_grouped); sketch_results.csv holds the distances\n"
+            "                    between the files in command-line order, and one line per file gives its\n"
+            "                    index, path, records and sketch size.  --max-seqs defaults to 0 here\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
@@ -125,6 +135,7 @@ int parse(int argc, char **argv, Options &o) {
             else return fprintf(stderr, "kmc: unknown dialect '%s'\n", d.c_str()), 2;
         } else if (a == "--max-seqs") {
             o.max_seqs = atoll(next("--max-seqs"));
+            o.max_seqs_set = true;
         } else if (a == "--out") {
             o.out_dir = next("--out");
         } else if (a == "--counts") {
@@ -145,6 +156,8 @@ int parse(int argc, char **argv, Options &o) {
                 return fprintf(stderr, "kmc: --sketch must be in 1..%d\n", KMC_SKETCH_MAX_SIZE), 2;
         } else if (a == "--sketch-direct") {
             o.sketch_direct = true;
+        } else if (a == "--per-file") {
+            o.per_file = true;
         } else if (a == "--min-count") {
             o.min_count = atol(next("--min-count"));
             o.min_count_set = true;
@@ -161,10 +174,11 @@ int parse(int argc, char **argv, Options &o) {
         } else if (o.input.empty()) {
             o.input = a;
         } else {
-            return fprintf(stderr, "kmc: more than one input file\n"), 2;
+            o.more_inputs.push_back(a);
         }
     }
     if (o.input.empty()) return usage(stderr), 2;
+    if (!o.more_inputs.empty() && !o.per_file) return fprintf(stderr, "kmc: more than one input file\n"), 2;
     if (o.dropin && o.k != KMC_DROPIN_K)
         return fprintf(stderr, "kmc: --dropin is the k = %d reference launch\n", KMC_DROPIN_K), 2;
     if (o.canonical ? (o.k < 1 || o.k > KMC_CANON_MAX_K) : (o.k < 1 || o.k > KMC_DENSE_MAX_K))
@@ -185,6 +199,11 @@ int parse(int argc, char **argv, Options &o) {
         fprintf(stderr, "kmc: --sketch-direct never counts: not with --min-count above 1, --counts or --distances\n");
         return usage(stderr), 2;
     }
+    if (o.per_file && !(o.canonical && o.sketch > 0 && o.sketch_direct)) {
+        fprintf(stderr, "kmc: --per-file needs --canonical --sketch S --sketch-direct\n");
+        return usage(stderr), 2;
+    }
+    if (o.per_file && !o.max_seqs_set) o.max_seqs = 0;
     if (o.gpus < 1) return fprintf(stderr, "kmc: --gpus must be >= 1\n"), 2;
     if (o.gpus > 1 && (o.dropin || o.canonical))
         return fprintf(stderr, "kmc: --gpus > 1 is for the dense path\n"), 2;
@@ -381,6 +400,41 @@ int run_sketch_direct(const Options &o, const Records &r, hipStream_t st) {
     }, r.n, st);
 }
 
+// --per-file: every input file is one group of all its records; file f's call writes row f
+// (rows of separate calls concatenate), so one file at a time is resident
+int run_per_file(const Options &o, hipStream_t st) {
+    std::vector<std::string> files{o.input};
+    files.insert(files.end(), o.more_inputs.begin(), o.more_inputs.end());
+    const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
+    return sketch_step(o, [&](uint32_t s, uint64_t *d_sk, uint32_t *d_sz) -> int {
+        DevBuf<int64_t> d_grp;
+        HIPCHK(dev_alloc(d_grp, 2));
+        for (size_t f = 0; f < files.size(); ++f) {
+            Options of = o;
+            of.input = files[f];
+            of.quiet = true;  // (the loader's lines are the single-file run's)
+            Records r;
+            if (int e = load(of, st, r)) return e;
+            uint32_t size = 0;
+            if (r.n == 0) {  // no record: the empty sketch
+                HIPCHK(hipMemsetAsync(d_sk + f * s, 0xFF, (size_t)s * 8, st));
+                HIPCHK(hipMemsetAsync(d_sz + f, 0, 4, st));
+            } else {
+                const int64_t grp[2] = {0, (int64_t)r.n};
+                HIPCHK(hipMemcpyAsync(d_grp.get(), grp, sizeof grp, hipMemcpyHostToDevice, st));
+                KMCCHK(kmc_sketch_from_sequences_grouped(r.data.get(), r.idx.get(), r.n, r.bytes, d_grp.get(), 1, o.k,
+                                                         flags, s, KMC_SKETCH_DEFAULT_SEED, d_sk + f * s, d_sz + f,
+                                                         nullptr, 0, st));
+                HIPCHK(hipMemcpyAsync(&size, d_sz + f, 4, hipMemcpyDeviceToHost, st));
+            }
+            HIPCHK(hipStreamSynchronize(st));  // before the file's buffers go
+            if (!o.quiet)
+                printf("File %zu: %s: %" PRIu64 " records, sketch size %u\n", f, files[f].c_str(), r.n, size);
+        }
+        return 0;
+    }, files.size(), st);
+}
+
 // --canonical: the sparse counts, then their dump, step 2 on them and their sketches
 int run_canonical(const Options &o, const Records &r, hipStream_t st) {
     const int k = o.k;
@@ -530,6 +584,7 @@ int run(const Options &o) {
     hipStream_t s = nullptr;
     HIPCHK(hipStreamCreate(&s));
     const Stream st(s);
+    if (o.per_file) return run_per_file(o, s);
     Records r;  // (after the stream: released before it)
     if (int e = load(o, s, r)) return e;
     if (!o.canonical) return run_dense(o, r, s);

@@ -48,6 +48,32 @@
 // s <= 1024 / 4096 / 16384: 20 / 44 / 140 KB shipped.
 // Workspace: 8 (n + 1) B of offsets + G (8 + 16 s) B of partial sets,
 // G = min(kWgPerCu * CUs, ceil((data_bytes / 16 + 3) / kMinChunks)).
+//
+// kmc_sketch_from_sequences_grouped: one row per group of consecutive records, the
+// bottom-s of the union of their windows' hashes.  The walk is the one above over
+// the records [gofs[0], gofs[ng]) (gofs: group_offsets clamped to [0, n], written by
+// prep); what changes is the life of the LDS set, which is reset and written out
+// when the group changes, not the record: the set, its threshold T and the staged
+// candidates are carried from one record piece to the next.  Where a set goes
+// follows from the group's byte span [widx[gofs[g]], widx[gofs[g + 1]]) alone
+// (group_span): a span inside one range is that range's to write to row g; a span
+// over the ranges w0 < .. < w1 leaves partial sets in slot 2 w0 + 1 and the slots
+// 2w, w0 < w <= w1, and the workgroup of cut w0 folds them and always writes the row.
+//   prep    widx as above, gofs[g] = clamp(group_offsets[g], 0, n)
+//   empty   every group whose span lies in one range (the empty ones among them)
+//           gets size 0 and a row of UINT64_MAX before the walk: a group of no
+//           window is never met by the walk, and telling so from the offsets would
+//           cost a scan of its records
+//   walk    as above; every workgroup first zeroes its two psize words, so that the
+//           slot of a range that holds no window of the crossing group (a stretch of
+//           records shorter than k, longer than a range) reads as an empty set
+//   merge   one workgroup per cut: the last group that starts before the cut, if
+//           its span crosses the cut and starts in the range before it
+// Workspace: the above + 8 (ng + 1) B of group offsets.
+//
+// kmc_sketch_merge_groups: one workgroup per group folds the group's input rows, in
+// order, into the LDS set with the same merge, kStage values at a time, and leaves a
+// row at its first staged run that starts at or above T.  No workspace.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -91,6 +117,24 @@ struct SArgs {
     uint32_t *sizes;
 };
 
+// kmc_sketch_from_sequences_grouped: the above (sketches, sizes: one row per group) and
+struct GArgs : SArgs {
+    const int64_t *group_offsets;  // the caller's
+    int64_t *gofs;                 // [ng + 1] clamped to [0, n]
+    int64_t ng;
+};
+
+struct MArgs {  // kmc_sketch_merge_groups
+    const uint64_t *in;
+    const uint32_t *sizes_in;
+    int64_t rows;
+    const int64_t *group_offsets;
+    int64_t ng;
+    uint32_t s;
+    uint64_t *out;
+    uint32_t *sizes_out;
+};
+
 // The walk's view (kmc_canon_walk.h) with the geometry of this call
 struct Walk {
     const char *data;
@@ -101,13 +145,14 @@ struct Walk {
     int64_t c_lo, cpw;
 };
 
-__device__ __forceinline__ Walk make_walk(const SArgs &a) {
+// over the records [r0, r1) of the call
+__device__ __forceinline__ Walk make_walk(const SArgs &a, int64_t r0, int64_t r1) {
     Walk W;
     W.data = a.data;
-    W.idx = a.widx;
-    W.n = a.n;
-    W.lo = a.widx[0];
-    W.hi = a.widx[a.n];
+    W.idx = a.widx + r0;
+    W.n = r1 - r0;
+    W.lo = a.widx[r0];
+    W.hi = a.widx[r1];
     if (W.hi < W.lo) W.hi = W.lo;
     W.k = a.k;
     W.flags = a.flags;
@@ -116,6 +161,14 @@ __device__ __forceinline__ Walk make_walk(const SArgs &a) {
     const int64_t cpw = (chunks + a.G - 1) / a.G;
     W.cpw = cpw > 1 ? cpw : 1;
     return W;
+}
+
+__device__ __forceinline__ Walk make_walk(const SArgs &a) { return make_walk(a, 0, a.n); }
+
+// the records of the groups: [gofs[0], gofs[ng])
+__device__ __forceinline__ Walk make_walk(const GArgs &a) {
+    const int64_t r0 = a.gofs[0], r1 = a.gofs[a.ng];
+    return make_walk(a, r0, r1 > r0 ? r1 : r0);
 }
 
 struct HashOf {
@@ -241,6 +294,104 @@ __device__ __forceinline__ int merge_stage(SetLds<CAP> &L, int m, int s, int c) 
     return total < s ? total : s;
 }
 
+// a wave-uniform 64-bit value as the compiler can see it (scalar registers and loads)
+__device__ __forceinline__ int64_t uniform64(int64_t x) {
+    const uint32_t l = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+    const uint32_t h = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
+    return (int64_t)(((uint64_t)h << 32) | l);
+}
+
+// Where the set of group g goes, from the offsets alone: its byte span
+// [widx[gofs[g]], widx[gofs[g + 1]]) lies in the ranges w0 .. w1 (of this launch);
+// cross: in more than one.  An empty group, or a descending pair: no span, not cross.
+struct Span {
+    int64_t gs, w0, w1;
+    bool cross;
+};
+
+__device__ __forceinline__ Span group_span(const Walk &W, const GArgs &a, int64_t g) {
+    const int64_t ga = a.gofs[g], gb = a.gofs[g + 1];
+    int64_t gs = a.widx[ga], ge = gb > ga ? a.widx[gb] : gs;
+    gs = gs > W.lo ? gs : W.lo;
+    ge = ge < W.hi ? ge : W.hi;
+    Span S;
+    S.gs = gs;
+    S.w0 = S.w1 = 0;
+    S.cross = false;
+    if (ge <= gs) return S;
+    const int64_t top = a.G - 1;
+    int64_t w0 = ((gs >> 4) - W.c_lo) / W.cpw, w1 = (((ge - 1) >> 4) - W.c_lo) / W.cpw;
+    // (guard) the slots of this launch only
+    w0 = w0 < 0 ? 0 : (w0 > top ? top : w0);
+    w1 = w1 < w0 ? w0 : (w1 > top ? top : w1);
+    S.w0 = w0;
+    S.w1 = w1;
+    S.cross = w1 > w0;
+    return S;
+}
+
+// The windows of record piece [ps, pe): every candidate hash goes through the staging
+// buffer into the set (m values, threshold T, `staged` values left in the buffer,
+// ci: the counter of the next round).  Every thread of the workgroup calls it.
+// The grouped walk's copy of the chunk loop of sketch_seq_walk_kernel below: that
+// kernel keeps its loop in place, because calling this function from it changed its
+// register allocation and schedule, and its device code is to stay as it was.
+template <bool FWD, bool BIGK, int CAP>
+__device__ __forceinline__ void walk_piece(SetLds<CAP> &L, const Walk &W, const HashOf hf, int64_t ps, int64_t pe,
+                                           int64_t rend, int s, int &m, uint32_t &staged, uint64_t &T, int &ci) {
+    const int tid = threadIdx.x;
+    const int64_t c0 = ps >> 4, c1 = ((pe - 1) >> 4) + 1;
+    ChunkRaw nx = chunk_raw(W, (c0 + tid) << 4);
+    for (int64_t cb = c0; cb < c1; cb += kBlock) {
+        const int64_t c = cb + tid;
+        unsigned long long h[16];
+        const ChunkRaw cr = nx;
+        nx = chunk_raw(W, (c + kBlock) << 4);  // next round's chunk
+        uint32_t pend = chunk_keys<FWD, BIGK>(W, cr, c << 4, ps, pe, rend, hf, h);  // (past the piece: 0)
+        for (;;) {
+            const bool full = m == s;
+            uint32_t cm = 0u;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) cm |= (uint32_t)(!full || h[j] < T) << j;
+            pend &= cm;
+            if (pend) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if (((pend >> j) & 1u) && in_set(L.set, m, h[j])) pend &= ~(1u << j);
+            }
+            const uint32_t cnt = (uint32_t)__popc(pend);
+            if (cnt) {
+                uint32_t at = staged + __hip_atomic_fetch_add(&L.ctr[ci], cnt, __ATOMIC_RELAXED,
+                                                              __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    if ((pend >> j) & 1u) {
+                        if (at < (uint32_t)kStage) {
+                            L.stage[at] = h[j];
+                            pend &= ~(1u << j);
+                        }
+                        ++at;
+                    }
+                }
+            }
+            lds_barrier();
+            const uint32_t total = staged + L.ctr[ci];
+            // the counter of the round before: every thread has read it (it passed this
+            // barrier), and its next adds come after the next barrier
+            if (tid == 0) L.ctr[(ci + 2) % 3] = 0u;
+            ci = (ci + 1) % 3;
+            if (total < (uint32_t)kStage) {
+                staged = total;
+                break;
+            }
+            m = merge_stage(L, m, s, kStage);
+            T = m == s ? L.set[s - 1] : kFill;
+            staged = 0;
+            if (total == (uint32_t)kStage) break;  // (else some lanes still hold candidates)
+        }
+    }
+}
+
 template <bool FWD, bool BIGK, int CAP>
 __global__ __launch_bounds__(kBlock) void sketch_seq_walk_kernel(SArgs a) {
     __shared__ SetLds<CAP> L;
@@ -321,6 +472,62 @@ __global__ __launch_bounds__(kBlock) void sketch_seq_walk_kernel(SArgs a) {
     });
 }
 
+// The grouped walk: the set, its threshold and the staged candidates outlive the
+// record piece; they are written out (flush) and reset when the piece's record belongs
+// to another group than the one before, and at the end of the range.
+template <bool FWD, bool BIGK, int CAP>
+__global__ __launch_bounds__(kBlock) void sketch_group_walk_kernel(GArgs a) {
+    __shared__ SetLds<CAP> L;
+    const Walk W = make_walk(a);
+    const int tid = threadIdx.x, s = (int)a.s, w = blockIdx.x;
+    const HashOf hf{a.seed};
+    // the slots of a range that holds no window of the crossing group read as empty
+    // (zeroed by the thread that may write them later: program order)
+    if (tid == 0) a.psize[2 * w] = a.psize[2 * w + 1] = 0u;
+    if (tid < 3) L.ctr[tid] = 0u;
+    int ci = 0;
+    int m = 0;
+    uint32_t staged = 0;
+    uint64_t T = kFill;
+    int64_t g = -1, g_end = 0;  // (wave-uniform) the records below g_end are group g's
+    const auto flush = [&]() {
+        if (staged) m = merge_stage(L, m, s, (int)staged);
+        const Span S = group_span(W, a, g);
+        if (!S.cross) {  // the whole group: its row
+            uint64_t *row = a.sketches + g * (int64_t)s;
+            for (int i = tid; i < s; i += kBlock) row[i] = i < m ? L.set[i] : kFill;
+            if (tid == 0) a.sizes[g] = (uint32_t)m;
+        } else {  // a partial set: the span starts before this range (slot 2w) or in it (2w + 1)
+            const int64_t slot = 2 * (int64_t)w + (S.w0 == w ? 1 : 0);
+            uint64_t *dst = a.part + slot * (int64_t)s;
+            for (int i = tid; i < m; i += kBlock) dst[i] = L.set[i];
+            if (tid == 0) a.psize[slot] = (uint32_t)m;
+        }
+        lds_barrier();  // the set is read out before the next group's merges
+        m = 0;
+        staged = 0;
+        T = kFill;
+    };
+    __syncthreads();
+    for_each_piece(W, &L.first, [&](int64_t r, int64_t ps, int64_t pe, int64_t rend) {
+        const int64_t R = uniform64(r + (W.idx - a.widx));  // the record in the call's numbering
+        if (R >= g_end) {
+            if (g >= 0) flush();
+            // the last group that starts at or before R (groups ascend: from g on)
+            int64_t lo = g < 0 ? 0 : g, hi = a.ng - 1;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi + 1) >> 1;
+                if (a.gofs[mid] <= R) lo = mid; else hi = mid - 1;
+            }
+            g = lo;
+            g_end = a.gofs[g + 1];
+            if (g_end <= R) g_end = R + 1;  // (guard: offsets that do not ascend)
+        }
+        walk_piece<FWD, BIGK>(L, W, hf, ps, pe, rend, s, m, staged, T, ci);
+    });
+    if (g >= 0) flush();
+}
+
 // The records of no window: size 0 and a row of UINT64_MAX (no LDS; the walk never
 // meets them, and neither does the merge).
 __global__ __launch_bounds__(256) void sketch_seq_fill_kernel(SArgs a) {
@@ -389,12 +596,110 @@ __global__ __launch_bounds__(kBlock) void sketch_seq_merge_kernel(SArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// groups of records
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sketch_group_prep_kernel(GArgs a) {
+    const int64_t top = a.n > a.ng ? a.n : a.ng;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i <= top; i += (int64_t)gridDim.x * 256) {
+        if (i <= a.n) {
+            int64_t x = a.indices[i];
+            x = x < 0 ? 0 : (x > a.data_bytes ? a.data_bytes : x);
+            a.widx[i] = x + a.mis;
+        }
+        if (i <= a.ng) {
+            const int64_t x = a.group_offsets[i];
+            a.gofs[i] = x < 0 ? 0 : (x > a.n ? a.n : x);
+        }
+    }
+}
+
+// Size 0 and a row of UINT64_MAX for every group whose span lies in one range, before
+// the walk: the walk overwrites those it meets a window of (the rows of the crossing
+// groups are the merge's, written in any case).
+__global__ __launch_bounds__(256) void sketch_group_empty_kernel(GArgs a) {
+    const Walk W = make_walk(a);
+    const int s = (int)a.s;
+    for (int64_t g = blockIdx.x; g < a.ng; g += gridDim.x) {
+        if (group_span(W, a, g).cross) continue;
+        uint64_t *row = a.sketches + g * (int64_t)s;
+        for (int i = threadIdx.x; i < s; i += 256) row[i] = kFill;
+        if (threadIdx.x == 0) a.sizes[g] = 0u;
+    }
+}
+
+// Folds the first min(pm, s) values of the ascending row `src` into the set, kStage
+// at a time, up to the first run that starts at or above T.
+template <int CAP>
+__device__ __forceinline__ void fold_row(SetLds<CAP> &L, const uint64_t *src, uint32_t pm, int s, int &m, uint64_t &T) {
+    const int tid = threadIdx.x;
+    if (pm > (uint32_t)s) pm = (uint32_t)s;
+    for (int c0 = 0; c0 < (int)pm; c0 += kStage) {
+        if (m == s && src[c0] >= T) break;  // ascending: nothing below T is left
+        const int c = (int)pm - c0 < kStage ? (int)pm - c0 : kStage;
+        if (tid < c) L.stage[tid] = src[c0 + tid];
+        lds_barrier();
+        m = merge_stage(L, m, s, c);
+        T = m == s ? L.set[s - 1] : kFill;
+    }
+}
+
+// One workgroup per cut between two ranges: the last group that starts before cut b,
+// if its span crosses the cut and b is the first cut it crosses, has its partial sets
+// folded and its row written (a slot no window went to has size 0).
+template <int CAP>
+__global__ __launch_bounds__(kBlock) void sketch_group_merge_kernel(GArgs a) {
+    __shared__ SetLds<CAP> L;
+    const Walk W = make_walk(a);
+    const int tid = threadIdx.x, s = (int)a.s;
+    const int64_t b = blockIdx.x;
+    const int64_t cut = (W.c_lo + (b + 1) * W.cpw) << 4;  // first byte of range b + 1
+    if (cut <= W.lo || cut >= W.hi) return;
+    int64_t lo = 0, hi = a.ng - 1;  // (wave-uniform: scalar loads)
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (a.widx[a.gofs[mid]] < cut) lo = mid; else hi = mid - 1;
+    }
+    const int64_t g = lo;
+    const Span S = group_span(W, a, g);
+    if (!S.cross || S.w0 != b || S.gs >= cut) return;  // none, or an earlier cut's workgroup has the group
+    int m = 0;
+    uint64_t T = kFill;
+    for (int64_t w = S.w0; w <= S.w1; ++w) {
+        const int64_t slot = 2 * w + (w == S.w0 ? 1 : 0);
+        fold_row(L, a.part + slot * (int64_t)s, a.psize[slot], s, m, T);
+    }
+    uint64_t *row = a.sketches + g * (int64_t)s;
+    for (int i = tid; i < s; i += kBlock) row[i] = i < m ? L.set[i] : kFill;
+    if (tid == 0) a.sizes[g] = (uint32_t)m;
+}
+
+// kmc_sketch_merge_groups: a workgroup folds the rows of its groups, one group at a time.
+template <int CAP>
+__global__ __launch_bounds__(kBlock) void sketch_merge_groups_kernel(MArgs a) {
+    __shared__ SetLds<CAP> L;
+    const int tid = threadIdx.x, s = (int)a.s;
+    for (int64_t g = blockIdx.x; g < a.ng; g += gridDim.x) {
+        int64_t ra = a.group_offsets[g], rb = a.group_offsets[g + 1];
+        ra = ra < 0 ? 0 : (ra > a.rows ? a.rows : ra);
+        rb = rb < 0 ? 0 : (rb > a.rows ? a.rows : rb);
+        int m = 0;
+        uint64_t T = kFill;
+        for (int64_t r = ra; r < rb; ++r) fold_row(L, a.in + r * (int64_t)s, a.sizes_in[r], s, m, T);
+        uint64_t *row = a.out + g * (int64_t)s;
+        for (int i = tid; i < s; i += kBlock) row[i] = i < m ? L.set[i] : kFill;
+        if (tid == 0) a.sizes_out[g] = (uint32_t)m;
+        lds_barrier();  // the set is read out before the next group's merges
+    }
+}
+
+// ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
 struct SLayout {
     int64_t *widx;
     uint32_t *psize;
     uint64_t *part;
+    int64_t *gofs;  // the grouped call's only
     size_t bytes;
 };
 
@@ -408,19 +713,65 @@ inline int walk_groups(uint64_t data_bytes, int cus) {
     return (int)(g < 1 ? 1 : g);
 }
 
-// the one layout behind the size query (base = null) and the bind
-inline SLayout layout(void *base, int64_t n, int G, uint32_t s) {
+// the one layout behind the size queries (base = null) and the binds; ng < 0: no groups
+inline SLayout layout(void *base, int64_t n, int G, uint32_t s, int64_t ng = -1) {
     Carver c(base);
     SLayout L;
     L.widx = c.take<int64_t>((size_t)n + 1);
     L.psize = c.take<uint32_t>(2 * (size_t)G);
     L.part = c.take<uint64_t>(2 * (size_t)G * s);
+    L.gofs = c.take_if<int64_t>(ng >= 0, (size_t)(ng < 0 ? 0 : ng) + 1);
     L.bytes = c.total();
     return L;
 }
 
 inline bool seq_args_ok(uint64_t num_seqs, uint64_t data_bytes, uint32_t sketch_size) {
     return sketch_size >= 1 && sketch_size <= KMC_SKETCH_MAX_SIZE && num_seqs <= kMaxSeqs && data_bytes < (1ull << 62);
+}
+
+// what both entry points refuse before anything else, in this order
+inline int seq_check(int k, uint64_t num_seqs, uint64_t data_bytes, uint32_t sketch_size, unsigned flags) {
+    if (k < 1 || k > KMC_CANON_MAX_K) return KMC_ERR_UNSUPPORTED_K;
+    if (!seq_args_ok(num_seqs, data_bytes, sketch_size)) return KMC_ERR_INVALID_ARG;
+    if (flags & ~(KMC_CANON_SOFTMASK | KMC_CANON_FORWARD)) return KMC_ERR_INVALID_ARG;
+    return KMC_OK;
+}
+
+DeviceCache q_ws;  // library-owned workspace
+
+// The workspace of a call (ng < 0: no groups) and the arguments both kinds of call share.
+inline int seq_bind(SArgs &a, int64_t **gofs, const char *data, const int64_t *indices, uint64_t num_seqs,
+                    uint64_t data_bytes, int k, unsigned flags, uint32_t sketch_size, uint64_t seed, uint64_t *sketches,
+                    uint32_t *sketch_sizes, int64_t ng, void *workspace, size_t workspace_bytes) {
+    int device = 0, cus = 0;
+    if (hipError_t he = hipGetDevice(&device)) return (int)he;
+    if (int e = device_cus(device, &cus)) return e;
+    const int64_t n = (int64_t)num_seqs;
+    const int G = walk_groups(data_bytes, cus);
+    const size_t need = layout(nullptr, n, G, sketch_size, ng).bytes;
+    void *ws = nullptr;
+    if (int e = bind_workspace(q_ws, device, need, workspace, workspace_bytes, 8, &ws)) return e;
+    const SLayout L = layout(ws, n, G, sketch_size, ng);
+    // any `data` pointer: rounded down to 16 bytes, every offset moved up by the
+    // difference (kmc_count_canonical_hash's rule, applied on the device by prep)
+    const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
+    a.data = data - mis;
+    a.indices = indices;
+    a.widx = L.widx;
+    a.n = n;
+    a.data_bytes = (int64_t)data_bytes;
+    a.mis = (int64_t)mis;
+    a.k = k;
+    a.flags = flags;
+    a.G = G;
+    a.s = sketch_size;
+    a.seed = seed;
+    a.part = L.part;
+    a.psize = L.psize;
+    a.sketches = sketches;
+    a.sizes = sketch_sizes;
+    *gofs = L.gofs;
+    return KMC_OK;
 }
 
 template <int CAP>
@@ -438,7 +789,26 @@ void launch_seq(const SArgs &a, unsigned rec_grid, hipStream_t st) {
     if (a.G > 1) hipLaunchKernelGGL((sketch_seq_merge_kernel<CAP>), dim3((unsigned)a.G - 1), b, 0, st, a);
 }
 
-DeviceCache q_ws;  // library-owned workspace
+template <int CAP>
+void launch_group(const GArgs &a, unsigned group_grid, hipStream_t st) {
+    const bool fwd = a.flags & KMC_CANON_FORWARD, big = a.k >= 16;
+    const dim3 g((unsigned)a.G), b(kBlock);
+    hipLaunchKernelGGL(sketch_group_empty_kernel, dim3(group_grid), dim3(256), 0, st, a);
+    if (fwd) {
+        if (big) hipLaunchKernelGGL((sketch_group_walk_kernel<true, true, CAP>), g, b, 0, st, a);
+        else hipLaunchKernelGGL((sketch_group_walk_kernel<true, false, CAP>), g, b, 0, st, a);
+    } else {
+        if (big) hipLaunchKernelGGL((sketch_group_walk_kernel<false, true, CAP>), g, b, 0, st, a);
+        else hipLaunchKernelGGL((sketch_group_walk_kernel<false, false, CAP>), g, b, 0, st, a);
+    }
+    if (a.G > 1) hipLaunchKernelGGL((sketch_group_merge_kernel<CAP>), dim3((unsigned)a.G - 1), b, 0, st, a);
+}
+
+// [p, p + bytes) and [q, q + qbytes) share a byte
+inline bool overlap(const void *p, uint64_t bytes, const void *q, uint64_t qbytes) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + qbytes && b < a + bytes;
+}
 
 }  // namespace
 }  // namespace kmc
@@ -457,45 +827,87 @@ extern "C" int kmc_sketch_from_sequences(const char *data, const int64_t *indice
                                          uint64_t data_bytes, int k, unsigned flags, uint32_t sketch_size,
                                          uint64_t seed, uint64_t *sketches, uint32_t *sketch_sizes, void *workspace,
                                          size_t workspace_bytes, hipStream_t stream) {
-    if (k < 1 || k > KMC_CANON_MAX_K) return KMC_ERR_UNSUPPORTED_K;
-    if (!seq_args_ok(num_seqs, data_bytes, sketch_size)) return KMC_ERR_INVALID_ARG;
-    if (flags & ~(KMC_CANON_SOFTMASK | KMC_CANON_FORWARD)) return KMC_ERR_INVALID_ARG;
+    if (int e = seq_check(k, num_seqs, data_bytes, sketch_size, flags)) return e;
     if (num_seqs == 0) return KMC_OK;
     if (!indices || !sketches || !sketch_sizes) return KMC_ERR_INVALID_ARG;
     if (data_bytes > 0 && !data) return KMC_ERR_INVALID_ARG;
-    int device = 0, cus = 0;
-    if (hipError_t he = hipGetDevice(&device)) return (int)he;
-    if (int e = device_cus(device, &cus)) return e;
-    const int64_t n = (int64_t)num_seqs;
-    const int G = walk_groups(data_bytes, cus);
-    const size_t need = layout(nullptr, n, G, sketch_size).bytes;
-    void *ws = nullptr;
-    if (int e = bind_workspace(q_ws, device, need, workspace, workspace_bytes, 8, &ws)) return e;
-    const SLayout L = layout(ws, n, G, sketch_size);
-    // any `data` pointer: rounded down to 16 bytes, every offset moved up by the
-    // difference (kmc_count_canonical_hash's rule, applied on the device by prep)
-    const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
     SArgs a;
-    a.data = data - mis;
-    a.indices = indices;
-    a.widx = L.widx;
-    a.n = n;
-    a.data_bytes = (int64_t)data_bytes;
-    a.mis = (int64_t)mis;
-    a.k = k;
-    a.flags = flags;
-    a.G = G;
-    a.s = sketch_size;
-    a.seed = seed;
-    a.part = L.part;
-    a.psize = L.psize;
-    a.sketches = sketches;
-    a.sizes = sketch_sizes;
+    int64_t *unused = nullptr;
+    if (int e = seq_bind(a, &unused, data, indices, num_seqs, data_bytes, k, flags, sketch_size, seed, sketches,
+                         sketch_sizes, -1, workspace, workspace_bytes))
+        return e;
+    const int64_t n = a.n;
     const int64_t pg = (n + 1 + 255) / 256;
     hipLaunchKernelGGL(sketch_seq_prep_kernel, dim3((unsigned)(pg < 4096 ? pg : 4096)), dim3(256), 0, stream, a);
     const unsigned rec_grid = (unsigned)(n < kMaxGridX ? n : kMaxGridX);
     if (sketch_size <= 1024) launch_seq<1024>(a, rec_grid, stream);
     else if (sketch_size <= 4096) launch_seq<4096>(a, rec_grid, stream);
     else launch_seq<KMC_SKETCH_MAX_SIZE>(a, rec_grid, stream);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t kmc_sketch_from_sequences_grouped_workspace_size(uint64_t num_seqs, uint64_t num_groups,
+                                                                   uint64_t data_bytes, uint32_t sketch_size,
+                                                                   int device) {
+    if (!seq_args_ok(num_seqs, data_bytes, sketch_size) || num_seqs == 0 || num_groups == 0 ||
+        num_groups > kMaxSeqs || device < 0)
+        return 0;
+    int cus = 0;  // (the arguments are checked before any HIP call)
+    if (device_cus(device, &cus)) return 0;
+    return layout(nullptr, (int64_t)num_seqs, walk_groups(data_bytes, cus), sketch_size, (int64_t)num_groups).bytes;
+}
+
+extern "C" int kmc_sketch_from_sequences_grouped(const char *data, const int64_t *indices, uint64_t num_seqs,
+                                                 uint64_t data_bytes, const int64_t *group_offsets,
+                                                 uint64_t num_groups, int k, unsigned flags, uint32_t sketch_size,
+                                                 uint64_t seed, uint64_t *sketches, uint32_t *sketch_sizes,
+                                                 void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    if (int e = seq_check(k, num_seqs, data_bytes, sketch_size, flags)) return e;
+    if (num_groups > kMaxSeqs) return KMC_ERR_INVALID_ARG;
+    if (num_groups == 0) return KMC_OK;
+    if (!group_offsets) return KMC_ERR_INVALID_ARG;
+    if (num_seqs == 0) return KMC_OK;
+    if (!indices || !sketches || !sketch_sizes) return KMC_ERR_INVALID_ARG;
+    if (data_bytes > 0 && !data) return KMC_ERR_INVALID_ARG;
+    GArgs a;
+    if (int e = seq_bind(a, &a.gofs, data, indices, num_seqs, data_bytes, k, flags, sketch_size, seed, sketches,
+                         sketch_sizes, (int64_t)num_groups, workspace, workspace_bytes))
+        return e;
+    a.group_offsets = group_offsets;
+    a.ng = (int64_t)num_groups;
+    const int64_t top = a.n > a.ng ? a.n : a.ng, pg = (top + 1 + 255) / 256;
+    hipLaunchKernelGGL(sketch_group_prep_kernel, dim3((unsigned)(pg < 4096 ? pg : 4096)), dim3(256), 0, stream, a);
+    const unsigned group_grid = (unsigned)(a.ng < kMaxGridX ? a.ng : kMaxGridX);
+    if (sketch_size <= 1024) launch_group<1024>(a, group_grid, stream);
+    else if (sketch_size <= 4096) launch_group<4096>(a, group_grid, stream);
+    else launch_group<KMC_SKETCH_MAX_SIZE>(a, group_grid, stream);
+    return (int)hipGetLastError();
+}
+
+extern "C" int kmc_sketch_merge_groups(const uint64_t *sketches_in, const uint32_t *sizes_in, uint64_t num_rows,
+                                       const int64_t *group_offsets, uint64_t num_groups, uint32_t sketch_size,
+                                       uint64_t *sketches_out, uint32_t *sizes_out, hipStream_t stream) {
+    if (sketch_size < 1 || sketch_size > KMC_SKETCH_MAX_SIZE || num_rows > kMaxSeqs || num_groups > kMaxSeqs)
+        return KMC_ERR_INVALID_ARG;
+    if (num_groups == 0) return KMC_OK;
+    if (!group_offsets || !sketches_out || !sizes_out) return KMC_ERR_INVALID_ARG;
+    if (num_rows > 0 && (!sketches_in || !sizes_in)) return KMC_ERR_INVALID_ARG;
+    const uint64_t row = 8ull * sketch_size;
+    if (num_rows > 0 && (overlap(sketches_out, num_groups * row, sketches_in, num_rows * row) ||
+                         overlap(sizes_out, num_groups * 4, sizes_in, num_rows * 4)))
+        return KMC_ERR_INVALID_ARG;
+    MArgs a;
+    a.in = sketches_in;
+    a.sizes_in = sizes_in;
+    a.rows = (int64_t)num_rows;
+    a.group_offsets = group_offsets;
+    a.ng = (int64_t)num_groups;
+    a.s = sketch_size;
+    a.out = sketches_out;
+    a.sizes_out = sizes_out;
+    const dim3 g((unsigned)(a.ng < kMaxGridX ? a.ng : kMaxGridX)), b(kBlock);
+    if (sketch_size <= 1024) hipLaunchKernelGGL((sketch_merge_groups_kernel<1024>), g, b, 0, stream, a);
+    else if (sketch_size <= 4096) hipLaunchKernelGGL((sketch_merge_groups_kernel<4096>), g, b, 0, stream, a);
+    else hipLaunchKernelGGL((sketch_merge_groups_kernel<KMC_SKETCH_MAX_SIZE>), g, b, 0, stream, a);
     return (int)hipGetLastError();
 }

@@ -188,6 +188,11 @@ def _load(path):
     L.kmc_sketch_from_sequences_workspace_size.argtypes = [_U64, _U64, ctypes.c_uint32, ctypes.c_int]
     L.kmc_sketch_from_sequences.argtypes = [_P, _P, _U64, _U64, ctypes.c_int, ctypes.c_uint, ctypes.c_uint32, _U64,
                                             _P, _P, _P, ctypes.c_size_t, _P]
+    L.kmc_sketch_from_sequences_grouped_workspace_size.restype = ctypes.c_size_t
+    L.kmc_sketch_from_sequences_grouped_workspace_size.argtypes = [_U64, _U64, _U64, ctypes.c_uint32, ctypes.c_int]
+    L.kmc_sketch_from_sequences_grouped.argtypes = [_P, _P, _U64, _U64, _P, _U64, ctypes.c_int, ctypes.c_uint,
+                                                    ctypes.c_uint32, _U64, _P, _P, _P, ctypes.c_size_t, _P]
+    L.kmc_sketch_merge_groups.argtypes = [_P, _P, _U64, _P, _U64, ctypes.c_uint32, _P, _P, _P]
     L.minKmeres2_hip.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.kmc_count_canonical_hash.argtypes = [_P, _P, _U64, ctypes.c_int, ctypes.c_uint, _P, _P, _U64, _P,
                                            ctypes.POINTER(_U64), _P]
@@ -438,6 +443,48 @@ def sketch_from_sequences(data, indices, k, sketch_size, flags=0, seed=SKETCH_DE
                                          _stream(stream))
     _check(rc, "kmc_sketch_from_sequences")
     return sk, sizes
+
+
+def sketch_from_sequences_grouped_workspace_size(num_seqs, num_groups, data_bytes, sketch_size, device=0):
+    return int(lib().kmc_sketch_from_sequences_grouped_workspace_size(num_seqs, num_groups, data_bytes, sketch_size,
+                                                                      device))
+
+
+def sketch_from_sequences_grouped(data, indices, group_offsets, k, sketch_size, flags=0, seed=SKETCH_DEFAULT_SEED,
+                                  data_bytes=None, workspace=None, stream=None):
+    """One bottom-s MinHash sketch per group of consecutive records
+    (kmc_sketch_from_sequences_grouped): group g owns the records
+    [group_offsets[g], group_offsets[g+1]) (device int64 tensor) and its row is the
+    sketch of the union of their k-mer sets.  Returns (sketches int64 [groups, s],
+    sizes int32 [groups]); without a record every group is empty (size 0, fill)."""
+    n = int(indices.numel() - 1)
+    ng = int(group_offsets.numel() - 1)
+    s = int(sketch_size)
+    if data_bytes is None:
+        data_bytes = data.numel()
+    sk, sizes = _sketch_out(ng, s, indices.device)
+    rc = lib().kmc_sketch_from_sequences_grouped(_dptr(data), _dptr(indices), n, int(data_bytes),
+                                                 _dptr(group_offsets), ng, k, flags, s, int(seed) & _M64, _dptr(sk),
+                                                 _dptr(sizes), *_ws(workspace), _stream(stream))
+    _check(rc, "kmc_sketch_from_sequences_grouped")
+    if n <= 0:  # the library writes nothing then
+        sk.fill_(-1)
+        sizes.zero_()
+    return sk, sizes
+
+
+def sketch_merge_groups(sketches, sizes, group_offsets, stream=None):
+    """Bottom-s of the union of the sketch rows [group_offsets[g], group_offsets[g+1])
+    (kmc_sketch_merge_groups) for every group g.  Returns new (sketches int64
+    [groups, s], sizes int32 [groups]); the input is left as it is."""
+    sketches = sketches.contiguous()
+    rows, s = int(sketches.shape[0]), int(sketches.shape[1])
+    ng = int(group_offsets.numel() - 1)
+    sk, sz = _sketch_out(ng, s, sketches.device)
+    rc = lib().kmc_sketch_merge_groups(_dptr(sketches), _dptr(sizes), rows, _dptr(group_offsets), ng, s, _dptr(sk),
+                                       _dptr(sz), _stream(stream))
+    _check(rc, "kmc_sketch_merge_groups")
+    return sk, sz
 
 
 def sketch_distances(sketches, sizes, k, with_counts=False, stream=None):

@@ -398,7 +398,53 @@ KMC_API int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *coun
  * host arguments only.  KMC_ERR_INVALID_ARG: sketch_size 0 or above
  * KMC_SKETCH_MAX_SIZE, unknown flag bits, num_seqs above 2^40, null indices,
  * sketches or sketch_sizes, null data with data_bytes > 0.  num_seqs == 0: KMC_OK.
- * The size query returns 0 on bad arguments (and needs no device for those). */
+ * The size query returns 0 on bad arguments (and needs no device for those).
+ *
+ * kmc_sketch_from_sequences_grouped: one sketch per group of consecutive records (the
+ * contigs of an assembly, the reads of a sample) instead of one per record.  Group g
+ * owns the records [group_offsets[g], group_offsets[g+1]); row g holds the
+ * sketch_size smallest distinct hashes over the valid windows of all of them,
+ * ascending, then UINT64_MAX; sketch_sizes[g] the number kept.  Windows, validity,
+ * keys, flags, k, seed and hash are kmc_sketch_from_sequences': no window spans two
+ * records, so a group is the union of its records' k-mer sets, not their
+ * concatenation.  With group_offsets = 0, 1, .., num_seqs the output is
+ * kmc_sketch_from_sequences' bit for bit, and rows of separate calls concatenate.
+ *   group_offsets device int64[num_groups + 1], ascending; values are clamped to
+ *                 [0, num_seqs] on the device.  A descending pair makes an empty
+ *                 group; otherwise offsets that do not ascend give an unspecified
+ *                 result and no stray access.  Records outside
+ *                 [group_offsets[0], group_offsets[num_groups]) are not sketched.
+ *   sketches      device uint64[num_groups * sketch_size]
+ *   sketch_sizes  device uint32[num_groups]; an empty group, or one whose records have
+ *                 no valid window, gets size 0 and a row of UINT64_MAX
+ *   workspace     as kmc_sketch_from_sequences, of
+ *                 kmc_sketch_from_sequences_grouped_workspace_size() bytes: that
+ *                 call's arrays and 8 (num_groups + 1) bytes of group offsets; it does
+ *                 not grow with the number of windows
+ * The LDS set of a walking workgroup lives as long as the group it is in, so a group
+ * of many short records pays one threshold, one row and one merge per range, not one
+ * per record.  Exact for any content; asynchronous on `stream`, no host read-back;
+ * the work launched depends on the host arguments only; nothing a former call left
+ * in the workspace is read.  Errors as kmc_sketch_from_sequences, and
+ * KMC_ERR_INVALID_ARG for num_groups above 2^40 and for null group_offsets with
+ * num_groups > 0.  num_groups == 0: KMC_OK.  num_seqs == 0: KMC_OK and nothing is
+ * written (every group is empty; the caller knows it).
+ *
+ * kmc_sketch_merge_groups: row g of the output is the bottom-sketch_size of the union
+ * of the input rows [group_offsets[g], group_offsets[g+1]) (offsets as above, clamped
+ * to [0, num_rows]): the first sizes_in[r] values (clamped to sketch_size) of each,
+ * assumed ascending and distinct within a row.  The bottom-s of a union is the
+ * bottom-s of the union of the bottom-s sets, so merging the rows
+ * kmc_sketch_from_sequences wrote gives what kmc_sketch_from_sequences_grouped
+ * writes; it also groups the rows of kmc_sketch_from_counts (min_count per record)
+ * and folds the rows of a collection sketched in several batches or on several
+ * GPUs.  One workgroup per group; a row is left at its first run of values at or
+ * above the current threshold.  No workspace; asynchronous on `stream`.  The output
+ * must not overlap the input: KMC_ERR_INVALID_ARG when the byte ranges of
+ * sketches_out and sketches_in, or of sizes_out and sizes_in, share a byte; also for
+ * a sketch_size outside 1..KMC_SKETCH_MAX_SIZE, num_rows or num_groups above 2^40,
+ * null group_offsets, sketches_out or sizes_out, null inputs with num_rows > 0.
+ * num_groups == 0: KMC_OK. */
 #define KMC_SKETCH_MAX_SIZE 16384
 #define KMC_SKETCH_DEFAULT_SEED 42ull
 KMC_API size_t kmc_sketch_workspace_size(uint64_t num_seqs, uint64_t num_entries, uint32_t sketch_size, int device);
@@ -415,6 +461,17 @@ KMC_API int kmc_sketch_from_sequences(const char *data, const int64_t *indices, 
                                       uint64_t data_bytes, int k, unsigned flags, uint32_t sketch_size,
                                       uint64_t seed, uint64_t *sketches, uint32_t *sketch_sizes,
                                       void *workspace, size_t workspace_bytes, hipStream_t stream);
+KMC_API size_t kmc_sketch_from_sequences_grouped_workspace_size(uint64_t num_seqs, uint64_t num_groups,
+                                                                uint64_t data_bytes, uint32_t sketch_size,
+                                                                int device);
+KMC_API int kmc_sketch_from_sequences_grouped(const char *data, const int64_t *indices, uint64_t num_seqs,
+                                              uint64_t data_bytes, const int64_t *group_offsets,
+                                              uint64_t num_groups, int k, unsigned flags, uint32_t sketch_size,
+                                              uint64_t seed, uint64_t *sketches, uint32_t *sketch_sizes,
+                                              void *workspace, size_t workspace_bytes, hipStream_t stream);
+KMC_API int kmc_sketch_merge_groups(const uint64_t *sketches_in, const uint32_t *sizes_in, uint64_t num_rows,
+                                    const int64_t *group_offsets, uint64_t num_groups, uint32_t sketch_size,
+                                    uint64_t *sketches_out, uint32_t *sizes_out, hipStream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Tracing (the reference times step 1 with cudaEvents, main.cu:262-300): when set,

@@ -5,7 +5,9 @@ of --runs) and writes one JSON line per (input, sketch size) to --out
 (profiles/pr_sketch.jsonl).  With --direct: kmc_sketch_from_sequences beside the
 two-step path kmc_count_canonical_hash + kmc_sketch_from_counts on the same inputs
 (rows asserted equal, both workspace sizes), and on one all-A record
-(profiles/pr_sketch_direct.jsonl).
+(profiles/pr_sketch_direct.jsonl).  With --grouped: kmc_sketch_from_sequences_grouped
+beside the ungrouped call, the ungrouped call + kmc_sketch_merge_groups and the
+distances on group rows and on record rows (profiles/pr_sketch_grouped.jsonl).
 
 Inputs (synthetic, generated on the device):
   iid          8 x 50 Mbase independent records, k = 31
@@ -137,6 +139,59 @@ def direct_main(args, dev, shapes):
             print(json.dumps(rec), flush=True)
 
 
+def grouped_main(args, dev):
+    """--grouped: kmc_sketch_from_sequences_grouped beside the paths the parent commit
+    offers for the same rows: the ungrouped call (identity grouping), the ungrouped call
+    followed by kmc_sketch_merge_groups, and kmc_sketch_distances on the group rows
+    beside the record rows.  Rows are asserted equal before anything is timed."""
+    shapes = [  # name, groups, records per group, record length, k, sketch sizes, time the record distances
+        ("identity", 4096, 1, 100_000, 21, (1000, 10000), False),
+        ("draft_assembly", 8, 500, 100_000, 21, (1000,), True),
+        ("read_set", 4, 650_000, 150, 21, (1000,), False),
+    ]
+    only = set(args.inputs.split(",")) if args.inputs != "iid,copies_1pct,many" else None
+    runs = 5
+    with open(args.out, "a") as out:
+        for name, groups, per, record_len, k, sizes, rec_dist in shapes:
+            if only is not None and name not in only:
+                continue
+            record_len = max(int(record_len * args.scale), k + 1) if name != "read_set" else record_len
+            if name == "read_set":
+                per = max(int(per * args.scale), 1)
+            records = groups * per
+            data, idx = make_input("many", records, record_len, dev)
+            go = torch.arange(0, records + 1, per, dtype=torch.int64, device=dev)
+            for s in sizes:
+                grp = kmc.sketch_from_sequences_grouped(data, idx, go, k, s)
+                rec_rows = kmc.sketch_from_sequences(data, idx, k, s)
+                via = rec_rows if per == 1 else kmc.sketch_merge_groups(*rec_rows, go)
+                torch.cuda.synchronize()
+                assert torch.equal(grp[0], via[0]) and torch.equal(grp[1], via[1]), (name, s)
+                rec = {
+                    "input": name, "groups": groups, "records": records, "record_len": record_len, "k": k,
+                    "sketch_size": s, "rows_equal": True,
+                    "workspace_bytes_grouped": kmc.sketch_from_sequences_grouped_workspace_size(
+                        records, groups, data.numel(), s),
+                    "workspace_bytes_ungrouped": kmc.sketch_from_sequences_workspace_size(records, data.numel(), s),
+                    "ungrouped_row_bytes": 8 * s * records,
+                    "kmc_sketch_from_sequences_grouped": timed(
+                        lambda: kmc.sketch_from_sequences_grouped(data, idx, go, k, s), runs),
+                    "kmc_sketch_from_sequences": timed(lambda: kmc.sketch_from_sequences(data, idx, k, s), runs),
+                }
+                if per > 1:
+                    rec["kmc_sketch_merge_groups"] = timed(lambda: kmc.sketch_merge_groups(*rec_rows, go), runs)
+                    rec["kmc_sketch_distances_groups"] = timed(lambda: kmc.sketch_distances(*grp, k), runs)
+                    if rec_dist:
+                        rec["kmc_sketch_distances_records"] = timed(lambda: kmc.sketch_distances(*rec_rows, k), runs)
+                out.write(json.dumps(rec) + "\n")
+                out.flush()
+                print(json.dumps(rec), flush=True)
+                del grp, rec_rows, via
+                torch.cuda.empty_cache()
+            del data, idx, go
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(HERE), "profiles", "pr_sketch.jsonl"))
@@ -147,8 +202,15 @@ def main():
     ap.add_argument("--direct", action="store_true",
                     help="time kmc_sketch_from_sequences beside kmc_count_canonical_hash + kmc_sketch_from_counts "
                          "(rows asserted equal) and on all_a; --out profiles/pr_sketch_direct.jsonl")
+    ap.add_argument("--grouped", action="store_true",
+                    help="time kmc_sketch_from_sequences_grouped beside kmc_sketch_from_sequences (+ "
+                         "kmc_sketch_merge_groups) on identity, draft_assembly and read_set (--inputs picks among "
+                         "them; rows asserted equal; 2 warm-ups, median of 5); appends to "
+                         "--out profiles/pr_sketch_grouped.jsonl")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.grouped:
+        return grouped_main(args, dev)
     shapes = {"iid": (8, 50_000_000, 31), "copies_1pct": (8, 50_000_000, 31), "many": (4096, 100_000, 21)}
     if args.direct:
         return direct_main(args, dev, shapes)
