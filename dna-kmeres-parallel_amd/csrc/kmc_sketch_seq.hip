@@ -1,42 +1,79 @@
-// kmc_sketch_seq.hip — bottom-s MinHash sketches straight from the record buffer:
-// kmc_sketch_from_sequences writes the rows and sizes kmc_sketch_from_counts
-// writes for the lists of kmc_count_canonical_hash, without those lists.  The bases
+// kmc_sketch_seq.hip — bottom-s MinHash sketches straight from the record buffer.
+// kmc_sketch_from_sequences writes, per record, the rows and sizes
+// kmc_sketch_from_counts writes for the lists of kmc_count_canonical_hash, without
+// those lists; kmc_sketch_from_sequences_grouped writes one row per group of
+// consecutive records, the bottom-s of the union of their windows' hashes.  Both are
+// one code path over units, a compile-time policy of the kernels (Records, Groups
+// below): a unit is a record or a group, and a record is a group of one.  The bases
 // are walked once (kmc_canon_walk.h, the canonical counter's walk), every valid
-// window's key is hashed (sketch_hash) and a workgroup keeps the s smallest
-// distinct hashes of the record piece it is in as a sorted set in LDS.  Exact for
-// any content: there is no table, no capacity and no retry.  Asynchronous, no host
-// read-back; the launches depend on the host arguments only.
+// window's key is hashed (sketch_hash) and a workgroup keeps the s smallest distinct
+// hashes of the unit it is in as a sorted set in LDS.  Exact for any content: there
+// is no table, no capacity and no retry.  Asynchronous, no host read-back; the
+// launches depend on the host arguments only.
+//
+// Where a unit's set goes follows from one rule, its span: a byte interval taken from
+// the offsets alone, clipped to the walked bytes [lo, hi), that holds every window
+// start of the unit.  A span inside one range of the walk is that range's workgroup's
+// to write to row u.  A span over the ranges w0 < .. < w1 leaves partial sets in slot
+// 2 w0 + 1 and the slots 2w, w0 < w <= w1, of `part` (sizes in `psize`), and the
+// workgroup of cut w0 folds them and always writes the row.
+//   Records  unit u is record u, of n.  Span: the record's window starts,
+//            [widx[u], widx[u] + nw), nw = max(widx[u + 1] - widx[u] - k, 0).  Exact:
+//            non-empty iff the record has a window, so a record whose last k - 1
+//            bytes alone cross a cut is one range's.  No offsets array.
+//   Groups   unit g is the records [gofs[g], gofs[g + 1]), of ng (gofs: group_offsets
+//            clamped to [0, n]; a descending pair is an empty group).  Span:
+//            [widx[gofs[g]], widx[gofs[g + 1]]).  Conservative: a non-empty span may
+//            hold no window, and telling so would cost a scan of the group's records.
 //
 //   prep    widx[r] = clamp(indices[r], 0, data_bytes) + (data & 15): the offsets
-//           over the 16-byte aligned buffer, as the canonical counter's host does
+//           over the 16-byte aligned buffer, as the canonical counter's host does;
+//           gofs for Groups
+//   fill    size 0 and a row of UINT64_MAX for every unit that neither the cut merge
+//           (a span over a cut) nor the walk (an exact, non-empty span) is certain to
+//           write: the records of no window; every group inside one range, of which
+//           the walk overwrites those it meets a window of.  256 threads per unit, no
+//           LDS.  A record with a window is never filled: no row is written twice.
 //   walk    G workgroups; workgroup w walks cpw = ceil(chunks / G) 16-byte chunks of
-//           [widx[0], widx[n]) (both read on the device), record piece by piece.
-//           A valid window with hash h is a candidate iff the set is not full or
-//           h < T (T: the set's largest value once it holds s), and h is not in the
-//           set (a binary search, so a repeated key is staged once per merge at
-//           most and low-complexity input costs searches, not merges).  Candidates
-//           are appended to a staging buffer of kStage values through an LDS
-//           counter; when it is full it is sorted (bitonic) and merged into the
-//           set: every staged value not equal to its predecessor nor in the set is
-//           kept, set values move up by the kept values below them, kept values
-//           land behind the set values below them, positions >= s fall off.  Lanes
-//           whose candidates did not fit filter them against the new T and append
-//           again.  After N random windows about s / N of the windows are
-//           candidates, so merges become rare and the walk's VALU work bounds the
-//           kernel.  A record wholly inside the range goes to its output row; of a
-//           record that crosses the range's start or end the set goes to the
-//           workgroup's slot 2w (crosses the start) or 2w + 1 (starts here) of
-//           `part`, its size to `psize`.
-//   fill    a record of no window gets size 0 and a row of UINT64_MAX (256 threads
-//           per record, no LDS); a record in one range was written by the walk
-//   merge   one workgroup per cut between two ranges (G - 1): at most one record
-//           has windows on both sides of a cut, and the workgroup of the first cut
-//           it crosses folds its partial sets -- slot 2w0 + 1, then 2w for
-//           w0 < w <= w1, the ranges follow from widx alone -- with the same merge,
-//           kStage values at a time, and writes the row, its tail and its size.
-// Which slots a record has is a function of widx and the geometry, and every slot
-// read was written by this call's walk: nothing in the workspace is accumulated
-// into, and nothing a former call left there is read.
+//           the units' records (both ends read on the device), record piece by piece
+//           (walk_piece, the one chunk loop).  A valid window with hash h is a
+//           candidate iff the set is not full or h < T (T: the set's largest value
+//           once it holds s), and h is not in the set (a binary search, so a repeated
+//           key is staged once per merge at most and low-complexity input costs
+//           searches, not merges).  Candidates are appended to a staging buffer of
+//           kStage values through an LDS counter; when it is full it is sorted
+//           (bitonic) and merged into the set: every staged value not equal to its
+//           predecessor nor in the set is kept, set values move up by the kept values
+//           below them, kept values land behind the set values below them, positions
+//           >= s fall off.  Lanes whose candidates did not fit filter them against the
+//           new T and append again.  After N random windows about s / N of the windows
+//           are candidates, so merges become rare and the walk's VALU work bounds the
+//           kernel.  The set, T and the staged candidates live as long as the unit:
+//           they are carried from one record piece to the next and written out and
+//           reset (flush) when the piece's record belongs to another unit, and at the
+//           end of the range: to row u if the span lies inside this range, else to
+//           slot 2w (the span starts before this range) or 2w + 1 (it starts here).
+//   merge   one workgroup per cut between two ranges (G - 1): spans are disjoint, so
+//           at most one contains the cut, the last unit that starts before it.  If
+//           its span crosses the cut and starts in the range before it (a span over
+//           several cuts belongs to the first) its slots are folded with the same
+//           merge, kStage values at a time, and the row, its tail and its size written.
+//
+// What holds for both kinds of unit:
+// - Every slot read was written or zeroed by this call's walk: each walking workgroup
+//   first zeroes its two psize words (those that return early included, by the thread
+//   that may write them later: program order), a flush then writes the slot and its
+//   size, and the merge reads psize[slot] values of a slot.  So the slot of a range
+//   that holds no window of the crossing group (a stretch of records shorter than k,
+//   longer than a range) reads as an empty set, nothing in the workspace is
+//   accumulated into, and nothing a former call left there is read.
+// - The zeroing costs Records nothing but the two stores: a crossing record has a
+//   window in every range from w0 to w1, so each of its slots is written by a flush
+//   after it was zeroed.
+// - Offsets that do not ascend give unspecified rows, but every search result, row,
+//   slot and range index is clamped to the launch, so nothing strays.
+// - The record number and the unit's state (u, its end, m, T, the staged count) are
+//   wave-uniform (uniform64): the unit search and the span are scalar loads and SGPRs.
 //
 // Constants, shipped / under -DKMC_DIAG_HOOKS (libkmc_diag.so: a few thousand bases
 // pass through many ranges, merges and partial sets; no new symbol):
@@ -47,29 +84,8 @@
 // LDS: 8 s' + 12 kStage bytes and a few words; s' = 1024 / 4096 / 16384 for
 // s <= 1024 / 4096 / 16384: 20 / 44 / 140 KB shipped.
 // Workspace: 8 (n + 1) B of offsets + G (8 + 16 s) B of partial sets,
-// G = min(kWgPerCu * CUs, ceil((data_bytes / 16 + 3) / kMinChunks)).
-//
-// kmc_sketch_from_sequences_grouped: one row per group of consecutive records, the
-// bottom-s of the union of their windows' hashes.  The walk is the one above over
-// the records [gofs[0], gofs[ng]) (gofs: group_offsets clamped to [0, n], written by
-// prep); what changes is the life of the LDS set, which is reset and written out
-// when the group changes, not the record: the set, its threshold T and the staged
-// candidates are carried from one record piece to the next.  Where a set goes
-// follows from the group's byte span [widx[gofs[g]], widx[gofs[g + 1]]) alone
-// (group_span): a span inside one range is that range's to write to row g; a span
-// over the ranges w0 < .. < w1 leaves partial sets in slot 2 w0 + 1 and the slots
-// 2w, w0 < w <= w1, and the workgroup of cut w0 folds them and always writes the row.
-//   prep    widx as above, gofs[g] = clamp(group_offsets[g], 0, n)
-//   empty   every group whose span lies in one range (the empty ones among them)
-//           gets size 0 and a row of UINT64_MAX before the walk: a group of no
-//           window is never met by the walk, and telling so from the offsets would
-//           cost a scan of its records
-//   walk    as above; every workgroup first zeroes its two psize words, so that the
-//           slot of a range that holds no window of the crossing group (a stretch of
-//           records shorter than k, longer than a range) reads as an empty set
-//   merge   one workgroup per cut: the last group that starts before the cut, if
-//           its span crosses the cut and starts in the range before it
-// Workspace: the above + 8 (ng + 1) B of group offsets.
+// G = min(kWgPerCu * CUs, ceil((data_bytes / 16 + 3) / kMinChunks)); Groups:
+// + 8 (ng + 1) B of group offsets.
 //
 // kmc_sketch_merge_groups: one workgroup per group folds the group's input rows, in
 // order, into the LDS set with the same merge, kStage values at a time, and leaves a
@@ -77,6 +93,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "kmc.h"
 #include "kmc_canon_walk.h"
@@ -100,7 +117,7 @@ constexpr int kWaves = kBlock / 64;
 constexpr uint64_t kFill = ~0ull;
 constexpr uint64_t kMaxSeqs = 1ull << 40;
 
-struct SArgs {
+struct Args {
     const char *data;        // rounded down to 16 bytes
     const int64_t *indices;  // the caller's
     int64_t *widx;           // [n + 1] offsets over `data`
@@ -113,12 +130,9 @@ struct SArgs {
     uint64_t seed;
     uint64_t *part;   // [2 G][s]
     uint32_t *psize;  // [2 G]
-    uint64_t *sketches;
+    uint64_t *sketches;  // one row per unit
     uint32_t *sizes;
-};
-
-// kmc_sketch_from_sequences_grouped: the above (sketches, sizes: one row per group) and
-struct GArgs : SArgs {
+    // Groups (Records: null, null, -1)
     const int64_t *group_offsets;  // the caller's
     int64_t *gofs;                 // [ng + 1] clamped to [0, n]
     int64_t ng;
@@ -135,6 +149,56 @@ struct MArgs {  // kmc_sketch_merge_groups
     uint32_t *sizes_out;
 };
 
+// What a unit is (the header comment has the two span rules).  Each policy gives
+//   count       the units of the call
+//   records     the records [r0, r1) the units cover: what is walked
+//   start       the byte unit u starts at (ascending in u)
+//   bytes       the span of unit u, unclipped; empty: ge <= gs
+//   kExactSpan  a non-empty span holds a window
+//   unit_of     the unit of record R, at or after unit `from`; end: its records end
+struct Records {
+    static constexpr bool kExactSpan = true;
+    static __device__ __forceinline__ int64_t count(const Args &a) { return a.n; }
+    static __device__ __forceinline__ void records(const Args &a, int64_t &r0, int64_t &r1) {
+        r0 = 0;
+        r1 = a.n;
+    }
+    static __device__ __forceinline__ int64_t start(const Args &a, int64_t u) { return a.widx[u]; }
+    static __device__ __forceinline__ void bytes(const Args &a, int64_t u, int64_t &gs, int64_t &ge) {
+        const int64_t ra = a.widx[u], re = a.widx[u + 1];
+        gs = ra;
+        ge = ra + (re - ra - a.k > 0 ? re - ra - a.k : 0);
+    }
+    static __device__ __forceinline__ int64_t unit_of(const Args &, int64_t R, int64_t) { return R; }
+    static __device__ __forceinline__ int64_t end(const Args &, int64_t u) { return u + 1; }
+};
+
+struct Groups {
+    static constexpr bool kExactSpan = false;
+    static __device__ __forceinline__ int64_t count(const Args &a) { return a.ng; }
+    static __device__ __forceinline__ void records(const Args &a, int64_t &r0, int64_t &r1) {
+        r0 = a.gofs[0];
+        r1 = a.gofs[a.ng];
+        if (r1 < r0) r1 = r0;
+    }
+    static __device__ __forceinline__ int64_t start(const Args &a, int64_t u) { return a.widx[a.gofs[u]]; }
+    static __device__ __forceinline__ void bytes(const Args &a, int64_t u, int64_t &gs, int64_t &ge) {
+        const int64_t ga = a.gofs[u], gb = a.gofs[u + 1];
+        gs = a.widx[ga];
+        ge = gb > ga ? a.widx[gb] : gs;
+    }
+    // the last group that starts at or before R (groups ascend: from `from` on)
+    static __device__ __forceinline__ int64_t unit_of(const Args &a, int64_t R, int64_t from) {
+        int64_t lo = from, hi = a.ng - 1;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (a.gofs[mid] <= R) lo = mid; else hi = mid - 1;
+        }
+        return lo;
+    }
+    static __device__ __forceinline__ int64_t end(const Args &a, int64_t u) { return a.gofs[u + 1]; }
+};
+
 // The walk's view (kmc_canon_walk.h) with the geometry of this call
 struct Walk {
     const char *data;
@@ -145,8 +209,11 @@ struct Walk {
     int64_t c_lo, cpw;
 };
 
-// over the records [r0, r1) of the call
-__device__ __forceinline__ Walk make_walk(const SArgs &a, int64_t r0, int64_t r1) {
+// over the records of the call's units
+template <class Units>
+__device__ __forceinline__ Walk make_walk(const Args &a) {
+    int64_t r0, r1;
+    Units::records(a, r0, r1);
     Walk W;
     W.data = a.data;
     W.idx = a.widx + r0;
@@ -163,12 +230,31 @@ __device__ __forceinline__ Walk make_walk(const SArgs &a, int64_t r0, int64_t r1
     return W;
 }
 
-__device__ __forceinline__ Walk make_walk(const SArgs &a) { return make_walk(a, 0, a.n); }
+// The span of unit u clipped to the walked bytes; empty: ge <= gs.
+struct Span {
+    int64_t gs, ge;
+    __device__ __forceinline__ bool any() const { return ge > gs; }
+};
 
-// the records of the groups: [gofs[0], gofs[ng])
-__device__ __forceinline__ Walk make_walk(const GArgs &a) {
-    const int64_t r0 = a.gofs[0], r1 = a.gofs[a.ng];
-    return make_walk(a, r0, r1 > r0 ? r1 : r0);
+template <class Units>
+__device__ __forceinline__ Span unit_span(const Walk &W, const Args &a, int64_t u) {
+    Span S;
+    Units::bytes(a, u, S.gs, S.ge);
+    S.gs = S.gs > W.lo ? S.gs : W.lo;
+    S.ge = S.ge < W.hi ? S.ge : W.hi;
+    return S;
+}
+
+// The ranges w0 <= w1 that hold the first and the last byte of a non-empty span.  The
+// walking workgroup w decides the same without a division: w0 == w iff gs is at or
+// past its range's first byte, w1 == w iff ge is at or before its end.
+__device__ __forceinline__ void span_ranges(const Walk &W, int G, const Span &S, int64_t &w0, int64_t &w1) {
+    const int64_t top = G - 1;
+    w0 = ((S.gs >> 4) - W.c_lo) / W.cpw;
+    w1 = (((S.ge - 1) >> 4) - W.c_lo) / W.cpw;
+    // (guard) the slots of this launch only
+    w0 = w0 < 0 ? 0 : (w0 > top ? top : w0);
+    w1 = w1 < w0 ? w0 : (w1 > top ? top : w1);
 }
 
 struct HashOf {
@@ -176,11 +262,19 @@ struct HashOf {
     __device__ __forceinline__ unsigned long long operator()(uint64_t key) const { return sketch_hash(key, seed); }
 };
 
-__global__ __launch_bounds__(256) void sketch_seq_prep_kernel(SArgs a) {
-    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r <= a.n; r += (int64_t)gridDim.x * 256) {
-        int64_t x = a.indices[r];
-        x = x < 0 ? 0 : (x > a.data_bytes ? a.data_bytes : x);
-        a.widx[r] = x + a.mis;
+// ng < 0: no groups
+__global__ __launch_bounds__(256) void sketch_prep_kernel(Args a) {
+    const int64_t top = a.n > a.ng ? a.n : a.ng;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i <= top; i += (int64_t)gridDim.x * 256) {
+        if (i <= a.n) {
+            int64_t x = a.indices[i];
+            x = x < 0 ? 0 : (x > a.data_bytes ? a.data_bytes : x);
+            a.widx[i] = x + a.mis;
+        }
+        if (i <= a.ng) {
+            const int64_t x = a.group_offsets[i];
+            a.gofs[i] = x < 0 ? 0 : (x > a.n ? a.n : x);
+        }
     }
 }
 
@@ -301,41 +395,39 @@ __device__ __forceinline__ int64_t uniform64(int64_t x) {
     return (int64_t)(((uint64_t)h << 32) | l);
 }
 
-// Where the set of group g goes, from the offsets alone: its byte span
-// [widx[gofs[g]], widx[gofs[g + 1]]) lies in the ranges w0 .. w1 (of this launch);
-// cross: in more than one.  An empty group, or a descending pair: no span, not cross.
-struct Span {
-    int64_t gs, w0, w1;
-    bool cross;
-};
+// The set as a row: its m values, the tail of UINT64_MAX and the size.
+template <int CAP>
+__device__ __forceinline__ void write_row(const SetLds<CAP> &L, uint64_t *row, uint32_t *size, int m, int s) {
+    for (int i = threadIdx.x; i < s; i += kBlock) row[i] = i < m ? L.set[i] : kFill;
+    if (threadIdx.x == 0) *size = (uint32_t)m;
+}
 
-__device__ __forceinline__ Span group_span(const Walk &W, const GArgs &a, int64_t g) {
-    const int64_t ga = a.gofs[g], gb = a.gofs[g + 1];
-    int64_t gs = a.widx[ga], ge = gb > ga ? a.widx[gb] : gs;
-    gs = gs > W.lo ? gs : W.lo;
-    ge = ge < W.hi ? ge : W.hi;
-    Span S;
-    S.gs = gs;
-    S.w0 = S.w1 = 0;
-    S.cross = false;
-    if (ge <= gs) return S;
-    const int64_t top = a.G - 1;
-    int64_t w0 = ((gs >> 4) - W.c_lo) / W.cpw, w1 = (((ge - 1) >> 4) - W.c_lo) / W.cpw;
-    // (guard) the slots of this launch only
-    w0 = w0 < 0 ? 0 : (w0 > top ? top : w0);
-    w1 = w1 < w0 ? w0 : (w1 > top ? top : w1);
-    S.w0 = w0;
-    S.w1 = w1;
-    S.cross = w1 > w0;
-    return S;
+// The set as a partial set: its m values and the size.
+template <int CAP>
+__device__ __forceinline__ void write_part(const SetLds<CAP> &L, uint64_t *dst, uint32_t *size, int m) {
+    for (int i = threadIdx.x; i < m; i += kBlock) dst[i] = L.set[i];
+    if (threadIdx.x == 0) *size = (uint32_t)m;
+}
+
+// Folds the first min(pm, s) values of the ascending row `src` into the set, kStage
+// at a time, up to the first run that starts at or above T.
+template <int CAP>
+__device__ __forceinline__ void fold_row(SetLds<CAP> &L, const uint64_t *src, uint32_t pm, int s, int &m, uint64_t &T) {
+    const int tid = threadIdx.x;
+    if (pm > (uint32_t)s) pm = (uint32_t)s;
+    for (int c0 = 0; c0 < (int)pm; c0 += kStage) {
+        if (m == s && src[c0] >= T) break;  // ascending: nothing below T is left
+        const int c = (int)pm - c0 < kStage ? (int)pm - c0 : kStage;
+        if (tid < c) L.stage[tid] = src[c0 + tid];
+        lds_barrier();
+        m = merge_stage(L, m, s, c);
+        T = m == s ? L.set[s - 1] : kFill;
+    }
 }
 
 // The windows of record piece [ps, pe): every candidate hash goes through the staging
 // buffer into the set (m values, threshold T, `staged` values left in the buffer,
 // ci: the counter of the next round).  Every thread of the workgroup calls it.
-// The grouped walk's copy of the chunk loop of sketch_seq_walk_kernel below: that
-// kernel keeps its loop in place, because calling this function from it changed its
-// register allocation and schedule, and its device code is to stay as it was.
 template <bool FWD, bool BIGK, int CAP>
 __device__ __forceinline__ void walk_piece(SetLds<CAP> &L, const Walk &W, const HashOf hf, int64_t ps, int64_t pe,
                                            int64_t rend, int s, int &m, uint32_t &staged, uint64_t &T, int &ci) {
@@ -392,118 +484,56 @@ __device__ __forceinline__ void walk_piece(SetLds<CAP> &L, const Walk &W, const 
     }
 }
 
-template <bool FWD, bool BIGK, int CAP>
-__global__ __launch_bounds__(kBlock) void sketch_seq_walk_kernel(SArgs a) {
-    __shared__ SetLds<CAP> L;
-    const Walk W = make_walk(a);
-    const int tid = threadIdx.x, s = (int)a.s, w = blockIdx.x;
-    const HashOf hf{a.seed};
-    if (tid < 3) L.ctr[tid] = 0u;
-    int ci = 0;  // the counter of the next round (the one after it is zero already)
-    __syncthreads();
-    for_each_piece(W, &L.first, [&](int64_t r, int64_t ps, int64_t pe, int64_t rend) {
-        int m = 0;
-        uint32_t staged = 0;  // values in the staging buffer (workgroup-uniform)
-        uint64_t T = kFill;
-        const int64_t c0 = ps >> 4, c1 = ((pe - 1) >> 4) + 1;
-        ChunkRaw nx = chunk_raw(W, (c0 + tid) << 4);
-        for (int64_t cb = c0; cb < c1; cb += kBlock) {
-            const int64_t c = cb + tid;
-            unsigned long long h[16];
-            const ChunkRaw cr = nx;
-            nx = chunk_raw(W, (c + kBlock) << 4);  // next round's chunk
-            uint32_t pend = chunk_keys<FWD, BIGK>(W, cr, c << 4, ps, pe, rend, hf, h);  // (past the piece: 0)
-            for (;;) {
-                const bool full = m == s;
-                uint32_t cm = 0u;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) cm |= (uint32_t)(!full || h[j] < T) << j;
-                pend &= cm;
-                if (pend) {
-#pragma unroll
-                    for (int j = 0; j < 16; ++j)
-                        if (((pend >> j) & 1u) && in_set(L.set, m, h[j])) pend &= ~(1u << j);
-                }
-                const uint32_t cnt = (uint32_t)__popc(pend);
-                if (cnt) {
-                    uint32_t at = staged + __hip_atomic_fetch_add(&L.ctr[ci], cnt, __ATOMIC_RELAXED,
-                                                                  __HIP_MEMORY_SCOPE_WORKGROUP);
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        if ((pend >> j) & 1u) {
-                            if (at < (uint32_t)kStage) {
-                                L.stage[at] = h[j];
-                                pend &= ~(1u << j);
-                            }
-                            ++at;
-                        }
-                    }
-                }
-                lds_barrier();
-                const uint32_t total = staged + L.ctr[ci];
-                // the counter of the round before: every thread has read it (it passed this
-                // barrier), and its next adds come after the next barrier
-                if (tid == 0) L.ctr[(ci + 2) % 3] = 0u;
-                ci = (ci + 1) % 3;
-                if (total < (uint32_t)kStage) {
-                    staged = total;
-                    break;
-                }
-                m = merge_stage(L, m, s, kStage);
-                T = m == s ? L.set[s - 1] : kFill;
-                staged = 0;
-                if (total == (uint32_t)kStage) break;  // (else some lanes still hold candidates)
-            }
+// Size 0 and a row of UINT64_MAX, before the walk, for every unit whose row neither
+// the cut merge nor the walk is certain to write (no LDS).
+template <class Units>
+__global__ __launch_bounds__(256) void sketch_fill_kernel(Args a) {
+    const Walk W = make_walk<Units>(a);
+    const int s = (int)a.s;
+    for (int64_t u = blockIdx.x; u < Units::count(a); u += gridDim.x) {
+        const Span S = unit_span<Units>(W, a, u);
+        if (S.any()) {
+            if (Units::kExactSpan) continue;  // the walk meets a window of it
+            int64_t w0, w1;
+            span_ranges(W, a.G, S, w0, w1);
+            if (w1 > w0) continue;  // the cut merge's
         }
-        if (staged) m = merge_stage(L, m, s, (int)staged);
-        const int64_t ra = W.idx[r];
-        const int64_t nw = rend - ra - W.k > 0 ? rend - ra - W.k : 0;
-        if (ps == ra && pe == ra + nw) {  // the whole record: its row
-            uint64_t *row = a.sketches + r * (int64_t)s;
-            for (int i = tid; i < s; i += kBlock) row[i] = i < m ? L.set[i] : kFill;
-            if (tid == 0) a.sizes[r] = (uint32_t)m;
-        } else {  // a partial set: crosses this range's start (slot 2w) or only its end (2w + 1)
-            const int64_t slot = 2 * (int64_t)w + (ps == ra ? 1 : 0);
-            uint64_t *dst = a.part + slot * (int64_t)s;
-            for (int i = tid; i < m; i += kBlock) dst[i] = L.set[i];
-            if (tid == 0) a.psize[slot] = (uint32_t)m;
-        }
-        lds_barrier();  // the set is read out before the next piece's merges
-    });
+        uint64_t *row = a.sketches + u * (int64_t)s;
+        for (int i = threadIdx.x; i < s; i += 256) row[i] = kFill;
+        if (threadIdx.x == 0) a.sizes[u] = 0u;
+    }
 }
 
-// The grouped walk: the set, its threshold and the staged candidates outlive the
-// record piece; they are written out (flush) and reset when the piece's record belongs
-// to another group than the one before, and at the end of the range.
-template <bool FWD, bool BIGK, int CAP>
-__global__ __launch_bounds__(kBlock) void sketch_group_walk_kernel(GArgs a) {
+// The set, its threshold and the staged candidates outlive the record piece; they are
+// written out (flush) and reset when the piece's record belongs to another unit than
+// the one before, and at the end of the range.
+template <class Units, bool FWD, bool BIGK, int CAP>
+__global__ __launch_bounds__(kBlock) void sketch_walk_kernel(Args a) {
     __shared__ SetLds<CAP> L;
-    const Walk W = make_walk(a);
+    const Walk W = make_walk<Units>(a);
     const int tid = threadIdx.x, s = (int)a.s, w = blockIdx.x;
     const HashOf hf{a.seed};
-    // the slots of a range that holds no window of the crossing group read as empty
-    // (zeroed by the thread that may write them later: program order)
+    const int64_t b0 = (W.c_lo + (int64_t)w * W.cpw) << 4, b1 = b0 + (W.cpw << 4);  // this range's bytes
+    // a slot of this range that no flush writes reads as empty (zeroed by the thread
+    // that may write it later: program order)
     if (tid == 0) a.psize[2 * w] = a.psize[2 * w + 1] = 0u;
     if (tid < 3) L.ctr[tid] = 0u;
-    int ci = 0;
+    int ci = 0;  // the counter of the next round (the one after it is zero already)
     int m = 0;
-    uint32_t staged = 0;
+    uint32_t staged = 0;  // values in the staging buffer (workgroup-uniform)
     uint64_t T = kFill;
-    int64_t g = -1, g_end = 0;  // (wave-uniform) the records below g_end are group g's
+    int64_t u = -1, u_end = 0;  // (wave-uniform) the records below u_end are unit u's
     const auto flush = [&]() {
         if (staged) m = merge_stage(L, m, s, (int)staged);
-        const Span S = group_span(W, a, g);
-        if (!S.cross) {  // the whole group: its row
-            uint64_t *row = a.sketches + g * (int64_t)s;
-            for (int i = tid; i < s; i += kBlock) row[i] = i < m ? L.set[i] : kFill;
-            if (tid == 0) a.sizes[g] = (uint32_t)m;
-        } else {  // a partial set: the span starts before this range (slot 2w) or in it (2w + 1)
-            const int64_t slot = 2 * (int64_t)w + (S.w0 == w ? 1 : 0);
-            uint64_t *dst = a.part + slot * (int64_t)s;
-            for (int i = tid; i < m; i += kBlock) dst[i] = L.set[i];
-            if (tid == 0) a.psize[slot] = (uint32_t)m;
+        const Span S = unit_span<Units>(W, a, u);
+        const bool first = S.gs >= b0;  // the span starts in this range
+        if (first && S.ge <= b1) {      // and ends in it, the whole unit: its row
+            write_row(L, a.sketches + u * (int64_t)s, a.sizes + u, m, s);
+        } else {
+            const int64_t slot = 2 * (int64_t)w + (first ? 1 : 0);
+            write_part(L, a.part + slot * (int64_t)s, a.psize + slot, m);
         }
-        lds_barrier();  // the set is read out before the next group's merges
+        lds_barrier();  // the set is read out before the next unit's merges
         m = 0;
         staged = 0;
         T = kFill;
@@ -511,173 +541,53 @@ __global__ __launch_bounds__(kBlock) void sketch_group_walk_kernel(GArgs a) {
     __syncthreads();
     for_each_piece(W, &L.first, [&](int64_t r, int64_t ps, int64_t pe, int64_t rend) {
         const int64_t R = uniform64(r + (W.idx - a.widx));  // the record in the call's numbering
-        if (R >= g_end) {
-            if (g >= 0) flush();
-            // the last group that starts at or before R (groups ascend: from g on)
-            int64_t lo = g < 0 ? 0 : g, hi = a.ng - 1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (a.gofs[mid] <= R) lo = mid; else hi = mid - 1;
-            }
-            g = lo;
-            g_end = a.gofs[g + 1];
-            if (g_end <= R) g_end = R + 1;  // (guard: offsets that do not ascend)
+        if (R >= u_end) {
+            if (u >= 0) flush();
+            u = Units::unit_of(a, R, u < 0 ? 0 : u);
+            u_end = Units::end(a, u);
+            if (u_end <= R) u_end = R + 1;  // (guard: offsets that do not ascend)
         }
         walk_piece<FWD, BIGK>(L, W, hf, ps, pe, rend, s, m, staged, T, ci);
     });
-    if (g >= 0) flush();
+    if (u >= 0) flush();
 }
 
-// The records of no window: size 0 and a row of UINT64_MAX (no LDS; the walk never
-// meets them, and neither does the merge).
-__global__ __launch_bounds__(256) void sketch_seq_fill_kernel(SArgs a) {
-    const Walk W = make_walk(a);
-    const int s = (int)a.s;
-    for (int64_t r = blockIdx.x; r < a.n; r += gridDim.x) {
-        const int64_t ra = W.idx[r], re = W.idx[r + 1];
-        const int64_t nw = re - ra - W.k > 0 ? re - ra - W.k : 0;
-        const int64_t ps = ra > W.lo ? ra : W.lo, pe = ra + nw < W.hi ? ra + nw : W.hi;
-        if (ps < pe) continue;
-        uint64_t *row = a.sketches + r * (int64_t)s;
-        for (int i = threadIdx.x; i < s; i += 256) row[i] = kFill;
-        if (threadIdx.x == 0) a.sizes[r] = 0u;
-    }
-}
-
-// One workgroup per cut between two ranges (G - 1 of them): the record whose windows
-// lie on both sides of cut b, if there is one and b is the first cut it crosses (a
-// record over several cuts belongs to the first), has its partial sets folded.
-template <int CAP>
-__global__ __launch_bounds__(kBlock) void sketch_seq_merge_kernel(SArgs a) {
+// One workgroup per cut between two ranges (G - 1 of them): the last unit that starts
+// before cut b, if its span crosses the cut and b is the first cut it crosses, has its
+// partial sets folded and its row written (a slot no window went to has size 0).
+template <class Units, int CAP>
+__global__ __launch_bounds__(kBlock) void sketch_cut_merge_kernel(Args a) {
     __shared__ SetLds<CAP> L;
-    const Walk W = make_walk(a);
-    const int tid = threadIdx.x, s = (int)a.s;
+    const Walk W = make_walk<Units>(a);
+    const int s = (int)a.s;
     const int64_t b = blockIdx.x;
     const int64_t cut = (W.c_lo + (b + 1) * W.cpw) << 4;  // first byte of range b + 1
     if (cut <= W.lo || cut >= W.hi) return;
-    if (tid == 0) {  // last record r with idx[r] < cut: the only one that can have windows on both sides
-        int64_t lo = 0, hi = a.n - 1;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) >> 1;
-            if (W.idx[mid] < cut) lo = mid; else hi = mid - 1;
-        }
-        L.first = lo;
+    int64_t lo = 0, hi = Units::count(a) - 1;  // (wave-uniform: scalar loads)
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (Units::start(a, mid) < cut) lo = mid; else hi = mid - 1;
     }
-    __syncthreads();
-    const int64_t r = L.first;
-    const int64_t ra = W.idx[r], re = W.idx[r + 1];
-    const int64_t nw = re - ra - W.k > 0 ? re - ra - W.k : 0;
-    const int64_t ps = ra > W.lo ? ra : W.lo, pe = ra + nw < W.hi ? ra + nw : W.hi;
-    if (ps >= cut || pe <= cut) return;  // no window before the cut, or none from it on
-    int64_t w0 = ((ps >> 4) - W.c_lo) / W.cpw, w1 = (((pe - 1) >> 4) - W.c_lo) / W.cpw;
-    if (w0 != b) return;  // an earlier cut's workgroup has the record
-    // (guard) the slots of this launch only
-    w0 = w0 < 0 ? 0 : (w0 > a.G - 1 ? a.G - 1 : w0);
-    w1 = w1 < w0 ? w0 : (w1 > a.G - 1 ? a.G - 1 : w1);
+    const int64_t u = lo;
+    const Span S = unit_span<Units>(W, a, u);
+    if (S.gs >= cut || S.ge <= cut) return;  // nothing before the cut, or nothing from it on
+    int64_t w0, w1;
+    span_ranges(W, a.G, S, w0, w1);
+    if (w0 != b) return;  // an earlier cut's workgroup has the unit
     int m = 0;
     uint64_t T = kFill;
     for (int64_t w = w0; w <= w1; ++w) {
         const int64_t slot = 2 * w + (w == w0 ? 1 : 0);
-        const uint64_t *src = a.part + slot * (int64_t)s;
-        uint32_t pm = a.psize[slot];
-        if (pm > a.s) pm = a.s;
-        for (int c0 = 0; c0 < (int)pm; c0 += kStage) {
-            if (m == s && src[c0] >= T) break;  // ascending: nothing below T is left
-            const int c = (int)pm - c0 < kStage ? (int)pm - c0 : kStage;
-            if (tid < c) L.stage[tid] = src[c0 + tid];
-            lds_barrier();
-            m = merge_stage(L, m, s, c);
-            T = m == s ? L.set[s - 1] : kFill;
-        }
-    }
-    uint64_t *row = a.sketches + r * (int64_t)s;
-    for (int i = tid; i < s; i += kBlock) row[i] = i < m ? L.set[i] : kFill;
-    if (tid == 0) a.sizes[r] = (uint32_t)m;
-}
-
-// ---------------------------------------------------------------------------
-// groups of records
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sketch_group_prep_kernel(GArgs a) {
-    const int64_t top = a.n > a.ng ? a.n : a.ng;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i <= top; i += (int64_t)gridDim.x * 256) {
-        if (i <= a.n) {
-            int64_t x = a.indices[i];
-            x = x < 0 ? 0 : (x > a.data_bytes ? a.data_bytes : x);
-            a.widx[i] = x + a.mis;
-        }
-        if (i <= a.ng) {
-            const int64_t x = a.group_offsets[i];
-            a.gofs[i] = x < 0 ? 0 : (x > a.n ? a.n : x);
-        }
-    }
-}
-
-// Size 0 and a row of UINT64_MAX for every group whose span lies in one range, before
-// the walk: the walk overwrites those it meets a window of (the rows of the crossing
-// groups are the merge's, written in any case).
-__global__ __launch_bounds__(256) void sketch_group_empty_kernel(GArgs a) {
-    const Walk W = make_walk(a);
-    const int s = (int)a.s;
-    for (int64_t g = blockIdx.x; g < a.ng; g += gridDim.x) {
-        if (group_span(W, a, g).cross) continue;
-        uint64_t *row = a.sketches + g * (int64_t)s;
-        for (int i = threadIdx.x; i < s; i += 256) row[i] = kFill;
-        if (threadIdx.x == 0) a.sizes[g] = 0u;
-    }
-}
-
-// Folds the first min(pm, s) values of the ascending row `src` into the set, kStage
-// at a time, up to the first run that starts at or above T.
-template <int CAP>
-__device__ __forceinline__ void fold_row(SetLds<CAP> &L, const uint64_t *src, uint32_t pm, int s, int &m, uint64_t &T) {
-    const int tid = threadIdx.x;
-    if (pm > (uint32_t)s) pm = (uint32_t)s;
-    for (int c0 = 0; c0 < (int)pm; c0 += kStage) {
-        if (m == s && src[c0] >= T) break;  // ascending: nothing below T is left
-        const int c = (int)pm - c0 < kStage ? (int)pm - c0 : kStage;
-        if (tid < c) L.stage[tid] = src[c0 + tid];
-        lds_barrier();
-        m = merge_stage(L, m, s, c);
-        T = m == s ? L.set[s - 1] : kFill;
-    }
-}
-
-// One workgroup per cut between two ranges: the last group that starts before cut b,
-// if its span crosses the cut and b is the first cut it crosses, has its partial sets
-// folded and its row written (a slot no window went to has size 0).
-template <int CAP>
-__global__ __launch_bounds__(kBlock) void sketch_group_merge_kernel(GArgs a) {
-    __shared__ SetLds<CAP> L;
-    const Walk W = make_walk(a);
-    const int tid = threadIdx.x, s = (int)a.s;
-    const int64_t b = blockIdx.x;
-    const int64_t cut = (W.c_lo + (b + 1) * W.cpw) << 4;  // first byte of range b + 1
-    if (cut <= W.lo || cut >= W.hi) return;
-    int64_t lo = 0, hi = a.ng - 1;  // (wave-uniform: scalar loads)
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (a.widx[a.gofs[mid]] < cut) lo = mid; else hi = mid - 1;
-    }
-    const int64_t g = lo;
-    const Span S = group_span(W, a, g);
-    if (!S.cross || S.w0 != b || S.gs >= cut) return;  // none, or an earlier cut's workgroup has the group
-    int m = 0;
-    uint64_t T = kFill;
-    for (int64_t w = S.w0; w <= S.w1; ++w) {
-        const int64_t slot = 2 * w + (w == S.w0 ? 1 : 0);
         fold_row(L, a.part + slot * (int64_t)s, a.psize[slot], s, m, T);
     }
-    uint64_t *row = a.sketches + g * (int64_t)s;
-    for (int i = tid; i < s; i += kBlock) row[i] = i < m ? L.set[i] : kFill;
-    if (tid == 0) a.sizes[g] = (uint32_t)m;
+    write_row(L, a.sketches + u * (int64_t)s, a.sizes + u, m, s);
 }
 
 // kmc_sketch_merge_groups: a workgroup folds the rows of its groups, one group at a time.
 template <int CAP>
 __global__ __launch_bounds__(kBlock) void sketch_merge_groups_kernel(MArgs a) {
     __shared__ SetLds<CAP> L;
-    const int tid = threadIdx.x, s = (int)a.s;
+    const int s = (int)a.s;
     for (int64_t g = blockIdx.x; g < a.ng; g += gridDim.x) {
         int64_t ra = a.group_offsets[g], rb = a.group_offsets[g + 1];
         ra = ra < 0 ? 0 : (ra > a.rows ? a.rows : ra);
@@ -685,9 +595,7 @@ __global__ __launch_bounds__(kBlock) void sketch_merge_groups_kernel(MArgs a) {
         int m = 0;
         uint64_t T = kFill;
         for (int64_t r = ra; r < rb; ++r) fold_row(L, a.in + r * (int64_t)s, a.sizes_in[r], s, m, T);
-        uint64_t *row = a.out + g * (int64_t)s;
-        for (int i = tid; i < s; i += kBlock) row[i] = i < m ? L.set[i] : kFill;
-        if (tid == 0) a.sizes_out[g] = (uint32_t)m;
+        write_row(L, a.out + g * (int64_t)s, a.sizes_out + g, m, s);
         lds_barrier();  // the set is read out before the next group's merges
     }
 }
@@ -739,10 +647,20 @@ inline int seq_check(int k, uint64_t num_seqs, uint64_t data_bytes, uint32_t ske
 
 DeviceCache q_ws;  // library-owned workspace
 
-// The workspace of a call (ng < 0: no groups) and the arguments both kinds of call share.
-inline int seq_bind(SArgs &a, int64_t **gofs, const char *data, const int64_t *indices, uint64_t num_seqs,
-                    uint64_t data_bytes, int k, unsigned flags, uint32_t sketch_size, uint64_t seed, uint64_t *sketches,
-                    uint32_t *sketch_sizes, int64_t ng, void *workspace, size_t workspace_bytes) {
+// f(the set capacity of sketch size s, as an integral constant)
+template <class F>
+inline void for_cap(uint32_t s, F &&f) {
+    if (s <= 1024) f(std::integral_constant<int, 1024>{});
+    else if (s <= 4096) f(std::integral_constant<int, 4096>{});
+    else f(std::integral_constant<int, KMC_SKETCH_MAX_SIZE>{});
+}
+
+// Both entry points after their argument checks: the workspace of the call (Records:
+// group_offsets null, ng = -1) and the launches.
+template <class Units>
+int sketch_units(const char *data, const int64_t *indices, uint64_t num_seqs, uint64_t data_bytes,
+                 const int64_t *group_offsets, int64_t ng, int k, unsigned flags, uint32_t sketch_size, uint64_t seed,
+                 uint64_t *sketches, uint32_t *sketch_sizes, void *workspace, size_t workspace_bytes, hipStream_t st) {
     int device = 0, cus = 0;
     if (hipError_t he = hipGetDevice(&device)) return (int)he;
     if (int e = device_cus(device, &cus)) return e;
@@ -755,6 +673,7 @@ inline int seq_bind(SArgs &a, int64_t **gofs, const char *data, const int64_t *i
     // any `data` pointer: rounded down to 16 bytes, every offset moved up by the
     // difference (kmc_count_canonical_hash's rule, applied on the device by prep)
     const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
+    Args a;
     a.data = data - mis;
     a.indices = indices;
     a.widx = L.widx;
@@ -770,38 +689,27 @@ inline int seq_bind(SArgs &a, int64_t **gofs, const char *data, const int64_t *i
     a.psize = L.psize;
     a.sketches = sketches;
     a.sizes = sketch_sizes;
-    *gofs = L.gofs;
-    return KMC_OK;
-}
-
-template <int CAP>
-void launch_seq(const SArgs &a, unsigned rec_grid, hipStream_t st) {
-    const bool fwd = a.flags & KMC_CANON_FORWARD, big = a.k >= 16;
-    const dim3 g((unsigned)a.G), b(kBlock);
-    if (fwd) {
-        if (big) hipLaunchKernelGGL((sketch_seq_walk_kernel<true, true, CAP>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((sketch_seq_walk_kernel<true, false, CAP>), g, b, 0, st, a);
-    } else {
-        if (big) hipLaunchKernelGGL((sketch_seq_walk_kernel<false, true, CAP>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((sketch_seq_walk_kernel<false, false, CAP>), g, b, 0, st, a);
-    }
-    hipLaunchKernelGGL(sketch_seq_fill_kernel, dim3(rec_grid), dim3(256), 0, st, a);
-    if (a.G > 1) hipLaunchKernelGGL((sketch_seq_merge_kernel<CAP>), dim3((unsigned)a.G - 1), b, 0, st, a);
-}
-
-template <int CAP>
-void launch_group(const GArgs &a, unsigned group_grid, hipStream_t st) {
-    const bool fwd = a.flags & KMC_CANON_FORWARD, big = a.k >= 16;
-    const dim3 g((unsigned)a.G), b(kBlock);
-    hipLaunchKernelGGL(sketch_group_empty_kernel, dim3(group_grid), dim3(256), 0, st, a);
-    if (fwd) {
-        if (big) hipLaunchKernelGGL((sketch_group_walk_kernel<true, true, CAP>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((sketch_group_walk_kernel<true, false, CAP>), g, b, 0, st, a);
-    } else {
-        if (big) hipLaunchKernelGGL((sketch_group_walk_kernel<false, true, CAP>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((sketch_group_walk_kernel<false, false, CAP>), g, b, 0, st, a);
-    }
-    if (a.G > 1) hipLaunchKernelGGL((sketch_group_merge_kernel<CAP>), dim3((unsigned)a.G - 1), b, 0, st, a);
+    a.group_offsets = group_offsets;
+    a.gofs = L.gofs;
+    a.ng = ng;
+    const int64_t top = n > ng ? n : ng, pg = (top + 1 + 255) / 256, units = ng < 0 ? n : ng;
+    hipLaunchKernelGGL(sketch_prep_kernel, dim3((unsigned)(pg < 4096 ? pg : 4096)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(sketch_fill_kernel<Units>, dim3((unsigned)(units < kMaxGridX ? units : kMaxGridX)), dim3(256), 0,
+                       st, a);
+    for_cap(sketch_size, [&](auto cap) {
+        constexpr int CAP = decltype(cap)::value;
+        const bool fwd = flags & KMC_CANON_FORWARD, big = k >= 16;
+        const dim3 g((unsigned)G), b(kBlock);
+        if (fwd) {
+            if (big) hipLaunchKernelGGL((sketch_walk_kernel<Units, true, true, CAP>), g, b, 0, st, a);
+            else hipLaunchKernelGGL((sketch_walk_kernel<Units, true, false, CAP>), g, b, 0, st, a);
+        } else {
+            if (big) hipLaunchKernelGGL((sketch_walk_kernel<Units, false, true, CAP>), g, b, 0, st, a);
+            else hipLaunchKernelGGL((sketch_walk_kernel<Units, false, false, CAP>), g, b, 0, st, a);
+        }
+        if (G > 1) hipLaunchKernelGGL((sketch_cut_merge_kernel<Units, CAP>), dim3((unsigned)G - 1), b, 0, st, a);
+    });
+    return (int)hipGetLastError();
 }
 
 // [p, p + bytes) and [q, q + qbytes) share a byte
@@ -831,19 +739,8 @@ extern "C" int kmc_sketch_from_sequences(const char *data, const int64_t *indice
     if (num_seqs == 0) return KMC_OK;
     if (!indices || !sketches || !sketch_sizes) return KMC_ERR_INVALID_ARG;
     if (data_bytes > 0 && !data) return KMC_ERR_INVALID_ARG;
-    SArgs a;
-    int64_t *unused = nullptr;
-    if (int e = seq_bind(a, &unused, data, indices, num_seqs, data_bytes, k, flags, sketch_size, seed, sketches,
-                         sketch_sizes, -1, workspace, workspace_bytes))
-        return e;
-    const int64_t n = a.n;
-    const int64_t pg = (n + 1 + 255) / 256;
-    hipLaunchKernelGGL(sketch_seq_prep_kernel, dim3((unsigned)(pg < 4096 ? pg : 4096)), dim3(256), 0, stream, a);
-    const unsigned rec_grid = (unsigned)(n < kMaxGridX ? n : kMaxGridX);
-    if (sketch_size <= 1024) launch_seq<1024>(a, rec_grid, stream);
-    else if (sketch_size <= 4096) launch_seq<4096>(a, rec_grid, stream);
-    else launch_seq<KMC_SKETCH_MAX_SIZE>(a, rec_grid, stream);
-    return (int)hipGetLastError();
+    return sketch_units<Records>(data, indices, num_seqs, data_bytes, nullptr, -1, k, flags, sketch_size, seed,
+                                 sketches, sketch_sizes, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t kmc_sketch_from_sequences_grouped_workspace_size(uint64_t num_seqs, uint64_t num_groups,
@@ -869,19 +766,8 @@ extern "C" int kmc_sketch_from_sequences_grouped(const char *data, const int64_t
     if (num_seqs == 0) return KMC_OK;
     if (!indices || !sketches || !sketch_sizes) return KMC_ERR_INVALID_ARG;
     if (data_bytes > 0 && !data) return KMC_ERR_INVALID_ARG;
-    GArgs a;
-    if (int e = seq_bind(a, &a.gofs, data, indices, num_seqs, data_bytes, k, flags, sketch_size, seed, sketches,
-                         sketch_sizes, (int64_t)num_groups, workspace, workspace_bytes))
-        return e;
-    a.group_offsets = group_offsets;
-    a.ng = (int64_t)num_groups;
-    const int64_t top = a.n > a.ng ? a.n : a.ng, pg = (top + 1 + 255) / 256;
-    hipLaunchKernelGGL(sketch_group_prep_kernel, dim3((unsigned)(pg < 4096 ? pg : 4096)), dim3(256), 0, stream, a);
-    const unsigned group_grid = (unsigned)(a.ng < kMaxGridX ? a.ng : kMaxGridX);
-    if (sketch_size <= 1024) launch_group<1024>(a, group_grid, stream);
-    else if (sketch_size <= 4096) launch_group<4096>(a, group_grid, stream);
-    else launch_group<KMC_SKETCH_MAX_SIZE>(a, group_grid, stream);
-    return (int)hipGetLastError();
+    return sketch_units<Groups>(data, indices, num_seqs, data_bytes, group_offsets, (int64_t)num_groups, k, flags,
+                                sketch_size, seed, sketches, sketch_sizes, workspace, workspace_bytes, stream);
 }
 
 extern "C" int kmc_sketch_merge_groups(const uint64_t *sketches_in, const uint32_t *sizes_in, uint64_t num_rows,
@@ -906,8 +792,8 @@ extern "C" int kmc_sketch_merge_groups(const uint64_t *sketches_in, const uint32
     a.out = sketches_out;
     a.sizes_out = sizes_out;
     const dim3 g((unsigned)(a.ng < kMaxGridX ? a.ng : kMaxGridX)), b(kBlock);
-    if (sketch_size <= 1024) hipLaunchKernelGGL((sketch_merge_groups_kernel<1024>), g, b, 0, stream, a);
-    else if (sketch_size <= 4096) hipLaunchKernelGGL((sketch_merge_groups_kernel<4096>), g, b, 0, stream, a);
-    else hipLaunchKernelGGL((sketch_merge_groups_kernel<KMC_SKETCH_MAX_SIZE>), g, b, 0, stream, a);
+    for_cap(sketch_size, [&](auto cap) {
+        hipLaunchKernelGGL((sketch_merge_groups_kernel<decltype(cap)::value>), g, b, 0, stream, a);
+    });
     return (int)hipGetLastError();
 }

@@ -16,6 +16,7 @@ import os
 import numpy as np
 import pytest
 
+import sketch_group_util as GU
 import sketch_util as S
 
 pytestmark = pytest.mark.gpu
@@ -261,6 +262,64 @@ def test_seq_record_boundaries_on_range_cuts(kmc, oracle, cuda, lib):
         assert_sketch(gpu_seq(kmc, cuda, data, idx, k, s), exp)
 
 
+def diag_range_bytes(nbytes):
+    """Bytes per range of the diag build's walk over `nbytes` of 16-byte aligned records
+    (kmc_sketch_seq.hip: 16 chunks per range at least; far fewer ranges than 2 x CUs)."""
+    chunks = (nbytes + 15) // 16
+    groups = -(-(nbytes // 16 + 3) // 16)
+    return 16 * max(-(-chunks // groups), 1)
+
+
+def records_at(rng, starts, total):
+    """Records that start at the bytes `starts` (0 first), the last one's terminator at total - 1."""
+    ends = list(starts[1:]) + [total]
+    return pack([bases(rng, e - a - 1) for a, e in zip(starts, ends)])
+
+
+@pytest.mark.parametrize("lib", LIBS)
+def test_seq_window_span_against_byte_span(kmc, oracle, cuda, lib):
+    """Where a record's set goes follows from its window starts, not from its bytes (diag
+    build, cuts every 256 bytes).  Record 1 starts at 300 and has 212 windows: the last
+    one starts at 511 and the last k - 1 bases and the terminator lie beyond cut 512, so
+    it is range 1's whole record.  Record 3 starts on cut 768 and crosses two cuts.
+    Record 4 starts in range 5, crosses cut 1536 and its windows end on cut 2048.
+    s = 16: the sets fill and merges run at 64 staged values."""
+    k, s = 21, 16
+    def make():
+        rng = np.random.default_rng(16)
+        starts = [0, 300, 533, 768, 1469, 2069]
+        data, idx = records_at(rng, starts, 4096)
+        assert data.size == 4096 and diag_range_bytes(data.size) == 256
+        nw = np.diff(idx) - k
+        assert idx[1] + nw[1] == 512 and idx[2] > 512 and idx[3] == 768 and idx[4] + nw[4] == 2048 < idx[5]
+        return data, idx, expected(oracle, data, idx, k, s)
+    data, idx, exp = cached("spans", make)
+    assert list(exp[1]) == [s] * 6
+    with which(kmc, lib):
+        assert_sketch(gpu_seq(kmc, cuda, data, idx, k, s), exp)
+
+
+@pytest.mark.parametrize("lib", LIBS)
+def test_seq_windowless_stretch_between_long_records(kmc, oracle, cuda, lib):
+    """60 records of 10 bases (660 bytes, k = 21: no window; in the diag build at least two
+    whole 256-byte ranges hold nothing else) between two records of 1 kbase that each cross
+    cuts: the short ones get size 0 and rows of UINT64_MAX, whatever the walk's workgroups
+    zeroed or left in their slots."""
+    k, s = 21, 16
+    def make():
+        rng = np.random.default_rng(17)
+        data, idx = pack([bases(rng, 1000)] + [bases(rng, 10) for _ in range(60)] + [bases(rng, 1000)])
+        rb = diag_range_bytes(data.size)
+        assert rb == 256 and idx[61] // rb - (idx[1] + rb - 1) // rb >= 2
+        return data, idx, expected(oracle, data, idx, k, s)
+    data, idx, exp = cached("stretch", make)
+    assert list(exp[1]) == [s] + [0] * 60 + [s]
+    with which(kmc, lib):
+        got = gpu_seq(kmc, cuda, data, idx, k, s)
+    assert (got[1][1:61] == 0).all() and (got[0][1:61] == S.FILL).all()
+    assert_sketch(got, exp)
+
+
 def test_seq_long_record_over_three_ship_ranges(kmc, oracle, cuda):
     """The shipped walk gives a workgroup at most 1024 chunks = 16 384 bytes while the
     input has fewer than CUs x 16 KB, so a record of 3 x 16 384 + 100 bases spans at
@@ -317,6 +376,49 @@ def test_seq_caller_workspace(kmc, oracle, cuda, lib):
         with pytest.raises(kmc.KmcError) as ei:
             gpu_seq(kmc, cuda, a[0], a[1], 15, 16, workspace=ws[: exact - 1])
         assert ei.value.code == 1004
+
+
+def stale_case(oracle):
+    """4096 bytes twice: one record over every range, then 41 records that cross other cuts
+    (and a windowless one), alone and as 6 groups (one empty, one windowless)."""
+    k, s = 21, 16
+    def make():
+        rng = np.random.default_rng(18)
+        one = records_at(rng, [0], 4096)
+        starts = [0] + sorted(int(x) for x in rng.choice(np.arange(30, 4000), size=39, replace=False)) + [4086]
+        many = records_at(rng, starts, 4096)
+        assert one[0].size == many[0].size == 4096 and diag_range_bytes(4096) == 256
+        go = np.array([0, 0, 7, 8, 30, 40, 41], dtype=np.int64)
+        return (one, expected(oracle, *one, k, s), many, expected(oracle, *many, k, s), go,
+                GU.grouped_expected(oracle, *many, go, k, s))
+    return cached("stale", make)
+
+
+@pytest.mark.parametrize("lib", LIBS)
+def test_seq_stale_workspace_of_another_layout(kmc, oracle, cuda, lib):
+    """The first call leaves its partial sets and their sizes in every range's slots; the
+    second call, on the same workspace and the same number of bytes, reads none of them."""
+    import torch
+    k, s = 21, 16
+    one, exp_one, many, exp_many, go, exp_groups = stale_case(oracle)
+    assert exp_one[1][0] == s and exp_many[1][-1] == 0 and list(exp_groups[1]) == [0, s, s, s, s, 0]
+    dv = cuda.index or 0
+    n = many[1].size - 1
+    with which(kmc, lib):
+        need = max(kmc.sketch_from_sequences_workspace_size(x, 4096, s, dv) for x in (1, n))
+        ws = torch.full((need,), 0xFF, dtype=torch.uint8, device=cuda)
+        assert_sketch(gpu_seq(kmc, cuda, *one, k, s, workspace=ws), exp_one, "one record")
+        assert_sketch(gpu_seq(kmc, cuda, *many, k, s, workspace=ws), exp_many, "many records after one")
+        # the same pair with the grouped call second
+        need = max(need, kmc.sketch_from_sequences_grouped_workspace_size(n, go.size - 1, 4096, s, dv))
+        ws = torch.full((need,), 0xFF, dtype=torch.uint8, device=cuda)
+        assert_sketch(gpu_seq(kmc, cuda, *one, k, s, workspace=ws), exp_one, "one record again")
+        d = torch.from_numpy(many[0]).to(cuda)
+        di = torch.from_numpy(many[1]).to(cuda)
+        got = kmc.sketch_from_sequences_grouped(d, di, torch.from_numpy(go).to(cuda), k, s, workspace=ws)
+        torch.cuda.synchronize()
+        assert_sketch((got[0].cpu().numpy().view(np.uint64), got[1].cpu().numpy().view(np.uint32)), exp_groups,
+                      "groups after one record")
 
 
 @pytest.mark.parametrize("lib", LIBS)
