@@ -19,7 +19,9 @@
 // kmc_pair_distances_sparse) or on MinHash sketches of them (--sketch:
 // kmc_sketch_from_counts + kmc_sketch_distances -> sketch_results.csv; --sketch-direct:
 // kmc_sketch_from_sequences instead, no canonical count; --per-file: one sketch per input file,
-// kmc_sketch_from_sequences_grouped).  GPU only: there is no CPU counting path here.
+// kmc_sketch_from_sequences_grouped; --query FILE: the input files are references that FILE's
+// sketches are searched in, kmc_sketch_nearest -> query_results.tsv, or with --top 0
+// kmc_sketch_distances_rect -> query_distances.csv).  GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,6 +62,10 @@ struct Options {
     bool sketch_direct = false;  // --sketch-direct: kmc_sketch_from_sequences, no canonical count
     bool per_file = false;       // --per-file: one sketch per input file (kmc_sketch_from_sequences_grouped)
     bool max_seqs_set = false;
+    std::string query;    // --query FILE: search FILE's sketches in the input's
+    long top = 10;        // --top T: hits per query; 0: the whole rectangle
+    long min_shared = 1;  // --min-shared M
+    bool top_set = false, min_shared_set = false;
     std::vector<std::string> more_inputs;  // the input files after the first
 };
 
@@ -67,6 +73,7 @@ void usage(FILE *f) {
     fprintf(f,
             "usage: kmc [options] <input.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --per-file [options] <a.fasta> <b.fasta> ...\n"
+            "       kmc --canonical --sketch S --sketch-direct --query q.fasta [--top T] [options] <refs.fasta>\n"
             "       kmc synth OUT.fa RECORDS LENGTH [SEED]   (benchmark input, SURVEY.md 8(d))\n"
             "  -k K              k-mer length (default %d, the reference's K); dense path 1..%d,\n"
             "                    --canonical 1..%d\n"
@@ -105,12 +112,25 @@ void usage(FILE *f) {
             "                    (kmc_sketch_from_sequences_grouped); sketch_results.csv holds the distances\n"
             "                    between the files in command-line order, and one line per file gives its\n"
             "                    index, path, records and sketch size.  --max-seqs defaults to 0 here\n"
+            "  --query FILE      with --canonical --sketch S --sketch-direct: the input file(s) are the\n"
+            "                    references, sketched as without it (per record, or per file with\n"
+            "                    --per-file); FILE is sketched the same way (per record, or as one genome\n"
+            "                    with --per-file) and every query sketch is searched in the references\n"
+            "                    (kmc_sketch_nearest).  <out>/query_results.tsv gets one line per hit:\n"
+            "                    query<TAB>rank<TAB>ref<TAB>shared<TAB>denom<TAB>distance, rank from 1,\n"
+            "                    best first; sketch_results.csv is not written\n"
+            "  --top T           with --query: hits per query, 1..%d (default 10); 0: every query against\n"
+            "                    every reference instead (kmc_sketch_distances_rect), written row-major,\n"
+            "                    one distance per line, to <out>/query_distances.csv\n"
+            "  --min-shared M    with --query: only references that share at least M sketch values with\n"
+            "                    the query are hits (default 1; 0: unrelated references too, at distance 1)\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
             "  -q                quiet (no progress lines)\n",
             KMC_DROPIN_K, KMC_DENSE_MAX_K, KMC_CANON_MAX_K, KMC_MAX_SEQS_REFERENCE, KMC_MAX_SEQS_REFERENCE + 1,
-            KMC_DROPIN_K, KMC_CANON_MAX_K, (unsigned long long)KMC_SKETCH_DEFAULT_SEED, KMC_SKETCH_MAX_SIZE);
+            KMC_DROPIN_K, KMC_CANON_MAX_K, (unsigned long long)KMC_SKETCH_DEFAULT_SEED, KMC_SKETCH_MAX_SIZE,
+            KMC_NEAREST_MAX_TOP);
 }
 
 int parse(int argc, char **argv, Options &o) {
@@ -163,6 +183,14 @@ int parse(int argc, char **argv, Options &o) {
             o.min_count_set = true;
             if (o.min_count < 0 || o.min_count > (long)UINT32_MAX)
                 return fprintf(stderr, "kmc: --min-count out of range\n"), 2;
+        } else if (a == "--query") {
+            o.query = next("--query");
+        } else if (a == "--top") {
+            o.top = atol(next("--top"));
+            o.top_set = true;
+        } else if (a == "--min-shared") {
+            o.min_shared = atol(next("--min-shared"));
+            o.min_shared_set = true;
         } else if (a == "--softmask") {
             o.softmask = true;
         } else if (a == "--host-loader") {
@@ -204,6 +232,18 @@ int parse(int argc, char **argv, Options &o) {
         return usage(stderr), 2;
     }
     if (o.per_file && !o.max_seqs_set) o.max_seqs = 0;
+    if (!o.query.empty() && !(o.canonical && o.sketch > 0 && o.sketch_direct)) {
+        fprintf(stderr, "kmc: --query needs --canonical --sketch S --sketch-direct\n");
+        return usage(stderr), 2;
+    }
+    if ((o.top_set || o.min_shared_set) && o.query.empty()) {
+        fprintf(stderr, "kmc: --top and --min-shared select the hits of --query\n");
+        return usage(stderr), 2;
+    }
+    if (o.top < 0 || o.top > KMC_NEAREST_MAX_TOP || o.min_shared < 0 || o.min_shared > (long)UINT32_MAX) {
+        fprintf(stderr, "kmc: --top must be in 0..%d, --min-shared in 0..%u\n", KMC_NEAREST_MAX_TOP, UINT32_MAX);
+        return usage(stderr), 2;
+    }
     if (o.gpus < 1) return fprintf(stderr, "kmc: --gpus must be >= 1\n"), 2;
     if (o.gpus > 1 && (o.dropin || o.canonical))
         return fprintf(stderr, "kmc: --gpus > 1 is for the dense path\n"), 2;
@@ -400,39 +440,136 @@ int run_sketch_direct(const Options &o, const Records &r, hipStream_t st) {
     }, r.n, st);
 }
 
-// --per-file: every input file is one group of all its records; file f's call writes row f
+// --per-file: every file is one group of all its records; file f's call writes row f
 // (rows of separate calls concatenate), so one file at a time is resident
+int sketch_files(const Options &o, const std::vector<std::string> &files, const char *what, uint32_t s, uint64_t *d_sk,
+                 uint32_t *d_sz, hipStream_t st) {
+    const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
+    DevBuf<int64_t> d_grp;
+    HIPCHK(dev_alloc(d_grp, 2));
+    for (size_t f = 0; f < files.size(); ++f) {
+        Options of = o;
+        of.input = files[f];
+        of.quiet = true;  // (the loader's lines are the single-file run's)
+        Records r;
+        if (int e = load(of, st, r)) return e;
+        uint32_t size = 0;
+        if (r.n == 0) {  // no record: the empty sketch
+            HIPCHK(hipMemsetAsync(d_sk + f * s, 0xFF, (size_t)s * 8, st));
+            HIPCHK(hipMemsetAsync(d_sz + f, 0, 4, st));
+        } else {
+            const int64_t grp[2] = {0, (int64_t)r.n};
+            HIPCHK(hipMemcpyAsync(d_grp.get(), grp, sizeof grp, hipMemcpyHostToDevice, st));
+            KMCCHK(kmc_sketch_from_sequences_grouped(r.data.get(), r.idx.get(), r.n, r.bytes, d_grp.get(), 1, o.k,
+                                                     flags, s, KMC_SKETCH_DEFAULT_SEED, d_sk + f * s, d_sz + f,
+                                                     nullptr, 0, st));
+            HIPCHK(hipMemcpyAsync(&size, d_sz + f, 4, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));  // before the file's buffers go
+        if (!o.quiet)
+            printf("%s %zu: %s: %" PRIu64 " records, sketch size %u\n", what, f, files[f].c_str(), r.n, size);
+    }
+    return 0;
+}
+
 int run_per_file(const Options &o, hipStream_t st) {
     std::vector<std::string> files{o.input};
     files.insert(files.end(), o.more_inputs.begin(), o.more_inputs.end());
-    const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
-    return sketch_step(o, [&](uint32_t s, uint64_t *d_sk, uint32_t *d_sz) -> int {
-        DevBuf<int64_t> d_grp;
-        HIPCHK(dev_alloc(d_grp, 2));
-        for (size_t f = 0; f < files.size(); ++f) {
-            Options of = o;
-            of.input = files[f];
-            of.quiet = true;  // (the loader's lines are the single-file run's)
-            Records r;
-            if (int e = load(of, st, r)) return e;
-            uint32_t size = 0;
-            if (r.n == 0) {  // no record: the empty sketch
-                HIPCHK(hipMemsetAsync(d_sk + f * s, 0xFF, (size_t)s * 8, st));
-                HIPCHK(hipMemsetAsync(d_sz + f, 0, 4, st));
-            } else {
-                const int64_t grp[2] = {0, (int64_t)r.n};
-                HIPCHK(hipMemcpyAsync(d_grp.get(), grp, sizeof grp, hipMemcpyHostToDevice, st));
-                KMCCHK(kmc_sketch_from_sequences_grouped(r.data.get(), r.idx.get(), r.n, r.bytes, d_grp.get(), 1, o.k,
-                                                         flags, s, KMC_SKETCH_DEFAULT_SEED, d_sk + f * s, d_sz + f,
-                                                         nullptr, 0, st));
-                HIPCHK(hipMemcpyAsync(&size, d_sz + f, 4, hipMemcpyDeviceToHost, st));
-            }
-            HIPCHK(hipStreamSynchronize(st));  // before the file's buffers go
-            if (!o.quiet)
-                printf("File %zu: %s: %" PRIu64 " records, sketch size %u\n", f, files[f].c_str(), r.n, size);
-        }
-        return 0;
+    return sketch_step(o, [&](uint32_t s, uint64_t *d_sk, uint32_t *d_sz) {
+        return sketch_files(o, files, "File", s, d_sk, d_sz, st);
     }, files.size(), st);
+}
+
+// The sketch rows of a query or reference set: one per record of the one file, or
+// (--per-file) one per file.
+struct Rows {
+    DevBuf<uint64_t> sk;
+    DevBuf<uint32_t> sz;
+    uint64_t n = 0;
+};
+
+int make_rows(const Options &o, const std::vector<std::string> &files, const char *what, bool announce, hipStream_t st,
+              Rows &rows) {
+    const uint32_t s = (uint32_t)o.sketch;
+    if (o.per_file) {
+        rows.n = files.size();
+        HIPCHK(dev_alloc(rows.sk, rows.n * s));
+        HIPCHK(dev_alloc(rows.sz, rows.n));
+        return sketch_files(o, files, what, s, rows.sk.get(), rows.sz.get(), st);
+    }
+    Options of = o;
+    of.input = files[0];
+    of.quiet = o.quiet || !announce;
+    Records r;
+    if (int e = load(of, st, r)) return e;
+    rows.n = r.n;
+    HIPCHK(dev_alloc(rows.sk, rows.n * s));
+    HIPCHK(dev_alloc(rows.sz, rows.n));
+    KMCCHK(kmc_sketch_from_sequences(r.data.get(), r.idx.get(), r.n, r.bytes, o.k, o.softmask ? KMC_CANON_SOFTMASK : 0u,
+                                     s, KMC_SKETCH_DEFAULT_SEED, rows.sk.get(), rows.sz.get(), nullptr, 0, st));
+    HIPCHK(hipStreamSynchronize(st));  // before the records go
+    if (!o.quiet && !announce) printf("%s: %s: %" PRIu64 " records\n", what, files[0].c_str(), r.n);
+    return 0;
+}
+
+// --query FILE: the inputs are the references; FILE's sketches are searched in them
+int run_query(const Options &o, hipStream_t st) {
+    std::vector<std::string> files{o.input};
+    files.insert(files.end(), o.more_inputs.begin(), o.more_inputs.end());
+    const uint32_t s = (uint32_t)o.sketch, top = (uint32_t)o.top;
+    Rows R, Q;
+    if (int e = make_rows(o, files, "Reference", true, st, R)) return e;
+    if (int e = make_rows(o, {o.query}, "Query", false, st, Q)) return e;
+    const uint64_t m = Q.n, n = R.n;
+    Event t0 = make_event(), t1 = make_event();
+    if (top == 0) {  // the whole rectangle
+        DevBuf<float> d_out;
+        HIPCHK(dev_alloc(d_out, m * n));
+        HIPCHK(hipEventRecord(t0.get(), st));
+        KMCCHK(kmc_sketch_distances_rect(Q.sk.get(), Q.sz.get(), m, R.sk.get(), R.sz.get(), n, s, o.k, d_out.get(),
+                                         nullptr, nullptr, st));
+        HIPCHK(hipEventRecord(t1.get(), st));
+        HIPCHK(hipEventSynchronize(t1.get()));
+        if (!o.quiet)
+            printf("Query distances (%" PRIu64 " x %" PRIu64 "): %.3f ms\n", m, n, ms_between(t0.get(), t1.get()));
+        std::vector<float> dist(m * n);
+        if (m * n > 0) HIPCHK(hipMemcpy(dist.data(), d_out.get(), m * n * sizeof(float), hipMemcpyDeviceToHost));
+        return write_csv(o.out_dir + "/query_distances.csv", dist) ? 1 : 0;
+    }
+    DevBuf<uint32_t> d_ref, d_sh, d_dn, d_cnt;
+    DevBuf<float> d_dist;
+    HIPCHK(dev_alloc(d_ref, m * top));
+    HIPCHK(dev_alloc(d_sh, m * top));
+    HIPCHK(dev_alloc(d_dn, m * top));
+    HIPCHK(dev_alloc(d_dist, m * top));
+    HIPCHK(dev_alloc(d_cnt, m));
+    HIPCHK(hipEventRecord(t0.get(), st));
+    KMCCHK(kmc_sketch_nearest(Q.sk.get(), Q.sz.get(), m, R.sk.get(), R.sz.get(), n, s, o.k, top,
+                              (uint32_t)o.min_shared, d_ref.get(), d_sh.get(), d_dn.get(), d_dist.get(), d_cnt.get(),
+                              nullptr, 0, st));
+    HIPCHK(hipEventRecord(t1.get(), st));
+    HIPCHK(hipEventSynchronize(t1.get()));
+    if (!o.quiet)
+        printf("Query search (%" PRIu64 " in %" PRIu64 ", top %u): %.3f ms\n", m, n, top,
+               ms_between(t0.get(), t1.get()));
+    std::vector<uint32_t> ref(m * top), sh(m * top), dn(m * top), cnt(m);
+    std::vector<float> dist(m * top);
+    if (m > 0) {
+        HIPCHK(hipMemcpy(ref.data(), d_ref.get(), ref.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(sh.data(), d_sh.get(), sh.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dn.data(), d_dn.get(), dn.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dist.data(), d_dist.get(), dist.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cnt.data(), d_cnt.get(), cnt.size() * 4, hipMemcpyDeviceToHost));
+    }
+    const std::string path = o.out_dir + "/query_results.tsv";
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return fprintf(stderr, "kmc: cannot write %s\n", path.c_str()), 1;
+    for (uint64_t q = 0; q < m; ++q)
+        for (uint32_t i = 0; i < cnt[q] && i < top; ++i) {
+            const uint64_t at = q * top + i;
+            fprintf(f, "%" PRIu64 "\t%u\t%u\t%u\t%u\t%f\n", q, i + 1, ref[at], sh[at], dn[at], dist[at]);
+        }
+    return fclose(f) == 0 ? 0 : 1;
 }
 
 // --canonical: the sparse counts, then their dump, step 2 on them and their sketches
@@ -584,6 +721,7 @@ int run(const Options &o) {
     hipStream_t s = nullptr;
     HIPCHK(hipStreamCreate(&s));
     const Stream st(s);
+    if (!o.query.empty()) return run_query(o, s);
     if (o.per_file) return run_per_file(o, s);
     Records r;  // (after the stream: released before it)
     if (int e = load(o, s, r)) return e;

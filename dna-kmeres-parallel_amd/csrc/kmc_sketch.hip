@@ -55,8 +55,8 @@
 //   kWalkBlock   threads of a walking workgroup           1024 / 64
 //   kChunk       entries per chunk (kWalkBlock * kItems)  4096 / 64
 //   kWalkPer     entries per walking workgroup, at least  16384 / 256
-//   kDistElems   LDS capacity of a distance tile, values  16384 / 512
-//   kTileMax     tile edge at most, rows                  32 / 4
+//   kDistElems   LDS capacity of a distance tile, values  16384 / 512   (kmc_sketch_pair.h)
+//   kTileMax     tile edge at most, rows                  32 / 4        (kmc_sketch_pair.h)
 // LDS, shipped: walk 1 KB; sort 8 / 32 / 128 KB for s <= 1024 / 4096 / 16384;
 // distance tile 128 KB (one workgroup of 1024 threads per CU of 160 KB).
 // Workspace: 2 KB of bins + 16 B per record.
@@ -67,6 +67,7 @@
 #include "kmc.h"
 #include "kmc_dist_common.h"
 #include "kmc_internal.h"
+#include "kmc_sketch_pair.h"
 #include "kmc_walk.h"
 #include "kmc_workspace.h"
 
@@ -77,22 +78,15 @@ namespace {
 constexpr int kWalkBlock = 64;
 constexpr int kItems = 1;
 constexpr int64_t kWalkPer = 256;
-constexpr int kDistElems = 512;
-constexpr int kTileMax = 4;
 #else
 constexpr int kWalkBlock = 1024;
 constexpr int kItems = 4;
 constexpr int64_t kWalkPer = 16384;
-constexpr int kDistElems = 16384;
-constexpr int kTileMax = 32;
 #endif
 constexpr int64_t kChunk = (int64_t)kWalkBlock * kItems;
 constexpr int kDigitBits = 8;
 constexpr int kDigits = 1 << kDigitBits;
 constexpr int kLevels = 64 / kDigitBits;
-constexpr int kDistBlock = 1024;
-constexpr int kStageMinTile = 4;  // a smaller staged tile leaves most of the 16 wavefronts idle
-constexpr int kGlobalTile = 8;
 constexpr uint64_t kFill = ~0ull;
 constexpr uint64_t kMaxEntries = 1ull << 40;
 
@@ -280,53 +274,7 @@ struct DParams {
     uint32_t *shared, *denom;
 };
 
-__device__ __forceinline__ float mash_distance(uint32_t shared, uint32_t denom, int k) {
-    if (denom == 0) return __uint_as_float(0x7fc00000u);
-    if (shared == 0) return 1.0f;
-    if (shared == denom) return 0.0f;
-    const double j = (double)shared / (double)denom;
-    double d = -log(2.0 * j / (1.0 + j)) / (double)k;
-    if (d > 1.0) d = 1.0;
-    return (float)d;
-}
-
-// One wavefront, one pair: A = row i (na values), B = row j (nb values), ascending.
-template <class PA, class PB>
-__device__ __forceinline__ void pair_counts(PA A, int na, PB B, int nb, int s, int lane, uint32_t *shared_out,
-                                            uint32_t *denom_out) {
-    const bool known = na == s || nb == s;  // the union holds at least s values
-    int M = 0, sh = 0;
-    for (int x0 = 0; x0 < na; x0 += 64) {
-        const int x = x0 + lane;
-        const bool act = x < na;
-        int pos = 0;
-        bool match = false;
-        if (act) {
-            const uint64_t v = A[x];
-            int lo = 0, hi = nb;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (B[mid] < v)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-            pos = lo;
-            match = pos < nb && B[pos] == v;
-        }
-        const unsigned long long mm = __ballot(match);
-        const int before = __popcll(mm & (~0ull >> (63 - lane)));  // matches among A[0..x]
-        const int rank = x + 1 + pos + (match ? 1 : 0) - (M + before);
-        const bool in_u = act && rank <= s;
-        sh += __popcll(__ballot(match && in_u));
-        M += __popcll(mm);
-        if (known && __ballot(act && !in_u)) break;  // ranks only grow
-    }
-    const int uni = na + nb - M;  // |A u B| when the loop ran to its end
-    *shared_out = (uint32_t)sh;
-    *denom_out = (uint32_t)(known ? s : (uni < s ? uni : s));
-}
-
+// pair_counts and mash_distance: kmc_sketch_pair.h, shared with kmc_sketch_query.hip
 template <bool STAGE>
 __global__ __launch_bounds__(kDistBlock) void sketch_dist_kernel(DParams p) {
     __shared__ uint64_t buf[STAGE ? kDistElems : 1];  // rows of A: [a * s], rows of B: [(T + b) * s]
@@ -493,10 +441,8 @@ extern "C" int kmc_sketch_distances(const uint64_t *sketches, const uint32_t *sk
     p.out = out;
     p.shared = shared;
     p.denom = denom;
-    int T = kDistElems / (int)sketch_size / 2;
-    if (T > kTileMax) T = kTileMax;
-    const bool stage = T >= kStageMinTile;
-    if (!stage) T = kGlobalTile < kTileMax ? kGlobalTile : kTileMax;
+    bool stage = false;
+    int T = tile_edge(kDistElems, sketch_size, &stage);
     if ((int64_t)T > p.n) T = (int)p.n;
     p.T = T;
     p.nt = (p.n + T - 1) / T;

@@ -193,6 +193,11 @@ def _load(path):
     L.kmc_sketch_from_sequences_grouped.argtypes = [_P, _P, _U64, _U64, _P, _U64, ctypes.c_int, ctypes.c_uint,
                                                     ctypes.c_uint32, _U64, _P, _P, _P, ctypes.c_size_t, _P]
     L.kmc_sketch_merge_groups.argtypes = [_P, _P, _U64, _P, _U64, ctypes.c_uint32, _P, _P, _P]
+    L.kmc_sketch_distances_rect.argtypes = [_P, _P, _U64, _P, _P, _U64, ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P]
+    L.kmc_sketch_nearest_workspace_size.restype = ctypes.c_size_t
+    L.kmc_sketch_nearest_workspace_size.argtypes = [_U64, _U64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
+    L.kmc_sketch_nearest.argtypes = [_P, _P, _U64, _P, _P, _U64, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
+                                     ctypes.c_uint32, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
     L.minKmeres2_hip.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.kmc_count_canonical_hash.argtypes = [_P, _P, _U64, ctypes.c_int, ctypes.c_uint, _P, _P, _U64, _P,
                                            ctypes.POINTER(_U64), _P]
@@ -502,6 +507,59 @@ def sketch_distances(sketches, sizes, k, with_counts=False, stream=None):
                                     _stream(stream))
     _check(rc, "kmc_sketch_distances")
     return (out, sh, dn) if with_counts else out
+
+
+NEAREST_MAX_TOP = 1024
+
+
+def _row_sets(q, r):
+    """Contiguous query and reference rows of one sketch size: (q, r, m, n, s)."""
+    q, r = q.contiguous(), r.contiguous()
+    if int(q.shape[1]) != int(r.shape[1]):
+        raise ValueError("query rows of %d values against reference rows of %d" % (q.shape[1], r.shape[1]))
+    return q, r, int(q.shape[0]), int(r.shape[0]), int(q.shape[1])
+
+
+def sketch_distances_rect(q, qs, r, rs, k, with_counts=False, stream=None):
+    """Mash distance of every query row against every reference row
+    (kmc_sketch_distances_rect): rows q [m, s] with sizes qs [m], rows r [n, s] with
+    sizes rs [n].  Returns float32 [m, n]; with_counts: (out, shared, denom), the
+    two integer counts as int32 tensors [m, n]."""
+    import torch
+    q, r, m, n, s = _row_sets(q, r)
+    out = torch.empty((m, n), dtype=torch.float32, device=q.device)
+    sh = torch.empty((m, n), dtype=torch.int32, device=q.device) if with_counts else None
+    dn = torch.empty((m, n), dtype=torch.int32, device=q.device) if with_counts else None
+    rc = lib().kmc_sketch_distances_rect(_dptr(q), _dptr(qs), m, _dptr(r), _dptr(rs), n, s, k, _dptr(out), _dptr(sh),
+                                         _dptr(dn), _stream(stream))
+    _check(rc, "kmc_sketch_distances_rect")
+    return (out, sh, dn) if with_counts else out
+
+
+def sketch_nearest_workspace_size(num_queries, num_refs, sketch_size, top, device=0):
+    return int(lib().kmc_sketch_nearest_workspace_size(num_queries, num_refs, sketch_size, top, device))
+
+
+def sketch_nearest(q, qs, r, rs, k, top, min_shared=1, workspace=None, stream=None):
+    """The `top` nearest reference rows of every query row (kmc_sketch_nearest), by
+    Jaccard estimate shared / denom descending, then by reference index; a
+    reference takes part with denom > 0 and shared >= min_shared.  Returns (refs,
+    shared, denom int32 [m, top], dist float32 [m, top], counts int32 [m]): row q
+    holds counts[q] hits, then -1 (UINT32_MAX), 0, 0 and NaN."""
+    import torch
+    q, r, m, n, s = _row_sets(q, r)
+    top = int(top)
+    shape = (m, max(top, 0))
+    refs = torch.empty(shape, dtype=torch.int32, device=q.device)
+    sh = torch.empty(shape, dtype=torch.int32, device=q.device)
+    dn = torch.empty(shape, dtype=torch.int32, device=q.device)
+    dist = torch.empty(shape, dtype=torch.float32, device=q.device)
+    counts = torch.empty(m, dtype=torch.int32, device=q.device)
+    rc = lib().kmc_sketch_nearest(_dptr(q), _dptr(qs), m, _dptr(r), _dptr(rs), n, s, k, top, int(min_shared),
+                                  _dptr(refs), _dptr(sh), _dptr(dn), _dptr(dist), _dptr(counts), *_ws(workspace),
+                                  _stream(stream))
+    _check(rc, "kmc_sketch_nearest")
+    return refs, sh, dn, dist, counts
 
 
 def min_kmeres2(sums, mins, num_seqs, current_seq, indexes, stream=None):

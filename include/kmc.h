@@ -326,6 +326,10 @@ KMC_API int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *coun
  * every k-mer costs too much.  A record is reduced to its sketch_size smallest
  * distinct key hashes; distances come from those sorted lists alone, and sketches
  * made in separate calls (with one seed and sketch_size) may be concatenated.
+ * The rows have two consumers: kmc_sketch_distances, all pairs of one row set, and
+ * the search of one row set (the queries) in another (the references):
+ * kmc_sketch_distances_rect, every query against every reference, and
+ * kmc_sketch_nearest, the best references of every query without that rectangle.
  *
  * kmc_sketch_from_counts: sketches of the per-record lists of
  * kmc_count_canonical_hash[_ex], with the list conventions of
@@ -444,8 +448,64 @@ KMC_API int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *coun
  * sketches_out and sketches_in, or of sizes_out and sizes_in, share a byte; also for
  * a sketch_size outside 1..KMC_SKETCH_MAX_SIZE, num_rows or num_groups above 2^40,
  * null group_offsets, sketches_out or sizes_out, null inputs with num_rows > 0.
- * num_groups == 0: KMC_OK. */
+ * num_groups == 0: KMC_OK.
+ *
+ * kmc_sketch_distances_rect: every query row against every reference row, by
+ * kmc_sketch_distances' pair rule exactly (the same device function): shared, denom
+ * and the float of query q and reference r go to out[q * num_refs + r], row-major,
+ * and to shared[] and denom[] (device uint32, same indexing) when non-NULL.  Both row
+ * sets share sketch_size; the pair is symmetric, and with both sets pointing at the
+ * same rows out[i * n + j] is the triangle's entry (i, j) bit for bit, the diagonal
+ * +0.0f for a non-empty row and NaN for an empty one.  No workspace; asynchronous
+ * on `stream`; the work launched depends on the host arguments only.  k in
+ * 1..KMC_CANON_MAX_K (KMC_ERR_UNSUPPORTED_K); num_queries == 0 or num_refs == 0:
+ * KMC_OK, nothing written; otherwise KMC_ERR_INVALID_ARG for null rows, sizes or
+ * out, a sketch_size outside 1..KMC_SKETCH_MAX_SIZE, or either count above
+ * KMC_SPARSE_MAX_SEQS.
+ *
+ * kmc_sketch_nearest: for every query the `top` best references, without the
+ * num_queries x num_refs matrix.
+ *   participation reference r takes part for query q iff denom(q, r) > 0 and
+ *                 shared(q, r) >= min_shared.  With min_shared = 0 unrelated
+ *                 references (distance 1.0) take part, an empty reference among
+ *                 them when the query is not empty (shared 0 of denom = the
+ *                 query's size); a pair of two empty rows (NaN) never does.
+ *   order         by the Jaccard estimate J = shared / denom, descending, the fractions
+ *                 compared exactly (shared_a * denom_b against shared_b * denom_a);
+ *                 equal J by ascending reference index.  The order is defined on the
+ *                 integers, not on the float: it depends neither on the device's log
+ *                 nor on the cap at 1.0.
+ *   hit_counts    device uint32[num_queries]: min(top, participating references)
+ *   hit_refs, hit_shared, hit_denom (device uint32), hit_dist (device float), each
+ *                 [num_queries * top]: entry [q * top + i] is the i-th best of query q
+ *                 for i < hit_counts[q]; the rest of each row holds UINT32_MAX, 0, 0
+ *                 and NaN.  hit_shared, hit_denom and hit_dist may each be NULL;
+ *                 hit_refs and hit_counts may not.  hit_dist is
+ *                 kmc_sketch_distances_rect's float of that pair, bit for bit.
+ *   limits        top in 1..KMC_NEAREST_MAX_TOP; num_refs <= 2^32 - 2 (the index is
+ *                 32 bits and UINT32_MAX marks an empty slot); num_queries <=
+ *                 KMC_SPARSE_MAX_SEQS
+ *   workspace     device scratch of kmc_sketch_nearest_workspace_size() bytes, or NULL
+ *                 for a library-owned buffer under kmc_pair_distances' rule
+ *                 (NULL-workspace calls on a device must not overlap);
+ *                 KMC_ERR_WORKSPACE when smaller.  The references are cut into S
+ *                 slabs, each searched on its own and the survivors merged:
+ *                     num_queries * S * top * 8  +  num_queries * S * 4  bytes
+ *                 (each array rounded up to 256), S <= max(1, 2 CUs / T) with T the
+ *                 number of query tiles (at most 32 queries each, fewer for a large
+ *                 sketch_size or top) and never more than the reference chunks.  It
+ *                 does not grow with num_refs beyond that.
+ * Asynchronous on `stream`, no host read-back; the work launched depends on the
+ * host arguments only; nothing a former call left in the workspace is read.
+ * num_queries == 0: KMC_OK.  num_refs == 0: KMC_OK, every hit_counts[q] = 0 and the
+ * rows filled as above (the sketch pointers may then be NULL).  k outside
+ * 1..KMC_CANON_MAX_K: KMC_ERR_UNSUPPORTED_K.  KMC_ERR_INVALID_ARG for the limits, a
+ * sketch_size outside 1..KMC_SKETCH_MAX_SIZE and, with num_queries > 0, null
+ * hit_refs or hit_counts, or null rows or sizes with num_refs > 0.  The size query
+ * returns 0 on bad arguments (and needs no device for those), and 0 when either
+ * count is 0: no workspace is used then. */
 #define KMC_SKETCH_MAX_SIZE 16384
+#define KMC_NEAREST_MAX_TOP 1024
 #define KMC_SKETCH_DEFAULT_SEED 42ull
 KMC_API size_t kmc_sketch_workspace_size(uint64_t num_seqs, uint64_t num_entries, uint32_t sketch_size, int device);
 KMC_API int kmc_sketch_from_counts(const uint64_t *keys, const uint32_t *counts, const uint64_t *rec_offsets,
@@ -472,6 +532,17 @@ KMC_API int kmc_sketch_from_sequences_grouped(const char *data, const int64_t *i
 KMC_API int kmc_sketch_merge_groups(const uint64_t *sketches_in, const uint32_t *sizes_in, uint64_t num_rows,
                                     const int64_t *group_offsets, uint64_t num_groups, uint32_t sketch_size,
                                     uint64_t *sketches_out, uint32_t *sizes_out, hipStream_t stream);
+KMC_API int kmc_sketch_distances_rect(const uint64_t *q_sketches, const uint32_t *q_sizes, uint64_t num_queries,
+                                      const uint64_t *r_sketches, const uint32_t *r_sizes, uint64_t num_refs,
+                                      uint32_t sketch_size, int k, float *out, uint32_t *shared, uint32_t *denom,
+                                      hipStream_t stream);
+KMC_API size_t kmc_sketch_nearest_workspace_size(uint64_t num_queries, uint64_t num_refs, uint32_t sketch_size,
+                                                 uint32_t top, int device);
+KMC_API int kmc_sketch_nearest(const uint64_t *q_sketches, const uint32_t *q_sizes, uint64_t num_queries,
+                               const uint64_t *r_sketches, const uint32_t *r_sizes, uint64_t num_refs,
+                               uint32_t sketch_size, int k, uint32_t top, uint32_t min_shared,
+                               uint32_t *hit_refs, uint32_t *hit_shared, uint32_t *hit_denom, float *hit_dist,
+                               uint32_t *hit_counts, void *workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Tracing (the reference times step 1 with cudaEvents, main.cu:262-300): when set,

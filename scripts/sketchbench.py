@@ -8,6 +8,9 @@ two-step path kmc_count_canonical_hash + kmc_sketch_from_counts on the same inpu
 (profiles/pr_sketch_direct.jsonl).  With --grouped: kmc_sketch_from_sequences_grouped
 beside the ungrouped call, the ungrouped call + kmc_sketch_merge_groups and the
 distances on group rows and on record rows (profiles/pr_sketch_grouped.jsonl).
+With --query: kmc_sketch_nearest and kmc_sketch_distances_rect (alone and followed by
+torch.topk) beside kmc_sketch_distances over the concatenation of queries and
+references, on synthetic rows (profiles/pr_sketch_query.jsonl).
 
 Inputs (synthetic, generated on the device):
   iid          8 x 50 Mbase independent records, k = 31
@@ -192,6 +195,70 @@ def grouped_main(args, dev):
             torch.cuda.empty_cache()
 
 
+def synthetic_rows(n, s, dev, seed):
+    """n full rows of s ascending values: a third of each row comes from a shared pool of
+    4 s values (so pairs share a few values and the hits differ), the rest is its own."""
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    own = torch.randint(0, 1 << 62, (n, s), dtype=torch.int64, device=dev, generator=g)
+    pool = torch.randint(0, 1 << 62, (4 * s,), dtype=torch.int64, device=dev, generator=g)
+    pick = torch.randint(0, 4 * s, (n, s // 3), device=dev, generator=g)
+    own[:, :s // 3] = pool[pick]
+    rows = torch.sort(own, dim=1).values
+    # distinct within a row: a repeated value moves up by its position (random 62-bit values: rare)
+    dup = torch.zeros_like(rows, dtype=torch.bool)
+    dup[:, 1:] = rows[:, 1:] == rows[:, :-1]
+    rows = torch.sort(rows + dup * torch.arange(1, s + 1, device=dev), dim=1).values
+    return rows.contiguous(), torch.full((n,), s, dtype=torch.int32, device=dev)
+
+
+def query_main(args, dev):
+    """--query: m queries in n references.  kmc_sketch_nearest, kmc_sketch_distances_rect,
+    the rectangle followed by torch.topk, and the parent commit's only route:
+    kmc_sketch_distances over the m + n rows.  The hits are asserted equal to the
+    rectangle's best before anything is timed."""
+    m, k, top = 64, 21, 10
+    shapes = [(4096, 1000), (65536, 1000), (4096, 10000)]
+    with open(args.out, "w") as out:
+        for n, s in shapes:
+            n = max(int(n * args.scale), top + 1)
+            q, qs = synthetic_rows(m, s, dev, 1)
+            r, rs = synthetic_rows(n, s, dev, 2)
+            r[:m:2] = q[:m:2]  # half of the queries are in the collection
+            both, both_s = torch.cat([q, r]), torch.cat([qs, rs])
+            refs, sh, dn, dist, counts = kmc.sketch_nearest(q, qs, r, rs, k, top)
+            rect, rsh, rdn = kmc.sketch_distances_rect(q, qs, r, rs, k, with_counts=True)
+            torch.cuda.synchronize()
+            assert int(counts.min()) == top
+            rows = torch.arange(m, device=dev)[:, None]
+            assert torch.equal(rsh[rows, refs.long()], sh) and torch.equal(rdn[rows, refs.long()], dn)
+            assert torch.equal(rect[rows, refs.long()], dist)
+            # the i-th hit's J is the i-th largest of the row (exact in double: both numbers <= 16384)
+            j_all = (rsh.double() / rdn.double()) * (rsh >= 1)
+            assert torch.equal(torch.topk(j_all, top, dim=1).values, sh.double() / dn.double())
+            pairs_all = (m + n) * (m + n - 1) // 2
+            rec = {
+                "queries": m, "refs": n, "sketch_size": s, "k": k, "top": top,
+                "pairs_rect": m * n, "pairs_all_pairs": pairs_all, "hits_equal_rect": True,
+                "workspace_bytes_nearest": kmc.sketch_nearest_workspace_size(m, n, s, top),
+                "rect_bytes": 4 * m * n, "all_pairs_bytes": 4 * pairs_all,
+                "kmc_sketch_nearest": timed(lambda: kmc.sketch_nearest(q, qs, r, rs, k, top), args.runs),
+                "kmc_sketch_distances_rect": timed(lambda: kmc.sketch_distances_rect(q, qs, r, rs, k), args.runs),
+                "rect_then_topk": timed(
+                    lambda: torch.topk(kmc.sketch_distances_rect(q, qs, r, rs, k), top, dim=1, largest=False),
+                    args.runs),
+            }
+            if 4 * pairs_all <= 16 << 30:  # the parent commit's route, where its triangle fits
+                # s = 10000 runs from global memory: fewer runs
+                rec["kmc_sketch_distances_all_pairs"] = timed(lambda: kmc.sketch_distances(both, both_s, k),
+                                                              3 if s > 2048 else args.runs, warmup=1)
+            out.write(json.dumps(rec) + "\n")
+            out.flush()
+            print(json.dumps(rec), flush=True)
+            del q, r, both, rect, rsh, rdn, j_all
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(HERE), "profiles", "pr_sketch.jsonl"))
@@ -207,8 +274,15 @@ def main():
                          "kmc_sketch_merge_groups) on identity, draft_assembly and read_set (--inputs picks among "
                          "them; rows asserted equal; 2 warm-ups, median of 5); appends to "
                          "--out profiles/pr_sketch_grouped.jsonl")
+    ap.add_argument("--query", action="store_true",
+                    help="time kmc_sketch_nearest and kmc_sketch_distances_rect beside kmc_sketch_distances over "
+                         "queries and references together: 64 queries in 4096 and 65536 references of s = 1000 and "
+                         "in 4096 of s = 10000, synthetic rows (hits asserted equal to the rectangle's; 2 warm-ups, "
+                         "median of --runs); --out profiles/pr_sketch_query.jsonl")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.query:
+        return query_main(args, dev)
     if args.grouped:
         return grouped_main(args, dev)
     shapes = {"iid": (8, 50_000_000, 31), "copies_1pct": (8, 50_000_000, 31), "many": (4096, 100_000, 21)}
