@@ -206,11 +206,8 @@ extern "C" int kmc_pair_distances(const int32_t *sum, uint64_t sum_ld, const int
     if (!sum || !indices || !out) return KMC_ERR_INVALID_ARG;
     if (sum_ld != 0 && sum_ld < num_seqs) return KMC_ERR_INVALID_ARG;
     if (num_seqs > (1ull << 31)) return KMC_ERR_INVALID_ARG;
-    int device = 0;
-    hipError_t he = hipGetDevice(&device);
-    if (he != hipSuccess) return (int)he;
-    int cus = 0;
-    int e = device_cus(device, &cus);
+    int device = 0, cus = 0;
+    int e = current_device_cus(&device, &cus);
     if (e) return e;
     const int64_t n = (int64_t)num_seqs;
     const Plan P = plan_for(n, k, cus);
@@ -229,7 +226,7 @@ extern "C" int kmc_pair_distances(const int32_t *sum, uint64_t sum_ld, const int
     p.out = out;
     p.acc = P.ws ? static_cast<unsigned long long *>(ws) : nullptr;
     if (p.acc) {
-        he = hipMemsetAsync(p.acc, 0, P.ws, stream);
+        const hipError_t he = hipMemsetAsync(p.acc, 0, P.ws, stream);
         if (he != hipSuccess) return (int)he;
     }
     const dim3 grid((unsigned)P.tiles, (unsigned)P.tiles, (unsigned)P.splits);

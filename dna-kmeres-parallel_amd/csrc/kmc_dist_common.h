@@ -25,6 +25,23 @@ __device__ __forceinline__ float distance_of(uint64_t s, int64_t li, int64_t lj,
     return 1.0f - (float)s / (float)(m - k + 1);
 }
 
+// Inverts q = tri_index(i, j, n).  Row i of the strict upper triangle of n starts at
+// tri_row_start(i, n) = tri_index(i, i + 1, n); tri_row is the row i <= n - 2 with
+// tri_row_start(i) <= q < tri_row_start(i + 1), found by search from a float guess.
+__device__ __forceinline__ int64_t tri_row_start(int64_t i, int64_t n) {
+    return i * (2 * n - i - 1) / 2;  // n i - i (i + 1) / 2, one product (even: i or 2n - 1 - i is)
+}
+
+__device__ __forceinline__ int64_t tri_row(int64_t q, int64_t n) {
+    const double nn = (double)n;
+    int64_t i = (int64_t)((2 * nn - 1 - sqrt((2 * nn - 1) * (2 * nn - 1) - 8.0 * (double)q)) / 2);
+    if (i < 0) i = 0;
+    if (i > n - 2) i = n - 2;
+    while (i > 0 && tri_row_start(i, n) > q) --i;
+    while (i + 2 < n && tri_row_start(i + 1, n) <= q) ++i;
+    return i;
+}
+
 __device__ __forceinline__ int64_t rec_len(const int64_t *idx, int64_t s) { return idx[s + 1] - idx[s] - 1; }
 
 // acc[pair] -> out[pair] over the n(n-1)/2 pairs of the packed triangle
@@ -32,13 +49,7 @@ __global__ __launch_bounds__(256) void pair_finish_kernel(const unsigned long lo
                                                           int64_t n, int k, float *out) {
     const int64_t npairs = n * (n - 1) / 2;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < npairs; q += (int64_t)gridDim.x * 256) {
-        // invert q = tri_index(i, j): row i starts at n*i - i*(i+1)/2 (found by search from a float guess)
-        const double nn = (double)n;
-        int64_t i = (int64_t)((2 * nn - 1 - sqrt((2 * nn - 1) * (2 * nn - 1) - 8.0 * (double)q)) / 2);
-        if (i < 0) i = 0;
-        while (i > 0 && n * i - i * (i + 1) / 2 > q) --i;
-        while (n * (i + 1) - (i + 1) * (i + 2) / 2 <= q) ++i;
-        const int64_t j = q - (n * i - i * (i + 1) / 2) + i + 1;
+        const int64_t i = tri_row(q, n), j = q - tri_row_start(i, n) + i + 1;
         out[q] = distance_of(acc[q], rec_len(indices, i), rec_len(indices, j), k);
     }
 }

@@ -330,11 +330,8 @@ extern "C" int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *c
     if (!rec_offsets || !indices || !out) return KMC_ERR_INVALID_ARG;
     if (num_entries > 0 && (!keys || !counts)) return KMC_ERR_INVALID_ARG;
     if (num_seqs > kMaxSeqs || num_entries > kMaxEntries) return KMC_ERR_INVALID_ARG;
-    int device = 0;
-    hipError_t he = hipGetDevice(&device);
-    if (he != hipSuccess) return (int)he;
-    int cus = 0;
-    int e = device_cus(device, &cus);
+    int device = 0, cus = 0;
+    int e = current_device_cus(&device, &cus);
     if (e) return e;
     const int64_t n = (int64_t)num_seqs, E = (int64_t)num_entries;
     const SPlan P = plan_for(E, cus);
@@ -357,7 +354,7 @@ extern "C" int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *c
     p.ent = L.ent;
     p.acc = L.acc;
     // acc is the only array accumulated into; cnt, off and ent are written whole before they are read
-    he = hipMemsetAsync(L.acc, 0, L.acc_bytes, stream);
+    const hipError_t he = hipMemsetAsync(L.acc, 0, L.acc_bytes, stream);
     if (he != hipSuccess) return (int)he;
     if (E > 0) {
         hipLaunchKernelGGL(sparse_count_kernel, dim3((unsigned)P.G), dim3(kWalkBlock), 0, stream, p);

@@ -2059,8 +2059,7 @@ extern "C" int kmc_count_canonical_hash_ex(const char *data, const int64_t *indi
     std::vector<int64_t> hidx;
     if (int e = fetch_offsets(indices, n, (int64_t)mis, stream, hidx)) return e;
     int device = 0, cus = 0;
-    if (hipError_t he = hipGetDevice(&device)) return (int)he;
-    if (int e = device_cus(device, &cus)) return e;
+    if (int e = current_device_cus(&device, &cus)) return e;
     CanonPlan P;
     canon_plan(hidx.data(), n, k, cus, P);
     HParams p{};

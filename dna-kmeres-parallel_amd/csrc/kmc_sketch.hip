@@ -30,15 +30,19 @@
 //   collect  the walk once more appends every participating h <= T_r to the row
 //            through a per-record cursor (a global atomic per kept entry; the write
 //            is skipped at or past sketch_sizes[r], which only a repeated key reaches)
-//   sort     one workgroup per record: bitonic sort of the row in LDS, padded to a
-//            power of two with UINT64_MAX, then the row with its tail fill
+//   sort     one workgroup per record: bitonic sort of the row in LDS (bitonic_sort of
+//            kmc_sketch_pair.h), padded to a power of two with UINT64_MAX, then the
+//            row with its tail fill
 // Per entry and level 8 B are re-read (12 B with min_count > 1), 9 times in all.
 // Digit width: 8 bits is the only width run so far (profiles/pr_sketch.jsonl); a wider
 // digit needs fewer passes and a larger table (kDigitBits = 11: 6 levels, 16 KB per record).
 //
 // kmc_sketch_distances: the packed triangle is cut into T x T tiles of row
 // pairs; a workgroup stages the 2T rows of a tile in LDS and its 16 wavefronts
-// take the tile's pairs.  For a pair (A, B) the lanes take 64 consecutive
+// take the tile's pairs.  The kernel, its tile loop and the pair's counts are
+// kmc_sketch_pair.h's, shared with the rectangle and the search of
+// kmc_sketch_query.hip; this file gives the shape Triangle (which tile, which pairs,
+// where a result goes).  For a pair (A, B) the lanes take 64 consecutive
 // elements x of A, lower-bound them in B (pos, match), and with the matches
 // before x (a ballot prefix) get the element's rank in the union,
 //     rank = (x + 1) + (pos + match) - matches(A[0..x]),
@@ -87,7 +91,6 @@ constexpr int64_t kChunk = (int64_t)kWalkBlock * kItems;
 constexpr int kDigitBits = 8;
 constexpr int kDigits = 1 << kDigitBits;
 constexpr int kLevels = 64 / kDigitBits;
-constexpr uint64_t kFill = ~0ull;
 constexpr uint64_t kMaxEntries = 1ull << 40;
 
 struct KParams {
@@ -234,27 +237,10 @@ __global__ __launch_bounds__(BLOCK) void sketch_sort_kernel(KParams p) {
     const int s = (int)p.s;  // <= CAP
     for (int64_t r = blockIdx.x; r < p.n; r += gridDim.x) {
         uint64_t *row = p.sketches + r * (int64_t)s;
-        int m = (int)p.sizes[r];
-        if (m > s) m = s;
-        int P = 1;
-        while (P < m) P <<= 1;
+        const int m = row_size(p.sizes, r, s), P = pow2_at_least(m);
         for (int i = tid; i < P; i += BLOCK) buf[i] = i < m ? row[i] : kFill;
         __syncthreads();
-        for (int kk = 2; kk <= P; kk <<= 1) {
-            for (int j = kk >> 1; j > 0; j >>= 1) {
-                for (int t = tid; t < (P >> 1); t += BLOCK) {
-                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                    const int l = i | j;
-                    const uint64_t a = buf[i], b = buf[l];
-                    const bool up = (i & kk) == 0;
-                    if ((a > b) == up) {
-                        buf[i] = b;
-                        buf[l] = a;
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        bitonic_sort<BLOCK>(buf, 1, P, tid, [] { __syncthreads(); });
         for (int i = tid; i < s; i += BLOCK) row[i] = i < m ? buf[i] : kFill;
         __syncthreads();
     }
@@ -263,63 +249,21 @@ __global__ __launch_bounds__(BLOCK) void sketch_sort_kernel(KParams p) {
 // ---------------------------------------------------------------------------
 // distances
 // ---------------------------------------------------------------------------
-struct DParams {
-    const uint64_t *sk;
-    const uint32_t *sizes;
-    int64_t n;
-    int64_t nt, ntiles;  // tile rows; tiles of the upper triangle, diagonal included
-    uint32_t s;
-    int k, T;
-    float *out;
-    uint32_t *shared, *denom;
-};
-
-// pair_counts and mash_distance: kmc_sketch_pair.h, shared with kmc_sketch_query.hip
-template <bool STAGE>
-__global__ __launch_bounds__(kDistBlock) void sketch_dist_kernel(DParams p) {
-    __shared__ uint64_t buf[STAGE ? kDistElems : 1];  // rows of A: [a * s], rows of B: [(T + b) * s]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int T = p.T, s = (int)p.s;
-    for (int64_t t = blockIdx.x; t < p.ntiles; t += gridDim.x) {
-        // invert t = row_start(bi) + (bj - bi), row_start(b) = b * nt - b * (b - 1) / 2
-        const double nn = (double)p.nt;
-        int64_t bi = (int64_t)((2 * nn + 1 - sqrt((2 * nn + 1) * (2 * nn + 1) - 8.0 * (double)t)) / 2);
-        if (bi < 0) bi = 0;
-        if (bi > p.nt - 1) bi = p.nt - 1;
-        while (bi > 0 && bi * p.nt - bi * (bi - 1) / 2 > t) --bi;
-        while (bi + 1 < p.nt && (bi + 1) * p.nt - (bi + 1) * bi / 2 <= t) ++bi;
-        const int64_t bj = bi + (t - (bi * p.nt - bi * (bi - 1) / 2));
-        const int64_t i0 = bi * T, j0 = bj * T;
-        if constexpr (STAGE) {
-            __syncthreads();  // the last tile's readers are done
-            for (int q = tid; q < 2 * T * s; q += kDistBlock) {
-                const int slot = q / s, x = q - slot * s;
-                const int64_t row = slot < T ? i0 + slot : j0 + (slot - T);
-                if (row < p.n && (uint32_t)x < p.sizes[row]) buf[q] = p.sk[row * s + x];
-            }
-            __syncthreads();
-        }
-        for (int pp = wave; pp < T * T; pp += kDistBlock / 64) {
-            const int a = pp / T, b = pp - a * T;
-            const int64_t i = i0 + a, j = j0 + b;
-            if (i >= j || j >= p.n) continue;
-            uint32_t na = p.sizes[i], nb = p.sizes[j];
-            if (na > p.s) na = p.s;
-            if (nb > p.s) nb = p.s;
-            uint32_t sh, dn;
-            if constexpr (STAGE)
-                pair_counts(&buf[a * s], (int)na, &buf[(T + b) * s], (int)nb, s, lane, &sh, &dn);
-            else
-                pair_counts(p.sk + i * s, (int)na, p.sk + j * s, (int)nb, s, lane, &sh, &dn);
-            if (lane == 0) {
-                const int64_t q = tri_index(i, j, p.n);
-                p.out[q] = mash_distance(sh, dn, p.k);
-                if (p.shared) p.shared[q] = sh;
-                if (p.denom) p.denom[q] = dn;
-            }
-        }
+// The packed upper triangle as a shape of sketch_dist_kernel (kmc_sketch_pair.h): both
+// row sets are the one set, the tiles are square, and tile t is the t-th of the nt
+// tile rows' upper triangle, diagonal included.
+struct Triangle {
+    static __device__ __forceinline__ void tile(const DParams &p, int64_t t, uint64_t *buf, TileRows &A, TileRows &B) {
+        // with its diagonal it is the strict triangle of nt + 1: b nt - b (b - 1) / 2 = (nt + 1) b - b (b + 1) / 2
+        const int64_t bi = tri_row(t, p.nrt + 1), bj = bi + (t - tri_row_start(bi, p.nrt + 1));
+        A = TileRows{p.q, p.qs, bi * p.Tq, p.n, buf};
+        B = TileRows{p.q, p.qs, bj * p.Tq, p.n, buf + p.Tq * (int)p.s};
     }
-}
+    static __device__ __forceinline__ bool counts(int64_t i, int64_t j) { return i < j; }
+    static __device__ __forceinline__ int64_t index(const DParams &p, int64_t i, int64_t j) {
+        return tri_index(i, j, p.n);
+    }
+};
 
 // ---------------------------------------------------------------------------
 // host
@@ -344,7 +288,7 @@ inline KLayout layout(void *base, int64_t n) {
 }
 
 inline bool sketch_args_ok(uint64_t num_entries, uint32_t sketch_size) {
-    return sketch_size >= 1 && sketch_size <= KMC_SKETCH_MAX_SIZE && num_entries <= kMaxEntries;
+    return sketch_size_ok(sketch_size) && num_entries <= kMaxEntries;
 }
 
 DeviceCache s_ws;  // library-owned workspace
@@ -370,17 +314,12 @@ extern "C" int kmc_sketch_from_counts(const uint64_t *keys, const uint32_t *coun
     if (num_entries > 0 && !keys) return KMC_ERR_INVALID_ARG;
     if (min_count > 1 && !counts) return KMC_ERR_INVALID_ARG;
     if (num_seqs > kMaxEntries) return KMC_ERR_INVALID_ARG;
-    int device = 0;
-    hipError_t he = hipGetDevice(&device);
-    if (he != hipSuccess) return (int)he;
-    int cus = 0;
-    int e = device_cus(device, &cus);
-    if (e) return e;
+    int device = 0, cus = 0;
+    if (int e = current_device_cus(&device, &cus)) return e;
     const int64_t n = (int64_t)num_seqs, E = (int64_t)num_entries;
-    const size_t need = layout(nullptr, n).bytes;
-    void *ws = nullptr;
-    if ((e = bind_workspace(s_ws, device, need, workspace, workspace_bytes, 0, &ws))) return e;
-    const KLayout L = layout(ws, n);
+    KLayout L;
+    if (int e = bind_layout(s_ws, device, workspace, workspace_bytes, 0, [&](void *b) { return layout(b, n); }, &L))
+        return e;
     int64_t g = (E + kWalkPer - 1) / kWalkPer;
     if (g > 2LL * cus) g = 2LL * cus;
     if (g < 1) g = 1;
@@ -401,8 +340,8 @@ extern "C" int kmc_sketch_from_counts(const uint64_t *keys, const uint32_t *coun
     p.sketches = sketches;
     p.sizes = sketch_sizes;
     // the bins and the cursors are accumulated into; thr and need are written by level 0's decide
-    he = hipMemsetAsync(ws, 0, need, stream);
-    if (he != hipSuccess) return (int)he;
+    // (the whole workspace: hist is its first array)
+    if (hipError_t he = hipMemsetAsync(L.hist, 0, L.bytes, stream)) return (int)he;
     const unsigned rec_grid = (unsigned)(n < kMaxGridX ? n : kMaxGridX);
     for (int level = 0; level < kLevels; ++level) {
         const int shift = 64 - kDigitBits * (level + 1);
@@ -415,42 +354,35 @@ extern "C" int kmc_sketch_from_counts(const uint64_t *keys, const uint32_t *coun
         hipLaunchKernelGGL(sketch_decide_kernel, dim3(rec_grid), dim3(kDigits), 0, stream, p, shift, level == 0 ? 1 : 0);
     }
     if (E > 0) hipLaunchKernelGGL(sketch_collect_kernel, dim3((unsigned)g), dim3(kWalkBlock), 0, stream, p);
-    if (sketch_size <= 1024)
-        hipLaunchKernelGGL((sketch_sort_kernel<1024, 256>), dim3(rec_grid), dim3(256), 0, stream, p);
-    else if (sketch_size <= 4096)
-        hipLaunchKernelGGL((sketch_sort_kernel<4096, 1024>), dim3(rec_grid), dim3(1024), 0, stream, p);
-    else
-        hipLaunchKernelGGL((sketch_sort_kernel<KMC_SKETCH_MAX_SIZE, 1024>), dim3(rec_grid), dim3(1024), 0, stream, p);
+    for_cap(sketch_size, [&](auto cap) {
+        constexpr int CAP = decltype(cap)::value, BLOCK = CAP <= 1024 ? 256 : 1024;
+        hipLaunchKernelGGL((sketch_sort_kernel<CAP, BLOCK>), dim3(rec_grid), dim3(BLOCK), 0, stream, p);
+    });
     return (int)hipGetLastError();
 }
 
 extern "C" int kmc_sketch_distances(const uint64_t *sketches, const uint32_t *sketch_sizes, uint64_t num_seqs,
                                     uint32_t sketch_size, int k, float *out, uint32_t *shared, uint32_t *denom,
                                     hipStream_t stream) {
-    if (k < 1 || k > KMC_CANON_MAX_K) return KMC_ERR_UNSUPPORTED_K;
+    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
     if (num_seqs < 2) return KMC_OK;
     if (!sketches || !sketch_sizes || !out) return KMC_ERR_INVALID_ARG;
-    if (sketch_size < 1 || sketch_size > KMC_SKETCH_MAX_SIZE) return KMC_ERR_INVALID_ARG;
+    if (!sketch_size_ok(sketch_size)) return KMC_ERR_INVALID_ARG;
     if (num_seqs > KMC_SPARSE_MAX_SEQS) return KMC_ERR_INVALID_ARG;
     DParams p;
-    p.sk = sketches;
-    p.sizes = sketch_sizes;
-    p.n = (int64_t)num_seqs;
+    p.q = p.r = sketches;
+    p.qs = p.rs = sketch_sizes;
+    p.m = p.n = (int64_t)num_seqs;
     p.s = sketch_size;
     p.k = k;
     p.out = out;
     p.shared = shared;
     p.denom = denom;
     bool stage = false;
-    int T = tile_edge(kDistElems, sketch_size, &stage);
+    int T = tile_edge(kDistElems, sketch_size, &stage);  // square: not the rectangle's Tr
     if ((int64_t)T > p.n) T = (int)p.n;
-    p.T = T;
-    p.nt = (p.n + T - 1) / T;
-    p.ntiles = p.nt * (p.nt + 1) / 2;
-    const unsigned grid = (unsigned)(p.ntiles < kMaxGridX ? p.ntiles : kMaxGridX);
-    if (stage)
-        hipLaunchKernelGGL(sketch_dist_kernel<true>, dim3(grid), dim3(kDistBlock), 0, stream, p);
-    else
-        hipLaunchKernelGGL(sketch_dist_kernel<false>, dim3(grid), dim3(kDistBlock), 0, stream, p);
-    return (int)hipGetLastError();
+    p.Tq = p.Tr = T;
+    p.nrt = ceil_div(p.n, T);
+    p.ntiles = p.nrt * (p.nrt + 1) / 2;
+    return launch_sketch_dist<Triangle>(p, stage, stream);
 }

@@ -2,14 +2,16 @@
 // sketches: the whole rectangle of Mash distances (kmc_sketch_distances_rect) and
 // the `top` nearest references of every query without that rectangle
 // (kmc_sketch_nearest).  A pair's shared, denom and float are those of
-// kmc_sketch_distances: pair_counts and mash_distance of kmc_sketch_pair.h.
+// kmc_sketch_distances: both calls run the tile loop, pair_counts and mash_distance
+// of kmc_sketch_pair.h.
 //
 // kmc_sketch_distances_rect: the m x n rectangle is cut into tiles of Tq query rows
 // by Tr reference rows; a workgroup stages the Tq + Tr rows of a tile in LDS and its
-// 16 wavefronts take the tile's pairs, one wavefront per pair.  T is the triangle
-// kernel's edge (tile_edge over kDistElems), Tq = min(T, m), Tr = min(kTileMax,
-// kDistElems / s - Tq, n): a short query set leaves its room to the references.
-// Below kStageMinTile (s > 2048 shipped) the rows stay in global memory.
+// 16 wavefronts take the tile's pairs, one wavefront per pair: sketch_dist_kernel of
+// kmc_sketch_pair.h, the triangle's kernel, with the shape Rectangle below.  T is the
+// triangle's edge (tile_edge over kDistElems), Tq = min(T, m), Tr = min(kTileMax,
+// kDistElems / s - Tq, n) (tile_shape): a short query set leaves its room to the
+// references.  Below kStageMinTile (s > 2048 shipped) the rows stay in global memory.
 //
 // kmc_sketch_nearest: reference r takes part for query q iff denom > 0 and shared >=
 // min_shared; the references that do are ordered by J = shared / denom, descending,
@@ -24,7 +26,7 @@
 //           the query's candidate buffer in LDS (C keys, C the power of two >= top +
 //           kTileMax) unless the key is above the query's threshold.  Before a chunk
 //           that could overflow a buffer (count + Tr > C) every buffer is sorted
-//           (bitonic, the network of sketch_sort_kernel), cut to its `top` smallest,
+//           (bitonic_sort of kmc_sketch_pair.h, a segment each), cut to its `top` smallest,
 //           and a buffer that holds `top` keys sets the threshold to its largest.
 //           After the slab the survivors go to the workspace: keys[q][slab][top]
 //           and count[q][slab].
@@ -33,8 +35,9 @@
 //           slab survivors and sorts, until all S * top slots are seen.  The first
 //           `top` keys are the hits; shared, denom and the float of each are
 //           computed again from the two rows (top pairs per query, not n).
-// Tq = min(tile_edge over kQueryElems, kCandElems / C, m); Tr = min(kTileMax,
-// kQueryElems / s - Tq, n), or the global tile edge when the rows are not staged.
+// tile_shape over kQueryElems with the query rows also capped by the candidate buffers:
+// Tq = min(tile edge, kCandElems / C, m); Tr = min(kTileMax, kQueryElems / s - Tq, n),
+// or the global tile edge when the rows are not staged.
 // Slabs: S = ceil(n / per), per a multiple of Tr with (query tiles) * S <= 2 CUs
 // (one slab when there are more query tiles than that), so the workspace is
 //     num_queries * S * (8 top + 4) bytes, S <= max(1, 2 CUs / query tiles).
@@ -73,7 +76,6 @@ constexpr int64_t kSlabMinRefs = 1;
 constexpr int kCandElems = 4096;
 constexpr int kMergeBlock = 256;
 constexpr int kMergeCap = 4096;  // the merge buffer as declared: >= kMergeElems and >= 2 pow2(KMC_NEAREST_MAX_TOP)
-constexpr uint64_t kFill = ~0ull;
 constexpr uint64_t kMaxRefs = 0xFFFFFFFEull;  // the index is 32 bits and UINT32_MAX marks an empty slot
 
 static_assert(2 * KMC_NEAREST_MAX_TOP <= kMergeCap && kMergeElems <= kMergeCap, "merge buffer");
@@ -82,62 +84,17 @@ static_assert(2 * KMC_NEAREST_MAX_TOP <= kCandElems, "one candidate buffer holds
 // ---------------------------------------------------------------------------
 // the rectangle
 // ---------------------------------------------------------------------------
-struct RParams {
-    const uint64_t *q, *r;
-    const uint32_t *qs, *rs;
-    int64_t m, n;
-    int64_t nrt, ntiles;  // reference tiles per query tile; tiles
-    uint32_t s;
-    int k, Tq, Tr;
-    float *out;
-    uint32_t *shared, *denom;
+// The m x n rectangle as a shape of sketch_dist_kernel (kmc_sketch_pair.h): nrt tiles
+// per tile row, every pair of a tile, row-major results.
+struct Rectangle {
+    static __device__ __forceinline__ void tile(const DParams &p, int64_t t, uint64_t *buf, TileRows &A, TileRows &B) {
+        const int64_t bi = t / p.nrt, bj = t - bi * p.nrt;
+        A = TileRows{p.q, p.qs, bi * p.Tq, p.m, buf};
+        B = TileRows{p.r, p.rs, bj * p.Tr, p.n, buf + p.Tq * (int)p.s};
+    }
+    static __device__ __forceinline__ bool counts(int64_t, int64_t) { return true; }
+    static __device__ __forceinline__ int64_t index(const DParams &p, int64_t i, int64_t j) { return i * p.n + j; }
 };
-
-// rows [row0, row0 + T) of sk into buf[slot * s], the first sizes[row] values of each
-__device__ __forceinline__ void stage_rows(uint64_t *buf, const uint64_t *sk, const uint32_t *sizes, int64_t row0,
-                                           int64_t rows_end, int T, int s, int tid) {
-    for (int e = tid; e < T * s; e += kDistBlock) {
-        const int slot = e / s, x = e - slot * s;
-        const int64_t row = row0 + slot;
-        if (row < rows_end && (uint32_t)x < sizes[row]) buf[e] = sk[row * s + x];
-    }
-}
-
-template <bool STAGE>
-__global__ __launch_bounds__(kDistBlock) void sketch_rect_kernel(RParams p) {
-    __shared__ uint64_t buf[STAGE ? kDistElems : 1];  // query rows: [a * s], reference rows: [(Tq + b) * s]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int Tq = p.Tq, Tr = p.Tr, s = (int)p.s;
-    for (int64_t t = blockIdx.x; t < p.ntiles; t += gridDim.x) {
-        const int64_t bq = t / p.nrt, br = t - bq * p.nrt;
-        const int64_t i0 = bq * Tq, j0 = br * Tr;
-        if constexpr (STAGE) {
-            __syncthreads();  // the last tile's readers are done
-            stage_rows(buf, p.q, p.qs, i0, p.m, Tq, s, tid);
-            stage_rows(buf + Tq * s, p.r, p.rs, j0, p.n, Tr, s, tid);
-            __syncthreads();
-        }
-        for (int pp = wave; pp < Tq * Tr; pp += kDistBlock / 64) {
-            const int a = pp / Tr, b = pp - a * Tr;
-            const int64_t i = i0 + a, j = j0 + b;
-            if (i >= p.m || j >= p.n) continue;
-            uint32_t na = p.qs[i], nb = p.rs[j];
-            if (na > p.s) na = p.s;
-            if (nb > p.s) nb = p.s;
-            uint32_t sh, dn;
-            if constexpr (STAGE)
-                pair_counts(&buf[a * s], (int)na, &buf[(Tq + b) * s], (int)nb, s, lane, &sh, &dn);
-            else
-                pair_counts(p.q + i * s, (int)na, p.r + j * s, (int)nb, s, lane, &sh, &dn);
-            if (lane == 0) {
-                const int64_t o = i * p.n + j;
-                p.out[o] = mash_distance(sh, dn, p.k);
-                if (p.shared) p.shared[o] = sh;
-                if (p.denom) p.denom[o] = dn;
-            }
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------
 // the nearest references
@@ -164,29 +121,6 @@ __device__ __forceinline__ uint64_t hit_key(uint32_t shared, uint32_t denom, uin
     return (((1ull << 30) - code) << 32) | ref;
 }
 
-// Ascending bitonic sort of `segs` consecutive segments of `len` keys (a power of two >= 2) each.
-template <int BLOCK>
-__device__ __forceinline__ void sort_segments(uint64_t *buf, int segs, int len, int tid) {
-    const int half = len >> 1;
-    for (int kk = 2; kk <= len; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < segs * half; t += BLOCK) {
-                const int seg = t / half, tt = t - seg * half;
-                const int i = ((tt & ~(j - 1)) << 1) | (tt & (j - 1));
-                const int l = i | j;
-                uint64_t *b = buf + seg * len;
-                const uint64_t x = b[i], y = b[l];
-                const bool up = (i & kk) == 0;
-                if ((x > y) == up) {
-                    b[i] = y;
-                    b[l] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
 // Every candidate buffer sorted and cut to its `top` smallest keys; a buffer that
 // holds `top` of them sets its query's threshold.  Called by the whole workgroup,
 // after a barrier that follows the last append.
@@ -197,7 +131,7 @@ __device__ __forceinline__ void compact(uint64_t *cand, uint32_t *cnt, uint64_t 
         if ((uint32_t)i >= cnt[a]) cand[e] = kFill;
     }
     __syncthreads();
-    sort_segments<kDistBlock>(cand, Tq, C, tid);
+    bitonic_sort<kDistBlock>(cand, Tq, C, tid, [] { __syncthreads(); });
     if (tid < Tq) {
         const uint32_t c = cnt[tid] < (uint32_t)top ? cnt[tid] : (uint32_t)top;
         cnt[tid] = c;
@@ -214,47 +148,38 @@ __global__ __launch_bounds__(kDistBlock) void nearest_slab_kernel(NParams p) {
     __shared__ uint64_t thr[kTileMax];                   // only keys below it can still be among the top
     __shared__ uint32_t cnt[kTileMax];
     __shared__ int full;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int Tq = p.Tq, Tr = p.Tr, C = p.C, s = (int)p.s, top = (int)p.top;
     const int64_t slab = blockIdx.y;
     const int64_t r_lo = slab * p.per;
     const int64_t r_hi = r_lo + p.per < p.n ? r_lo + p.per : p.n;
     for (int64_t qt = blockIdx.x; qt < p.nqt; qt += gridDim.x) {
         const int64_t i0 = qt * Tq;
+        const TileRows A{p.q, p.qs, i0, p.m, rows};
         __syncthreads();  // the last tile's readers are done
         if (tid < Tq) {
             cnt[tid] = 0;
             thr[tid] = kFill;
         }
         if (tid == 0) full = 0;
-        if constexpr (STAGE) stage_rows(rows, p.q, p.qs, i0, p.m, Tq, s, tid);
+        if constexpr (STAGE) stage_rows(A, Tq, s, tid);
         for (int64_t j0 = r_lo; j0 < r_hi; j0 += Tr) {
+            const TileRows B{p.r, p.rs, j0, r_hi, rows + Tq * s};
             __syncthreads();  // the last chunk's pairs are done, the counts final
             if (tid < Tq && cnt[tid] + (uint32_t)Tr > (uint32_t)C) full = 1;
-            if constexpr (STAGE) stage_rows(rows + Tq * s, p.r, p.rs, j0, r_hi, Tr, s, tid);
+            if constexpr (STAGE) stage_rows(B, Tr, s, tid);
             __syncthreads();
             if (full) compact(cand, cnt, thr, &full, Tq, C, top, tid);  // (the same answer in every thread)
-            for (int pp = wave; pp < Tq * Tr; pp += kDistBlock / 64) {
-                const int a = pp / Tr, b = pp - a * Tr;
-                const int64_t i = i0 + a, j = j0 + b;
-                if (i >= p.m || j >= r_hi) continue;
-                uint32_t na = p.qs[i], nb = p.rs[j];
-                if (na > p.s) na = p.s;
-                if (nb > p.s) nb = p.s;
-                uint32_t sh, dn;
-                if constexpr (STAGE)
-                    pair_counts(&rows[a * s], (int)na, &rows[(Tq + b) * s], (int)nb, s, lane, &sh, &dn);
-                else
-                    pair_counts(p.q + i * s, (int)na, p.r + j * s, (int)nb, s, lane, &sh, &dn);
-                if (lane == 0 && dn > 0 && sh >= p.min_shared) {
-                    const uint64_t key = hit_key(sh, dn, (uint32_t)j);
-                    if (key < thr[a]) {
-                        // at most Tr appends per query and chunk, and count + Tr <= C before it
-                        const uint32_t at = atomicAdd(&cnt[a], 1u);
-                        if (at < (uint32_t)C) cand[a * C + at] = key;
-                    }
-                }
-            }
+            tile_pairs<STAGE>(A, B, Tq, Tr, s, tid, [](int64_t, int64_t) { return true; },
+                              [&](int a, int, int64_t, int64_t j, uint32_t sh, uint32_t dn) {
+                                  if (dn == 0 || sh < p.min_shared) return;
+                                  const uint64_t key = hit_key(sh, dn, (uint32_t)j);
+                                  if (key < thr[a]) {
+                                      // at most Tr appends per query and chunk, and count + Tr <= C before it
+                                      const uint32_t at = atomicAdd(&cnt[a], 1u);
+                                      if (at < (uint32_t)C) cand[a * C + at] = key;
+                                  }
+                              });
         }
         __syncthreads();
         compact(cand, cnt, thr, &full, Tq, C, top, tid);
@@ -288,7 +213,7 @@ __global__ __launch_bounds__(kMergeBlock) void nearest_merge_kernel(NParams p) {
                 buf[P + i] = v;
             }
             __syncthreads();
-            sort_segments<kMergeBlock>(buf, 1, M, tid);
+            bitonic_sort<kMergeBlock>(buf, 1, M, tid, [] { __syncthreads(); });
         }
         __syncthreads();
         // ascending, the fill last: the hits are the keys before the first fill among the first `top`
@@ -307,16 +232,13 @@ __global__ __launch_bounds__(kMergeBlock) void nearest_merge_kernel(NParams p) {
             }
         }
         if (total == 0 || (!p.hit_shared && !p.hit_denom && !p.hit_dist)) continue;  // (no reference: no rows at all)
-        uint32_t na = p.qs[q];
-        if (na > p.s) na = p.s;
+        const int na = row_size(p.qs, q, s);
         for (int i = wave; i < top; i += kMergeBlock / 64) {
             const uint64_t key = buf[i];
             if (key == kFill) break;
             const int64_t j = (int64_t)(uint32_t)key;
-            uint32_t nb = p.rs[j];
-            if (nb > p.s) nb = p.s;
             uint32_t sh, dn;
-            pair_counts(p.q + q * s, (int)na, p.r + j * s, (int)nb, s, lane, &sh, &dn);
+            pair_counts(p.q + q * s, na, p.r + j * s, row_size(p.rs, j, s), s, lane, &sh, &dn);
             if (lane == 0) {
                 const int64_t o = q * top + i;
                 if (p.hit_shared) p.hit_shared[o] = sh;
@@ -330,14 +252,6 @@ __global__ __launch_bounds__(kMergeBlock) void nearest_merge_kernel(NParams p) {
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-inline int pow2_at_least(int64_t v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 // The shapes of one kmc_sketch_nearest call: what the launches and the workspace follow.
 struct NPlan {
     bool stage;
@@ -347,21 +261,14 @@ struct NPlan {
 
 inline NPlan plan(int64_t m, int64_t n, uint32_t s, uint32_t top, int cus) {
     NPlan L;
-    const int T = tile_edge(kQueryElems, s, &L.stage);
     L.C = pow2_at_least((int64_t)top + kTileMax);
-    int64_t Tq = T;
-    if (Tq > kCandElems / L.C) Tq = kCandElems / L.C;
-    if (Tq > m) Tq = m;
-    int64_t Tr = T;
-    if (L.stage) {
-        Tr = kQueryElems / (int)s - Tq;
-        if (Tr > kTileMax) Tr = kTileMax;
-    }
-    if (Tr > n) Tr = n;
-    if (Tr < 1) Tr = 1;
-    L.Tq = (int)Tq;
-    L.Tr = (int)Tr;
-    L.nqt = ceil_div(m, Tq);
+    // a query tile is also at most the candidate buffers that fit, before Tr takes the room it leaves
+    const TileShape ts = tile_shape(kQueryElems, s, m < kCandElems / L.C ? m : kCandElems / L.C, n);
+    L.stage = ts.stage;
+    L.Tq = ts.Tq;
+    L.Tr = ts.Tr;
+    const int64_t Tr = L.Tr;
+    L.nqt = ceil_div(m, L.Tq);
 #ifdef KMC_DIAG_HOOKS
     int64_t smax = kMaxGridY;
     (void)cus;
@@ -400,8 +307,8 @@ inline NLayout layout(void *base, int64_t m, const NPlan &L, uint32_t top) {
 }
 
 inline bool nearest_args_ok(uint64_t num_queries, uint64_t num_refs, uint32_t sketch_size, uint32_t top) {
-    return sketch_size >= 1 && sketch_size <= KMC_SKETCH_MAX_SIZE && top >= 1 && top <= KMC_NEAREST_MAX_TOP &&
-           num_refs <= kMaxRefs && num_queries <= KMC_SPARSE_MAX_SEQS;
+    return sketch_size_ok(sketch_size) && top >= 1 && top <= KMC_NEAREST_MAX_TOP && num_refs <= kMaxRefs &&
+           num_queries <= KMC_SPARSE_MAX_SEQS;
 }
 
 DeviceCache n_ws;  // library-owned workspace
@@ -415,12 +322,12 @@ extern "C" int kmc_sketch_distances_rect(const uint64_t *q_sketches, const uint3
                                          const uint64_t *r_sketches, const uint32_t *r_sizes, uint64_t num_refs,
                                          uint32_t sketch_size, int k, float *out, uint32_t *shared, uint32_t *denom,
                                          hipStream_t stream) {
-    if (k < 1 || k > KMC_CANON_MAX_K) return KMC_ERR_UNSUPPORTED_K;
+    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
     if (num_queries == 0 || num_refs == 0) return KMC_OK;
     if (!q_sketches || !q_sizes || !r_sketches || !r_sizes || !out) return KMC_ERR_INVALID_ARG;
-    if (sketch_size < 1 || sketch_size > KMC_SKETCH_MAX_SIZE) return KMC_ERR_INVALID_ARG;
+    if (!sketch_size_ok(sketch_size)) return KMC_ERR_INVALID_ARG;
     if (num_queries > KMC_SPARSE_MAX_SEQS || num_refs > KMC_SPARSE_MAX_SEQS) return KMC_ERR_INVALID_ARG;
-    RParams p;
+    DParams p;
     p.q = q_sketches;
     p.qs = q_sizes;
     p.r = r_sketches;
@@ -432,25 +339,12 @@ extern "C" int kmc_sketch_distances_rect(const uint64_t *q_sketches, const uint3
     p.out = out;
     p.shared = shared;
     p.denom = denom;
-    bool stage = false;
-    const int T = tile_edge(kDistElems, sketch_size, &stage);
-    int64_t Tq = T < p.m ? T : p.m;
-    int64_t Tr = T;
-    if (stage) {
-        Tr = kDistElems / (int)sketch_size - Tq;
-        if (Tr > kTileMax) Tr = kTileMax;
-    }
-    if (Tr > p.n) Tr = p.n;
-    p.Tq = (int)Tq;
-    p.Tr = (int)Tr;
-    p.nrt = ceil_div(p.n, Tr);
-    p.ntiles = ceil_div(p.m, Tq) * p.nrt;
-    const unsigned grid = (unsigned)(p.ntiles < kMaxGridX ? p.ntiles : kMaxGridX);
-    if (stage)
-        hipLaunchKernelGGL(sketch_rect_kernel<true>, dim3(grid), dim3(kDistBlock), 0, stream, p);
-    else
-        hipLaunchKernelGGL(sketch_rect_kernel<false>, dim3(grid), dim3(kDistBlock), 0, stream, p);
-    return (int)hipGetLastError();
+    const TileShape ts = tile_shape(kDistElems, sketch_size, p.m, p.n);
+    p.Tq = ts.Tq;
+    p.Tr = ts.Tr;
+    p.nrt = ceil_div(p.n, ts.Tr);
+    p.ntiles = ceil_div(p.m, ts.Tq) * p.nrt;
+    return launch_sketch_dist<Rectangle>(p, ts.stage, stream);
 }
 
 extern "C" size_t kmc_sketch_nearest_workspace_size(uint64_t num_queries, uint64_t num_refs, uint32_t sketch_size,
@@ -468,7 +362,7 @@ extern "C" int kmc_sketch_nearest(const uint64_t *q_sketches, const uint32_t *q_
                                   uint32_t sketch_size, int k, uint32_t top, uint32_t min_shared, uint32_t *hit_refs,
                                   uint32_t *hit_shared, uint32_t *hit_denom, float *hit_dist, uint32_t *hit_counts,
                                   void *workspace, size_t workspace_bytes, hipStream_t stream) {
-    if (k < 1 || k > KMC_CANON_MAX_K) return KMC_ERR_UNSUPPORTED_K;
+    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
     if (!nearest_args_ok(num_queries, num_refs, sketch_size, top)) return KMC_ERR_INVALID_ARG;
     if (num_queries == 0) return KMC_OK;
     if (!hit_refs || !hit_counts) return KMC_ERR_INVALID_ARG;
@@ -496,17 +390,13 @@ extern "C" int kmc_sketch_nearest(const uint64_t *q_sketches, const uint32_t *q_
     p.P = pow2_at_least(top);
     p.M = 2 * p.P;
     if (p.n > 0) {
-        int device = 0;
-        const hipError_t he = hipGetDevice(&device);
-        if (he != hipSuccess) return (int)he;
-        int cus = 0;
-        if (int e = device_cus(device, &cus)) return e;
+        int device = 0, cus = 0;
+        if (int e = current_device_cus(&device, &cus)) return e;
         const NPlan L = plan(p.m, p.n, sketch_size, top, cus);
-        void *ws = nullptr;
-        if (int e = bind_workspace(n_ws, device, layout(nullptr, p.m, L, top).bytes, workspace, workspace_bytes, 0,
-                                   &ws))
+        NLayout W;
+        if (int e = bind_layout(n_ws, device, workspace, workspace_bytes, 0,
+                                [&](void *b) { return layout(b, p.m, L, top); }, &W))
             return e;
-        const NLayout W = layout(ws, p.m, L, top);
         p.ws_keys = W.keys;
         p.ws_cnt = W.cnt;
         p.nqt = L.nqt;

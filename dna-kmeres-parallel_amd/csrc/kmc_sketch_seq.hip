@@ -42,7 +42,7 @@
 //           key is staged once per merge at most and low-complexity input costs
 //           searches, not merges).  Candidates are appended to a staging buffer of
 //           kStage values through an LDS counter; when it is full it is sorted
-//           (bitonic) and merged into the set: every staged value not equal to its
+//           (bitonic_sort of kmc_sketch_pair.h) and merged into the set: every staged value not equal to its
 //           predecessor nor in the set is kept, set values move up by the kept values
 //           below them, kept values land behind the set values below them, positions
 //           >= s fall off.  Lanes whose candidates did not fit filter them against the
@@ -93,11 +93,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <type_traits>
 
 #include "kmc.h"
 #include "kmc_canon_walk.h"
 #include "kmc_internal.h"
+#include "kmc_sketch_pair.h"
 #include "kmc_workspace.h"
 
 namespace kmc {
@@ -114,7 +114,6 @@ constexpr int kWgPerCu = 1;
 #endif
 constexpr int kStage = kBlock;
 constexpr int kWaves = kBlock / 64;
-constexpr uint64_t kFill = ~0ull;
 constexpr uint64_t kMaxSeqs = 1ull << 40;
 
 struct Args {
@@ -289,19 +288,7 @@ struct SetLds {
 };
 static_assert(sizeof(SetLds<KMC_SKETCH_MAX_SIZE>) <= 160 * 1024, "the set and its staging buffer fit the CU's LDS");
 
-// first index in a[0, n) whose value is not below v
-__device__ __forceinline__ int lower_bound(const uint64_t *a, int n, uint64_t v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < v)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
+// (lower_bound and bitonic_sort: kmc_sketch_pair.h)
 __device__ __forceinline__ bool in_set(const uint64_t *set, int m, uint64_t v) {
     const int i = lower_bound(set, m, v);
     return i < m && set[i] == v;
@@ -314,25 +301,11 @@ template <int CAP>
 __device__ __forceinline__ int merge_stage(SetLds<CAP> &L, int m, int s, int c) {
     constexpr int R = CAP / kBlock < 1 ? 1 : (CAP / kBlock > 4 ? 4 : CAP / kBlock);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int P = 1;
-    while (P < c) P <<= 1;
+    const int P = pow2_at_least(c);  // <= kStage = kBlock
     if (tid >= c && tid < P) L.stage[tid] = kFill;
     lds_barrier();
-    for (int kk = 2; kk <= P; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            if (tid < (P >> 1)) {
-                const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1));
-                const int l = i | j;
-                const uint64_t x = L.stage[i], y = L.stage[l];
-                const bool up = (i & kk) == 0;
-                if ((x > y) == up) {
-                    L.stage[i] = y;
-                    L.stage[l] = x;
-                }
-            }
-            lds_barrier();
-        }
-    }
+    // LDS-only barriers: a __syncthreads() would wait for the walk's chunk prefetch
+    bitonic_sort<kBlock, true>(L.stage, 1, P, tid, [] { lds_barrier(); });
     // staged value tid: kept unless it repeats its predecessor or is in the set
     uint64_t v = 0;
     int lb = 0;
@@ -634,26 +607,18 @@ inline SLayout layout(void *base, int64_t n, int G, uint32_t s, int64_t ng = -1)
 }
 
 inline bool seq_args_ok(uint64_t num_seqs, uint64_t data_bytes, uint32_t sketch_size) {
-    return sketch_size >= 1 && sketch_size <= KMC_SKETCH_MAX_SIZE && num_seqs <= kMaxSeqs && data_bytes < (1ull << 62);
+    return sketch_size_ok(sketch_size) && num_seqs <= kMaxSeqs && data_bytes < (1ull << 62);
 }
 
 // what both entry points refuse before anything else, in this order
 inline int seq_check(int k, uint64_t num_seqs, uint64_t data_bytes, uint32_t sketch_size, unsigned flags) {
-    if (k < 1 || k > KMC_CANON_MAX_K) return KMC_ERR_UNSUPPORTED_K;
+    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
     if (!seq_args_ok(num_seqs, data_bytes, sketch_size)) return KMC_ERR_INVALID_ARG;
     if (flags & ~(KMC_CANON_SOFTMASK | KMC_CANON_FORWARD)) return KMC_ERR_INVALID_ARG;
     return KMC_OK;
 }
 
 DeviceCache q_ws;  // library-owned workspace
-
-// f(the set capacity of sketch size s, as an integral constant)
-template <class F>
-inline void for_cap(uint32_t s, F &&f) {
-    if (s <= 1024) f(std::integral_constant<int, 1024>{});
-    else if (s <= 4096) f(std::integral_constant<int, 4096>{});
-    else f(std::integral_constant<int, KMC_SKETCH_MAX_SIZE>{});
-}
 
 // Both entry points after their argument checks: the workspace of the call (Records:
 // group_offsets null, ng = -1) and the launches.
@@ -662,14 +627,13 @@ int sketch_units(const char *data, const int64_t *indices, uint64_t num_seqs, ui
                  const int64_t *group_offsets, int64_t ng, int k, unsigned flags, uint32_t sketch_size, uint64_t seed,
                  uint64_t *sketches, uint32_t *sketch_sizes, void *workspace, size_t workspace_bytes, hipStream_t st) {
     int device = 0, cus = 0;
-    if (hipError_t he = hipGetDevice(&device)) return (int)he;
-    if (int e = device_cus(device, &cus)) return e;
+    if (int e = current_device_cus(&device, &cus)) return e;
     const int64_t n = (int64_t)num_seqs;
     const int G = walk_groups(data_bytes, cus);
-    const size_t need = layout(nullptr, n, G, sketch_size, ng).bytes;
-    void *ws = nullptr;
-    if (int e = bind_workspace(q_ws, device, need, workspace, workspace_bytes, 8, &ws)) return e;
-    const SLayout L = layout(ws, n, G, sketch_size, ng);
+    SLayout L;
+    if (int e = bind_layout(q_ws, device, workspace, workspace_bytes, 8,
+                            [&](void *b) { return layout(b, n, G, sketch_size, ng); }, &L))
+        return e;
     // any `data` pointer: rounded down to 16 bytes, every offset moved up by the
     // difference (kmc_count_canonical_hash's rule, applied on the device by prep)
     const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
@@ -773,8 +737,7 @@ extern "C" int kmc_sketch_from_sequences_grouped(const char *data, const int64_t
 extern "C" int kmc_sketch_merge_groups(const uint64_t *sketches_in, const uint32_t *sizes_in, uint64_t num_rows,
                                        const int64_t *group_offsets, uint64_t num_groups, uint32_t sketch_size,
                                        uint64_t *sketches_out, uint32_t *sizes_out, hipStream_t stream) {
-    if (sketch_size < 1 || sketch_size > KMC_SKETCH_MAX_SIZE || num_rows > kMaxSeqs || num_groups > kMaxSeqs)
-        return KMC_ERR_INVALID_ARG;
+    if (!sketch_size_ok(sketch_size) || num_rows > kMaxSeqs || num_groups > kMaxSeqs) return KMC_ERR_INVALID_ARG;
     if (num_groups == 0) return KMC_OK;
     if (!group_offsets || !sketches_out || !sizes_out) return KMC_ERR_INVALID_ARG;
     if (num_rows > 0 && (!sketches_in || !sizes_in)) return KMC_ERR_INVALID_ARG;

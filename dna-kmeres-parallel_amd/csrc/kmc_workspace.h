@@ -1,7 +1,9 @@
 // kmc_workspace.h — host-side workspace plumbing shared by the .hip translation
 // units (no kernels, no device code): the 256-byte rounding of every layout, the
 // carver that lays a workspace out, the per-device grow-only scratch buffer, the
-// choice between it and a caller's workspace, and the cached CU count of a device.
+// choice between it and a caller's workspace, the cached CU count of a device, and
+// the two steps most entry points open with: the current device with its CU count,
+// and a layout sized, bound and laid out (bind_layout).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -98,6 +100,24 @@ inline int device_cus(int device, int *cus) {
         known[device] = v;
     }
     *cus = known[device];
+    return 0;
+}
+
+// The calling thread's current device and its compute units.
+inline int current_device_cus(int *device, int *cus) {
+    if (hipError_t he = hipGetDevice(device)) return (int)he;
+    return device_cus(*device, cus);
+}
+
+// Sizes, binds and lays out the workspace of one call.  layout_of(base) is the one
+// layout of the subsystem, a struct of pointers with the size in `bytes`: over null
+// it gives the size to bind (bind_workspace), over the bound workspace *out.
+template <class LayoutOf, class Layout>
+inline int bind_layout(DeviceCache &cache, int device, void *caller, size_t caller_bytes, size_t align,
+                       LayoutOf layout_of, Layout *out) {
+    void *ws = nullptr;
+    if (int e = bind_workspace(cache, device, layout_of(nullptr).bytes, caller, caller_bytes, align, &ws)) return e;
+    *out = layout_of(ws);
     return 0;
 }
 

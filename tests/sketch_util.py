@@ -1,6 +1,9 @@
 """Host-side oracle shared by the sketch tests (test_sketch_abi.py,
 test_sketch_gpu.py, test_sketch_cli.py): plain numpy with uint64 wrap-around
-arithmetic, no device."""
+arithmetic, no device.  After it, the helpers the GPU test files of the sketch and
+sparse-distance paths have in common."""
+import contextlib
+
 import numpy as np
 
 _U = np.uint64
@@ -95,3 +98,46 @@ def distances_expected(rows, sizes, s, k):
             out[q] = mash_formula(sh, u.size, k)
             q += 1
     return out, shared, denom
+
+
+# helpers of the GPU test files ---------------------------------------------------------
+def which(kmc, lib):
+    """The library a case runs in: libkmc_diag.so inside the context, else libkmc.so."""
+    return kmc.diag() if lib == "diag" else contextlib.nullcontext()
+
+
+def dev(x, cuda):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(x)).to(cuda)
+
+
+def cache():
+    """cached(key, make) over a store of its own: make() runs once per key."""
+    store = {}
+
+    def cached(key, make):
+        if key not in store:
+            store[key] = make()
+        return store[key]
+    return cached
+
+
+def bases(rng, n):
+    return rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=int(n))
+
+
+def pack(records):
+    """Records (uint8 base arrays) -> (data with a 0 terminator after each, int64 offsets)."""
+    parts, idx = [], [0]
+    for r in records:
+        parts += [np.asarray(r, dtype=np.uint8), np.zeros(1, np.uint8)]
+        idx.append(idx[-1] + len(r) + 1)
+    return np.concatenate(parts), np.asarray(idx, dtype=np.int64)
+
+
+def assert_sketch(got, exp, msg=""):
+    (rows, sizes), (erows, esizes) = got, exp
+    np.testing.assert_array_equal(sizes, esizes, err_msg="%s sizes" % msg)
+    assert rows.shape == erows.shape, msg
+    bad = np.nonzero((rows != erows).any(axis=1))[0]
+    assert bad.size == 0, "%s: rows %s differ" % (msg, bad[:5])

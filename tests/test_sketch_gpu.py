@@ -10,27 +10,19 @@ in double: two correct double logs differ by less than a double ulp, which moves
 the rounded float by at most one ulp), the special values NaN, 1.0 and +0.0 bit
 for bit.
 """
-import contextlib
 
 import numpy as np
 import pytest
 
 import golden_util as G
 import sketch_util as S
+from sketch_util import assert_sketch, dev, which
 
 pytestmark = pytest.mark.gpu
 
 LIBS = ["ship", "diag"]
+cached = S.cache()
 U64 = np.uint64
-
-
-def which(kmc, lib):
-    return kmc.diag() if lib == "diag" else contextlib.nullcontext()
-
-
-def dev(x, cuda):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x)).to(cuda)
 
 
 def dev_lists(keys, counts, off, cuda):
@@ -48,14 +40,6 @@ def gpu_sketch(kmc, cuda, keys, counts, off, s, **kw):
     return sk.cpu().numpy().view(np.uint64), sz.cpu().numpy().view(np.uint32)
 
 
-def assert_sketch(got, exp, msg=""):
-    (rows, sizes), (erows, esizes) = got, exp
-    np.testing.assert_array_equal(sizes, esizes, err_msg="%s sizes" % msg)
-    assert rows.shape == erows.shape, msg
-    bad = np.nonzero((rows != erows).any(axis=1))[0]
-    assert bad.size == 0, "%s: rows %s differ" % (msg, bad[:5])
-
-
 def lists_of(rng, sizes):
     """Random distinct 62-bit keys, sizes[r] of them in record r, shuffled."""
     total = int(np.sum(sizes))
@@ -64,15 +48,6 @@ def lists_of(rng, sizes):
     assert keys.size == total
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
     return keys, off
-
-
-_cache = {}
-
-
-def cached(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
 
 
 # 1. record shapes -----------------------------------------------------------------
@@ -268,7 +243,9 @@ def gpu_distances(kmc, cuda, rows, sizes, k, with_counts):
 
 @pytest.mark.parametrize("lib", LIBS)
 @pytest.mark.parametrize("n,s,k", [(2, 16, 21), (3, 16, 21), (65, 16, 21), (130, 16, 21),
-                                   (5, 1, 3), (5, 1000, 3), (5, 16384, 3)])
+                                   (5, 1, 3), (5, 1000, 3), (5, 16384, 3),
+                                   # diag tile edge 4: one full tile, one row past it, three ragged tile rows
+                                   (4, 64, 21), (5, 64, 21), (9, 64, 21)])
 def test_sketch_distance_counts_and_floats(kmc, cuda, lib, n, s, k):
     rows, sizes = dist_rows(n, s)
     exp = cached(("dist", n, s, k), lambda: S.distances_expected(rows, sizes, s, k))

@@ -6,7 +6,6 @@ bit, tail fill included.  Every case runs in libkmc.so and in libkmc_diag.so, wh
 thousand bases through many ranges, merges and partial sets: there a group's span
 crosses many range cuts, and a stretch of short records is longer than a range.
 """
-import contextlib
 import ctypes
 
 import numpy as np
@@ -14,34 +13,19 @@ import pytest
 
 import sketch_group_util as GU
 import sketch_util as S
+from sketch_util import assert_sketch, bases, pack, which
 
 pytestmark = pytest.mark.gpu
 
 LIBS = ["ship", "diag"]
+cached = S.cache()
 SOFT, FWD = GU.SOFT, GU.FWD
-
-
-def which(kmc, lib):
-    return kmc.diag() if lib == "diag" else contextlib.nullcontext()
-
-
-def bases(rng, n):
-    return rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=int(n))
 
 
 def revcomp(seq):
     comp = np.zeros(256, np.uint8)
     comp[list(b"ACGT")] = list(b"TGCA")
     return comp[seq][::-1]
-
-
-def pack(records):
-    """Records (uint8 base arrays) -> (data with a 0 terminator after each, int64 offsets)."""
-    parts, idx = [], [0]
-    for r in records:
-        parts += [np.asarray(r, dtype=np.uint8), np.zeros(1, np.uint8)]
-        idx.append(idx[-1] + len(r) + 1)
-    return np.concatenate(parts), np.asarray(idx, dtype=np.int64)
 
 
 def to_device(cuda, data, idx, shift=0):
@@ -74,23 +58,6 @@ def gpu_merged(kmc, cuda, data, idx, go, k, s, flags=0, **kw):
     dg = torch.from_numpy(np.asarray(go, dtype=np.int64)).to(cuda)
     rows, sizes = kmc.sketch_from_sequences(d, di, k, s, flags=flags, **kw)
     return host(kmc.sketch_merge_groups(rows, sizes, dg))
-
-
-def assert_sketch(got, exp, msg=""):
-    (rows, sizes), (erows, esizes) = got, exp
-    np.testing.assert_array_equal(sizes, esizes, err_msg="%s sizes" % msg)
-    assert rows.shape == erows.shape, msg
-    bad = np.nonzero((rows != erows).any(axis=1))[0]
-    assert bad.size == 0, "%s: rows %s differ" % (msg, bad[:5])
-
-
-_cache = {}
-
-
-def cached(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
 
 
 # 1. identity grouping -----------------------------------------------------------------

@@ -13,7 +13,6 @@ evaluates the formula in double, and two correct double logs differ by less than
 a double ulp, which moves the rounded float by at most one ulp).  hit_dist equals
 kmc_sketch_distances_rect's float of the pair bit for bit.
 """
-import contextlib
 import os
 import subprocess
 
@@ -23,22 +22,15 @@ import pytest
 import golden_util as G
 import sketch_query_util as Q
 import sketch_util as S
+from sketch_util import dev, which
 
 pytestmark = pytest.mark.gpu
 
 LIBS = ["ship", "diag"]
+cached = S.cache()
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KMC = os.environ.get("KMC_BIN") or os.path.join(REPO, "dna-kmeres-parallel_amd", "bin", "kmc")
 RANDOM_FA = os.path.join(G.GOLDEN, "random.fa")
-
-
-def which(kmc, lib):
-    return kmc.diag() if lib == "diag" else contextlib.nullcontext()
-
-
-def dev(x, cuda):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x)).to(cuda)
 
 
 def dev_rows(rows, sizes, cuda):
@@ -48,15 +40,6 @@ def dev_rows(rows, sizes, cuda):
 def host(t, dtype=None):
     a = t.cpu().numpy()
     return a if dtype is None else a.view(dtype)
-
-
-_cache = {}
-
-
-def cached(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
 
 
 def random_rows(rng, n, s, pool, forced=()):

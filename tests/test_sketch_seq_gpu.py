@@ -10,7 +10,6 @@ Offsets above 2^31 are not tested here: the walk's 64-bit path (chunk_raw's
 rebased buffer resource, kmc_canon_walk.h) is shared unchanged with the canonical
 counter, whose large-offset tests cover it.
 """
-import contextlib
 import os
 
 import numpy as np
@@ -18,29 +17,14 @@ import pytest
 
 import sketch_group_util as GU
 import sketch_util as S
+from sketch_util import assert_sketch, bases, pack, which
 
 pytestmark = pytest.mark.gpu
 
 LIBS = ["ship", "diag"]
+cached = S.cache()
 SOFT, FWD = 1, 2
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def which(kmc, lib):
-    return kmc.diag() if lib == "diag" else contextlib.nullcontext()
-
-
-def bases(rng, n):
-    return rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=int(n))
-
-
-def pack(records):
-    """Records (uint8 base arrays) -> (data with a 0 terminator after each, int64 offsets)."""
-    parts, idx = [], [0]
-    for r in records:
-        parts += [np.asarray(r, dtype=np.uint8), np.zeros(1, np.uint8)]
-        idx.append(idx[-1] + len(r) + 1)
-    return np.concatenate(parts), np.asarray(idx, dtype=np.int64)
 
 
 def expected(oracle, data, idx, k, s, flags=0, seed=S.DEFAULT_SEED):
@@ -59,23 +43,6 @@ def gpu_seq(kmc, cuda, data, idx, k, s, flags=0, shift=0, **kw):
     sk, sz = kmc.sketch_from_sequences(d, di, k, s, flags=flags, **kw)
     torch.cuda.synchronize()
     return sk.cpu().numpy().view(np.uint64), sz.cpu().numpy().view(np.uint32)
-
-
-def assert_sketch(got, exp, msg=""):
-    (rows, sizes), (erows, esizes) = got, exp
-    np.testing.assert_array_equal(sizes, esizes, err_msg="%s sizes" % msg)
-    assert rows.shape == erows.shape, msg
-    bad = np.nonzero((rows != erows).any(axis=1))[0]
-    assert bad.size == 0, "%s: rows %s differ" % (msg, bad[:5])
-
-
-_cache = {}
-
-
-def cached(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
 
 
 # 1. record shapes -----------------------------------------------------------------

@@ -7,13 +7,13 @@ through the multi-pass and the tiled paths.
 
 Floats are compared bit for bit (NaN == NaN, +0 == -0); the sums are exact.
 """
-import contextlib
 
 import numpy as np
 import pytest
 
 import golden_util as G
 import sparse_dist_util as U
+from sketch_util import dev, which
 
 pytestmark = pytest.mark.gpu
 
@@ -28,15 +28,6 @@ def same_floats(got, exp, msg=""):
     bad = ~both_nan & (got.view(np.uint32) != exp.view(np.uint32)) & ~((got == 0) & (exp == 0))
     assert not bad.any(), "%s: %d mismatches, first at %d: %r vs %r" % (
         msg, int(bad.sum()), int(np.argmax(bad)), got[bad][:3], exp[bad][:3])
-
-
-def which(kmc, lib):
-    return kmc.diag() if lib == "diag" else contextlib.nullcontext()
-
-
-def dev(x, cuda):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x)).to(cuda)
 
 
 def dev_lists(keys, counts, off, cuda):
