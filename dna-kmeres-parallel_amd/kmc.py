@@ -12,6 +12,15 @@ Reference interface mirrored (axlwild/dna-kmeres-parallel):
         -> count_dense(data, indices, k)
     importSeqs / importSeqsNoNL                                     main.cu:474-545 / 401-473
         -> load_fasta(path, dialect)
+
+Streams: every device wrapper takes `stream=` (None: torch's current stream) and
+hands it to the library.  What the wrapper itself does with tensors (allocating
+outputs, zeroing, padding, `.contiguous()` copies) runs on that same stream: with
+`stream=s` given it is done under `torch.cuda.stream(s)`, so the library never
+reads or writes a tensor the wrapper is still preparing on another stream.  The
+caller orders its own use of the inputs and results against `s`.  The wrappers
+that return tensors also take `out=`: the caller's own output tensors, in the
+order they are returned.
 """
 import ctypes
 import os
@@ -234,6 +243,13 @@ def _stream(stream):
     return ctypes.c_void_p(s.cuda_stream)
 
 
+def _on(stream):
+    """Context of a wrapper's own tensor work: on `stream` when one is given, else
+    on the current stream (see the module docstring)."""
+    import torch
+    return torch.cuda.stream(stream)  # (a no-op for None)
+
+
 def _dptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -245,9 +261,12 @@ def _ws(workspace):
     return _dptr(workspace), workspace.numel() * workspace.element_size()
 
 
-def _sketch_out(n, s, device):
-    """Uninitialised (sketches int64 [n, s], sizes int32 [n]) of the sketch entry points."""
+def _sketch_out(n, s, device, out=None):
+    """Uninitialised (sketches int64 [n, s], sizes int32 [n]) of the sketch entry
+    points, or the caller's own pair `out`."""
     import torch
+    if out is not None:
+        return out
     return (torch.empty((max(n, 0), max(s, 0)), dtype=torch.int64, device=device),
             torch.empty(max(n, 0), dtype=torch.int32, device=device))
 
@@ -258,7 +277,8 @@ def dropin_count(data, indices, num_seqs=None, out=None, stream=None):
     import torch
     n = int(num_seqs if num_seqs is not None else indices.numel() - 1)
     if out is None:
-        out = torch.empty((1 << (2 * DROPIN_K)) * n, dtype=torch.int32, device=data.device)
+        with _on(stream):
+            out = torch.empty((1 << (2 * DROPIN_K)) * n, dtype=torch.int32, device=data.device)
     rc = lib().sumKmereCoincidencesGlobalMemory_hip(_dptr(data), _dptr(indices), n, _dptr(out), _stream(stream))
     _check(rc, "sumKmereCoincidencesGlobalMemory_hip")
     return out
@@ -269,15 +289,20 @@ def dense_workspace_size(k, num_seqs, data_bytes, device=0):
 
 
 def count_dense(data, indices, k, data_bytes=None, invalid=False, workspace=None, out=None, stream=None):
-    """k-mer histogram of every record: returns (sum (4^k, n) int32, invalid (n,) or None)."""
+    """k-mer histogram of every record: returns (sum (4^k, n) int32, invalid (n,) or None).
+    `invalid`: True for a new tensor, or the caller's own int32 tensor (n,)."""
     import torch
     n = indices.numel() - 1
     nb = 1 << (2 * k)
     if data_bytes is None:
         data_bytes = data.numel()
-    if out is None:
-        out = torch.empty((nb, n), dtype=torch.int32, device=data.device)
-    inv = torch.empty(n, dtype=torch.int32, device=data.device) if invalid else None
+    with _on(stream):
+        if out is None:
+            out = torch.empty((nb, n), dtype=torch.int32, device=data.device)
+        if isinstance(invalid, torch.Tensor):
+            inv = invalid
+        else:
+            inv = torch.empty(n, dtype=torch.int32, device=data.device) if invalid else None
     rc = lib().kmc_count_dense(_dptr(data), _dptr(indices), n, data_bytes, k, _dptr(out), _dptr(inv),
                                *_ws(workspace), _stream(stream))
     _check(rc, "kmc_count_dense")
@@ -340,7 +365,8 @@ def pair_distances(counts, indices, k, num_seqs=None, ld=0, out=None, workspace=
     import torch
     n = int(num_seqs if num_seqs is not None else indices.numel() - 1)
     if out is None:
-        out = torch.empty(max(n * (n - 1) // 2, 0), dtype=torch.float32, device=counts.device)
+        with _on(stream):
+            out = torch.empty(max(n * (n - 1) // 2, 0), dtype=torch.float32, device=counts.device)
     rc = lib().kmc_pair_distances(_dptr(counts), ld, _dptr(indices), n, k, _dptr(out), *_ws(workspace),
                                   _stream(stream))
     _check(rc, "kmc_pair_distances")
@@ -352,19 +378,24 @@ CANON_FORWARD = 2
 CANON_MAX_K = 31
 
 
-def count_canonical(data, indices, k, flags=0, capacity=None, workspace=None, stream=None):
+def count_canonical(data, indices, k, flags=0, capacity=None, workspace=None, out=None, stream=None):
     """Canonical k-mer counts per record (kmc_count_canonical_hash[_ex]): returns
     (keys uint64 as int64 tensor, counts int32 tensor, rec_offsets int64 tensor);
     record s owns [rec_offsets[s], rec_offsets[s+1]), order within it unspecified.
     `workspace`: a caller device buffer of canonical_workspace_size() bytes (None:
-    the library's own)."""
+    the library's own).  `out`: the caller's own (keys, counts, rec_offsets), the
+    first two of `capacity` elements; views of them are returned."""
     import torch
     n = indices.numel() - 1
     if capacity is None:
         capacity = max(int(data.numel()), 1)
-    keys = torch.empty(capacity, dtype=torch.int64, device=data.device)
-    counts = torch.empty(capacity, dtype=torch.int32, device=data.device)
-    off = torch.zeros(max(n + 1, 1), dtype=torch.int64, device=data.device)
+    if out is not None:
+        keys, counts, off = out
+    else:
+        with _on(stream):
+            keys = torch.empty(capacity, dtype=torch.int64, device=data.device)
+            counts = torch.empty(capacity, dtype=torch.int32, device=data.device)
+            off = torch.zeros(max(n + 1, 1), dtype=torch.int64, device=data.device)
     tot = _U64(0)
     # (kmc_count_canonical_hash is this call with no workspace)
     rc = lib().kmc_count_canonical_hash_ex(_dptr(data), _dptr(indices), n, k, flags, _dptr(keys), _dptr(counts),
@@ -395,7 +426,8 @@ def pair_distances_sparse(keys, counts, rec_offsets, indices, k, num_entries=Non
     if num_entries is None:
         num_entries = keys.numel()
     if out is None:
-        out = torch.empty(max(n * (n - 1) // 2, 0), dtype=torch.float32, device=indices.device)
+        with _on(stream):
+            out = torch.empty(max(n * (n - 1) // 2, 0), dtype=torch.float32, device=indices.device)
     rc = lib().kmc_pair_distances_sparse(_dptr(keys), _dptr(counts), _dptr(rec_offsets), int(num_entries),
                                          _dptr(indices), n, k, _dptr(out), *_ws(workspace), _stream(stream))
     _check(rc, "kmc_pair_distances_sparse")
@@ -411,7 +443,7 @@ def sketch_workspace_size(num_seqs, num_entries, sketch_size, device=0):
 
 
 def sketch_from_counts(keys, counts, rec_offsets, sketch_size, seed=SKETCH_DEFAULT_SEED, min_count=1,
-                       workspace=None, num_entries=None, stream=None):
+                       workspace=None, num_entries=None, out=None, stream=None):
     """Bottom-s MinHash sketches (kmc_sketch_from_counts) of per-record lists as
     count_canonical returns them (`counts` may be None while min_count <= 1).
     Returns (sketches int64 [n, s]: uint64 hashes ascending, then all-ones fill;
@@ -420,7 +452,8 @@ def sketch_from_counts(keys, counts, rec_offsets, sketch_size, seed=SKETCH_DEFAU
     s = int(sketch_size)
     if num_entries is None:
         num_entries = keys.numel()
-    sk, sizes = _sketch_out(n, s, rec_offsets.device)
+    with _on(stream):
+        sk, sizes = _sketch_out(n, s, rec_offsets.device, out)
     rc = lib().kmc_sketch_from_counts(_dptr(keys), _dptr(counts), _dptr(rec_offsets), int(num_entries), n, s,
                                       int(seed) & _M64, int(min_count), _dptr(sk), _dptr(sizes), *_ws(workspace),
                                       _stream(stream))
@@ -433,7 +466,7 @@ def sketch_from_sequences_workspace_size(num_seqs, data_bytes, sketch_size, devi
 
 
 def sketch_from_sequences(data, indices, k, sketch_size, flags=0, seed=SKETCH_DEFAULT_SEED, data_bytes=None,
-                          workspace=None, stream=None):
+                          workspace=None, out=None, stream=None):
     """Bottom-s MinHash sketches straight from the record buffer
     (kmc_sketch_from_sequences): the rows and sizes sketch_from_counts gives for
     count_canonical's lists of the same data, indices, k and flags, in one pass and
@@ -442,7 +475,8 @@ def sketch_from_sequences(data, indices, k, sketch_size, flags=0, seed=SKETCH_DE
     s = int(sketch_size)
     if data_bytes is None:
         data_bytes = data.numel()
-    sk, sizes = _sketch_out(n, s, indices.device)
+    with _on(stream):
+        sk, sizes = _sketch_out(n, s, indices.device, out)
     rc = lib().kmc_sketch_from_sequences(_dptr(data), _dptr(indices), n, int(data_bytes), k, flags, s,
                                          int(seed) & _M64, _dptr(sk), _dptr(sizes), *_ws(workspace),
                                          _stream(stream))
@@ -456,7 +490,7 @@ def sketch_from_sequences_grouped_workspace_size(num_seqs, num_groups, data_byte
 
 
 def sketch_from_sequences_grouped(data, indices, group_offsets, k, sketch_size, flags=0, seed=SKETCH_DEFAULT_SEED,
-                                  data_bytes=None, workspace=None, stream=None):
+                                  data_bytes=None, workspace=None, out=None, stream=None):
     """One bottom-s MinHash sketch per group of consecutive records
     (kmc_sketch_from_sequences_grouped): group g owns the records
     [group_offsets[g], group_offsets[g+1]) (device int64 tensor) and its row is the
@@ -467,42 +501,54 @@ def sketch_from_sequences_grouped(data, indices, group_offsets, k, sketch_size, 
     s = int(sketch_size)
     if data_bytes is None:
         data_bytes = data.numel()
-    sk, sizes = _sketch_out(ng, s, indices.device)
+    with _on(stream):
+        sk, sizes = _sketch_out(ng, s, indices.device, out)
     rc = lib().kmc_sketch_from_sequences_grouped(_dptr(data), _dptr(indices), n, int(data_bytes),
                                                  _dptr(group_offsets), ng, k, flags, s, int(seed) & _M64, _dptr(sk),
                                                  _dptr(sizes), *_ws(workspace), _stream(stream))
     _check(rc, "kmc_sketch_from_sequences_grouped")
     if n <= 0:  # the library writes nothing then
-        sk.fill_(-1)
-        sizes.zero_()
+        with _on(stream):
+            sk.fill_(-1)
+            sizes.zero_()
     return sk, sizes
 
 
-def sketch_merge_groups(sketches, sizes, group_offsets, stream=None):
+def sketch_merge_groups(sketches, sizes, group_offsets, out=None, stream=None):
     """Bottom-s of the union of the sketch rows [group_offsets[g], group_offsets[g+1])
     (kmc_sketch_merge_groups) for every group g.  Returns new (sketches int64
     [groups, s], sizes int32 [groups]); the input is left as it is."""
-    sketches = sketches.contiguous()
+    with _on(stream):
+        sketches = sketches.contiguous()
     rows, s = int(sketches.shape[0]), int(sketches.shape[1])
     ng = int(group_offsets.numel() - 1)
-    sk, sz = _sketch_out(ng, s, sketches.device)
+    with _on(stream):
+        sk, sz = _sketch_out(ng, s, sketches.device, out)
     rc = lib().kmc_sketch_merge_groups(_dptr(sketches), _dptr(sizes), rows, _dptr(group_offsets), ng, s, _dptr(sk),
                                        _dptr(sz), _stream(stream))
     _check(rc, "kmc_sketch_merge_groups")
     return sk, sz
 
 
-def sketch_distances(sketches, sizes, k, with_counts=False, stream=None):
+def _dist_out(shape, device, with_counts, out):
+    """Uninitialised (out float32, shared, denom int32 or None, None) of `shape`, or
+    the caller's own triple `out`."""
+    import torch
+    if out is not None:
+        return out
+    return (torch.empty(shape, dtype=torch.float32, device=device),
+            torch.empty(shape, dtype=torch.int32, device=device) if with_counts else None,
+            torch.empty(shape, dtype=torch.int32, device=device) if with_counts else None)
+
+
+def sketch_distances(sketches, sizes, k, with_counts=False, out=None, stream=None):
     """All-pairs Mash distance (kmc_sketch_distances) of sketch rows [n, s] and their
     sizes [n].  Returns float32 [n(n-1)/2], packed upper triangle; with_counts:
     (out, shared, denom), the two integer counts as int32 tensors."""
-    import torch
-    sketches = sketches.contiguous()
-    n, s = int(sketches.shape[0]), int(sketches.shape[1])
-    npairs = max(n * (n - 1) // 2, 0)
-    out = torch.empty(npairs, dtype=torch.float32, device=sketches.device)
-    sh = torch.empty(npairs, dtype=torch.int32, device=sketches.device) if with_counts else None
-    dn = torch.empty(npairs, dtype=torch.int32, device=sketches.device) if with_counts else None
+    with _on(stream):
+        sketches = sketches.contiguous()
+        n, s = int(sketches.shape[0]), int(sketches.shape[1])
+        out, sh, dn = _dist_out(max(n * (n - 1) // 2, 0), sketches.device, with_counts, out)
     rc = lib().kmc_sketch_distances(_dptr(sketches), _dptr(sizes), n, s, k, _dptr(out), _dptr(sh), _dptr(dn),
                                     _stream(stream))
     _check(rc, "kmc_sketch_distances")
@@ -512,24 +558,23 @@ def sketch_distances(sketches, sizes, k, with_counts=False, stream=None):
 NEAREST_MAX_TOP = 1024
 
 
-def _row_sets(q, r):
+def _row_sets(q, r, stream):
     """Contiguous query and reference rows of one sketch size: (q, r, m, n, s)."""
-    q, r = q.contiguous(), r.contiguous()
+    with _on(stream):
+        q, r = q.contiguous(), r.contiguous()
     if int(q.shape[1]) != int(r.shape[1]):
         raise ValueError("query rows of %d values against reference rows of %d" % (q.shape[1], r.shape[1]))
     return q, r, int(q.shape[0]), int(r.shape[0]), int(q.shape[1])
 
 
-def sketch_distances_rect(q, qs, r, rs, k, with_counts=False, stream=None):
+def sketch_distances_rect(q, qs, r, rs, k, with_counts=False, out=None, stream=None):
     """Mash distance of every query row against every reference row
     (kmc_sketch_distances_rect): rows q [m, s] with sizes qs [m], rows r [n, s] with
     sizes rs [n].  Returns float32 [m, n]; with_counts: (out, shared, denom), the
     two integer counts as int32 tensors [m, n]."""
-    import torch
-    q, r, m, n, s = _row_sets(q, r)
-    out = torch.empty((m, n), dtype=torch.float32, device=q.device)
-    sh = torch.empty((m, n), dtype=torch.int32, device=q.device) if with_counts else None
-    dn = torch.empty((m, n), dtype=torch.int32, device=q.device) if with_counts else None
+    q, r, m, n, s = _row_sets(q, r, stream)
+    with _on(stream):
+        out, sh, dn = _dist_out((m, n), q.device, with_counts, out)
     rc = lib().kmc_sketch_distances_rect(_dptr(q), _dptr(qs), m, _dptr(r), _dptr(rs), n, s, k, _dptr(out), _dptr(sh),
                                          _dptr(dn), _stream(stream))
     _check(rc, "kmc_sketch_distances_rect")
@@ -540,21 +585,25 @@ def sketch_nearest_workspace_size(num_queries, num_refs, sketch_size, top, devic
     return int(lib().kmc_sketch_nearest_workspace_size(num_queries, num_refs, sketch_size, top, device))
 
 
-def sketch_nearest(q, qs, r, rs, k, top, min_shared=1, workspace=None, stream=None):
+def sketch_nearest(q, qs, r, rs, k, top, min_shared=1, workspace=None, out=None, stream=None):
     """The `top` nearest reference rows of every query row (kmc_sketch_nearest), by
     Jaccard estimate shared / denom descending, then by reference index; a
     reference takes part with denom > 0 and shared >= min_shared.  Returns (refs,
     shared, denom int32 [m, top], dist float32 [m, top], counts int32 [m]): row q
     holds counts[q] hits, then -1 (UINT32_MAX), 0, 0 and NaN."""
     import torch
-    q, r, m, n, s = _row_sets(q, r)
+    q, r, m, n, s = _row_sets(q, r, stream)
     top = int(top)
     shape = (m, max(top, 0))
-    refs = torch.empty(shape, dtype=torch.int32, device=q.device)
-    sh = torch.empty(shape, dtype=torch.int32, device=q.device)
-    dn = torch.empty(shape, dtype=torch.int32, device=q.device)
-    dist = torch.empty(shape, dtype=torch.float32, device=q.device)
-    counts = torch.empty(m, dtype=torch.int32, device=q.device)
+    if out is not None:
+        refs, sh, dn, dist, counts = out
+    else:
+        with _on(stream):
+            refs = torch.empty(shape, dtype=torch.int32, device=q.device)
+            sh = torch.empty(shape, dtype=torch.int32, device=q.device)
+            dn = torch.empty(shape, dtype=torch.int32, device=q.device)
+            dist = torch.empty(shape, dtype=torch.float32, device=q.device)
+            counts = torch.empty(m, dtype=torch.int32, device=q.device)
     rc = lib().kmc_sketch_nearest(_dptr(q), _dptr(qs), m, _dptr(r), _dptr(rs), n, s, k, top, int(min_shared),
                                   _dptr(refs), _dptr(sh), _dptr(dn), _dptr(dist), _dptr(counts), *_ws(workspace),
                                   _stream(stream))
@@ -656,14 +705,16 @@ def parse_fasta_device(raw, dialect=DIALECT_BLANK, stream=None):
     tensor; returns (data uint8 tensor, indices int64 tensor [n+1]) on its device."""
     import torch
     n = int(raw.numel())
-    if n % 16 or raw.data_ptr() % 16:  # the kernel reads whole 16-byte pieces of raw
-        pad = torch.zeros(n + 16 - n % 16, dtype=torch.uint8, device=raw.device)
-        pad[:n] = raw
-        raw = pad
-    data = torch.empty(n + 16, dtype=torch.uint8, device=raw.device)
+    with _on(stream):
+        if n % 16 or raw.data_ptr() % 16:  # the kernel reads whole 16-byte pieces of raw
+            pad = torch.zeros(n + 16 - n % 16, dtype=torch.uint8, device=raw.device)
+            pad[:n] = raw
+            raw = pad
+        data = torch.empty(n + 16, dtype=torch.uint8, device=raw.device)
     cap = 1024
     while True:
-        idx = torch.empty(cap, dtype=torch.int64, device=raw.device)
+        with _on(stream):
+            idx = torch.empty(cap, dtype=torch.int64, device=raw.device)
         ns, nb = _U64(0), _U64(0)
         rc = lib().kmc_fasta_parse_device(_dptr(raw) if n else None, n, dialect, _dptr(data), n + 16, _dptr(idx),
                                           cap, ctypes.byref(ns), ctypes.byref(nb), _stream(stream))

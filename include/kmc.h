@@ -6,7 +6,10 @@
  * main.cu:290) and its host-side feeders.  Plain C: pointers, sizes and int
  * error codes only (0 = success, hipError_t values pass through, library codes
  * are >= 1000).  Every device entry point is asynchronous on the given stream
- * and never calls exit().
+ * and never calls exit(); the ones that return a size to the host say
+ * "Synchronous" in their own comment (kmc_count_canonical_hash[_ex],
+ * kmc_fasta_parse_device, kmc_fasta_load_device, and kmc_count_multi, which
+ * takes host buffers).
  *
  * Count layout (identical to the reference, kernels.h:142): int32
  * sum[s + ld*code] ("k-mer-major, record-minor"), ld = num_seqs unless stated,
