@@ -2,7 +2,8 @@
 // (kmc_hash.hip: K1, K3a) and the direct sketcher (kmc_sketch_seq.hip): a
 // workgroup's 16-byte chunk range cut into record pieces (for_each_piece), the 48
 // bytes behind a chunk's 16 window starts (chunk_raw) and their 16 canonical keys
-// with the validity mask (chunk_keys).  Device code only.
+// with the validity mask (chunk_keys).  Device code only.  (The dense and radix
+// kernels, k <= 13, walk 1 KiB tiles instead: for_each_tile_piece, kmc_stream.h.)
 //
 // The parameter block P of a kernel supplies
 //   data, idx, n       the bytes (data[p] is byte p), the record offsets, the records

@@ -82,10 +82,12 @@ struct Params {
                              // kmc_dense_status flag): a kmc_status code when the counts are not valid
 };
 
-// Store a kmc_status code in the call's status word (a plain system-scope store:
-// the word may be host-mapped; any nonzero code marks the call failed).
-__device__ __forceinline__ void raise_status(uint32_t *st, uint32_t code) {
-    if (st) __hip_atomic_store(st, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+// The launch geometry: the ranges of the call, or (derive) the records' own.
+template <class Idx>
+__device__ __forceinline__ Geom make_geom(const Params &p) {
+    if (!p.derive) return tile_geom(p);
+    const int64_t lo = rec_off<Idx>(p, 0), hi = rec_off<Idx>(p, p.n);
+    return tile_geom(lo, hi, lo, hi, p.G);
 }
 
 // 1 or 0x10000 from bit `hb` (0/1): one v_mad_u32_u24 (hipcc otherwise emits
@@ -313,47 +315,31 @@ __global__ __launch_bounds__(BLOCK) void count_dense_kernel(Params p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = blockIdx.x;
     const Geom g = make_geom<Idx>(p);
-    const int64_t tb = g.T0 + (int64_t)w * g.tpw;
-    const int64_t te = (tb + g.tpw) < g.T1 ? (tb + g.tpw) : g.T1;
+    const WgRange rng = wg_range(g, w);
     int64_t slot0 = -1, slot1 = -1;
 
-    if (tb < te) {
-        const int64_t R0 = (tb << kTileShift) > g.wl ? (tb << kTileShift) : g.wl;
-        const int64_t R1 = (te << kTileShift) < g.wh ? (te << kTileShift) : g.wh;
+    if (!rng.empty()) {
         int64_t s0 = 0;
         // (round 4: the first record found by one load per thread when n <= BLOCK,
         // the LDS cleared and the slab flushed 16 bytes per lane: the fixed part of a
         // launch, which an 8-way shard's step pays on 1/8 of the work)
+        if (tid == 0) {
+            misc[0] = 0u;
+            misc[3] = 0u;
+            misc[4] = 0u;
+            misc[5] = 0u;
+            misc[7] = 0u;
+        }
         if (p.n <= BLOCK) {
             // last record s with indices[s] <= R0 (records before it end before R0;
             // the offsets are sorted): the number of such records, less one
-            if (tid == 0) {
-                misc[0] = 0u;
-                misc[3] = 0u;
-                misc[4] = 0u;
-                misc[5] = 0u;
-                misc[7] = 0u;
-            }
-            const bool le = tid < p.n && rec_off<Idx>(p, tid) <= R0;
+            const bool le = tid < p.n && rec_off<Idx>(p, tid) <= rng.R0;
             for (int i = tid; i < NW / 4; i += BLOCK) reinterpret_cast<uint4 *>(h)[i] = make_uint4(0u, 0u, 0u, 0u);
             const int cnt = __syncthreads_count(le);
             s0 = cnt > 0 ? cnt - 1 : 0;
         } else {
             if (tid == 0) {
-                // last record s with indices[s] <= R0 (records before it end before R0)
-                int64_t lo = 0, hi = p.n - 1;
-                if (rec_off<Idx>(p, 0) <= R0) {
-                    while (lo < hi) {
-                        const int64_t mid = (lo + hi + 1) >> 1;
-                        if (rec_off<Idx>(p, mid) <= R0) lo = mid;
-                        else hi = mid - 1;
-                    }
-                }
-                misc[0] = 0u;
-                misc[3] = 0u;
-                misc[4] = 0u;
-                misc[5] = 0u;
-                misc[7] = 0u;
+                const int64_t lo = first_record_at<Idx>(p, rng.R0);
                 misc[1] = (uint32_t)lo;
                 misc[2] = (uint32_t)((uint64_t)lo >> 32);
             }
@@ -370,37 +356,24 @@ __global__ __launch_bounds__(BLOCK) void count_dense_kernel(Params p) {
         pc.cap = p.spill_cap;
 
         int npieces = 0;
-        for (int64_t s = s0; s < p.n; ++s) {
-            if (rec_off<Idx>(p, s) >= R1) break;
-            int64_t ca, ce;
-            record_windows<K, Idx>(p, g, s, ca, ce);
-            const int64_t ps = ca > R0 ? ca : R0;
-            const int64_t pe = ce < R1 ? ce : R1;
-            if (ps >= pe) continue;
+        const auto piece = [&](int64_t s, int64_t ps, int64_t pe, bool entire) __attribute__((always_inline)) {
             pc.rec = s;
             // this piece's tiles: k >= 7 in chunks taken by the waves as they go
             // (misc[7]: the chunk counter, zero at the piece's start), k <= 6 in one
             // contiguous run per wave
-            const int64_t tp0 = ps >> kTileShift;
-            const int64_t tp1 = ((pe - 1) >> kTileShift) + 1;
+            const WaveRun wr = wave_run(ps, pe, BLOCK / 64, __builtin_amdgcn_readfirstlane(tid >> 6));
             using Op = DenseOp<K, R, HM, BLOCK>;
             Op op(h, lane, pc);
             if constexpr (K >= 7) {
-                stream_chunks<K, kChunk, Op::kSegChunks>(p.data, tp0, tp1, ps, pe, g.rl, g.rh, lane, &misc[7], op);
+                stream_chunks<K, kChunk, Op::kSegChunks>(p.data, wr.tp0, wr.tp1, ps, pe, g.rl, g.rh, lane, &misc[7], op);
             } else {
-                constexpr int NWAVES = BLOCK / 64;
-                const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-                const int64_t per = (tp1 - tp0 + NWAVES - 1) / NWAVES;
-                const int64_t a0 = tp0 + (int64_t)wave * per;
-                const int64_t a1 = (a0 + per) < tp1 ? (a0 + per) : tp1;
-                stream_tiles<K>(p.data, a0, a1, per, ps, pe, g.rl, g.rh, lane, op);
+                stream_tiles<K>(p.data, wr.a0, wr.a1, wr.per, ps, pe, g.rl, g.rh, lane, op);
             }
             if constexpr (HM == 3) {
                 const uint32_t wsum = wave_sum(op.nwin);
                 if (lane == 0) atomicAdd(&misc[3], wsum);
             }
             __syncthreads();
-            const bool entire = (ps == ca) && (pe == ce);
             int slot = 0;
             if (!entire) {
                 slot = (npieces == 0) ? 0 : 1;
@@ -480,16 +453,17 @@ __global__ __launch_bounds__(BLOCK) void count_dense_kernel(Params p) {
             if (tid == 0) misc[7] = 0u;  // (every wave's last take of this piece is behind the barrier after it)
             __syncthreads();
             ++npieces;
-        }
+        };
+        for_each_tile_piece<K, Idx>(p, g, rng, s0, piece);
     }
     if (tid == 0) {
         p.slot_rec[2 * w] = slot0;
         p.slot_rec[2 * w + 1] = slot1;
         if (p.spill_cnt) {
-            p.spill_cnt[w] = (tb < te) ? misc[0] : 0u;
+            p.spill_cnt[w] = !rng.empty() ? misc[0] : 0u;
             // never expected (spill_cap_for bounds the entries), but a lost entry
             // would be a silent short count: raise the deferred status flag
-            if (tb < te && misc[0] > p.spill_cap) raise_status(p.status, KMC_ERR_CAPACITY);
+            if (!rng.empty() && misc[0] > p.spill_cap) raise_status(p.status, KMC_ERR_CAPACITY);
         }
     }
 }
@@ -545,20 +519,16 @@ __global__ __launch_bounds__(256) void reduce_dense_kernel(Params p) {
         }
     };
     for (int64_t s = blockIdx.y; s < p.n; s += gridDim.y) {
-        int64_t ca, ce;
-        record_windows<K, Idx>(p, g, s, ca, ce);
-        // int32 bins (and invalid counts) of a record with >= 2^31 windows in range
-        // could wrap (the reference's int counters, main.cu:637, never see one)
-        if (blockIdx.x == 0 && tid == 0 && ce - ca >= ((int64_t)1 << 31)) raise_status(p.status, KMC_ERR_RECORD_TOO_LONG);
-        if (ce <= ca) {
+        const Windows rw = windows_in_range<K, Idx>(p, g, s);
+        if (blockIdx.x == 0 && tid == 0) check_record_windows(p.status, rw.count());
+        if (rw.count() == 0) {
             for (int i = tid; i < RW * NH; i += 256) {
                 const int64_t c = c0 + i % RW + (i / RW) * NW;
                 p.sum[s + p.ld * c] = 0;
             }
             continue;
         }
-        const int64_t wf = ((ca >> kTileShift) - g.T0) / g.tpw;
-        const int64_t wlast = (((ce - 1) >> kTileShift) - g.T0) / g.tpw;
+        const int64_t wf = wg_of(g, rw.ca), wlast = wg_of(g, rw.ce - 1);
         bool spills = false;
         if constexpr (P16) {
             uint32_t any = 0u;
@@ -630,10 +600,7 @@ __global__ __launch_bounds__(256) void invalid_kernel(Params p) {
             __syncthreads();
         }
         if (threadIdx.x == 0) {
-            const Geom g = make_geom<Idx>(p);
-            int64_t ca, ce;
-            record_windows<K, Idx>(p, g, s, ca, ce);
-            const int64_t nw = ce > ca ? ce - ca : 0;
+            const int64_t nw = windows_in_range<K, Idx>(p, make_geom<Idx>(p), s).count();
             p.invalid[s] = (int32_t)(nw - red[0]);
         }
         __syncthreads();  // red is reused by the next record
@@ -913,34 +880,13 @@ int run_dense(const Request &q, hipStream_t st) {
 
 template <class Idx>
 int dispatch(int k, const Request &q, hipStream_t st) {
-    switch (k) {
-        case 1: return run_dense<1, Idx>(q, st);
-        case 2: return run_dense<2, Idx>(q, st);
-        case 3: return run_dense<3, Idx>(q, st);
-        case 4: return run_dense<4, Idx>(q, st);
-        case 5: return run_dense<5, Idx>(q, st);
-        case 6: return run_dense<6, Idx>(q, st);
-        case 7: return run_dense<7, Idx>(q, st);
-        case 8: return run_dense<8, Idx>(q, st);
-        default: return KMC_ERR_UNSUPPORTED_K;
-    }
+    return with_k<1, 8>(k, [&](auto kc) { return run_dense<decltype(kc)::value, Idx>(q, st); });
 }
 
 template <class Idx>
 size_t workspace_for(int k, int device, bool derive, int64_t wl, int64_t wh) {
     Plan pl;
-    int e = 0;
-    switch (k) {
-        case 1: e = make_plan<1, Idx>(device, derive, wl, wh, pl); break;
-        case 2: e = make_plan<2, Idx>(device, derive, wl, wh, pl); break;
-        case 3: e = make_plan<3, Idx>(device, derive, wl, wh, pl); break;
-        case 4: e = make_plan<4, Idx>(device, derive, wl, wh, pl); break;
-        case 5: e = make_plan<5, Idx>(device, derive, wl, wh, pl); break;
-        case 6: e = make_plan<6, Idx>(device, derive, wl, wh, pl); break;
-        case 7: e = make_plan<7, Idx>(device, derive, wl, wh, pl); break;
-        case 8: e = make_plan<8, Idx>(device, derive, wl, wh, pl); break;
-        default: return 0;
-    }
+    const int e = with_k<1, 8>(k, [&](auto kc) { return make_plan<decltype(kc)::value, Idx>(device, derive, wl, wh, pl); });
     return e ? 0 : pl.ws_bytes;
 }
 
@@ -1010,10 +956,7 @@ extern "C" size_t kmc_count_dense_ex_workspace_size(const kmc_dense_args *a0, in
     int64_t bias = 0;
     const kmc_dense_args al = aligned_args(a0, bias);
     const kmc_dense_args *a = &al;
-    if (a->k > 8) {
-        size_t sz = 0;
-        return radix_dense(a, bias, nullptr, true, &sz) == 0 ? sz : 0;
-    }
+    if (a->k > 8) return radix_workspace_size(a);
     const int64_t wl = (int64_t)a->win_lo, wh = (int64_t)a->win_hi;
     return workspace_for<int64_t>(a->k, device, false, wl, wh);
 }
@@ -1037,7 +980,7 @@ extern "C" int kmc_count_dense_ex(const kmc_dense_args *a0, hipStream_t stream) 
         if (e) return e;
         al.status = reinterpret_cast<int32_t *>(sd);
     }
-    if (a->k > 8) return radix_dense(a, bias, stream, false, nullptr);
+    if (a->k > 8) return radix_dense(a, bias, stream);
     Request q{};
     q.data = a->data;
     q.ibias = bias;
@@ -1067,8 +1010,7 @@ extern "C" size_t kmc_count_dense_workspace_size(int k, uint64_t num_seqs, uint6
         a.num_seqs = num_seqs;
         a.read_lo = a.win_lo = 15;
         a.read_hi = a.win_hi = data_bytes + 15;
-        size_t sz = 0;
-        return radix_dense(&a, 15, nullptr, true, &sz) == 0 ? sz : 0;
+        return radix_workspace_size(&a);
     }
     return workspace_for<int64_t>(k, device, false, 15, (int64_t)data_bytes + 15);
 }

@@ -22,9 +22,12 @@ extern thread_local hipEvent_t t_trace_before, t_trace_after;
 
 // 9 <= k <= KMC_DENSE_MAX_K: radix-partitioned dense counting (kmc_radix.hip).
 // a->data is 16-byte aligned; ibias is added to every record offset (the caller's
-// misalignment, already added to a's ranges).  size_only: report the workspace size
-// in *size_out instead of launching.
-int radix_dense(const ::kmc_dense_args *a, int64_t ibias, hipStream_t st, bool size_only, size_t *size_out);
+// misalignment, already added to a's ranges).  Both make the same plan (grid, exact
+// or sampled partition, capacities) on the current device; radix_workspace_size lays
+// the workspace out over no base and returns its size (0: no such k, or an error),
+// radix_dense binds the workspace, lays it out and launches on st.
+size_t radix_workspace_size(const ::kmc_dense_args *a);
+int radix_dense(const ::kmc_dense_args *a, int64_t ibias, hipStream_t st);
 
 // splitmix64 output n (0-based) of the stream seeded with `seed` (Steele et al.):
 // z = seed + (n+1)*golden; two xor-shift-multiply rounds; final xor-shift.

@@ -68,18 +68,16 @@ struct RParams {
     int64_t ibias;           // added to every indices[] value (kmc_stream.h rec_off)
     int64_t n;
     int64_t wl, wh, rl, rh;
-    int derive;
     int G;           // workgroups of R1/R3
-    int nbk;         // buckets per record
-    uint32_t *cnt;   // [n][nbk][G] entries of list (s, b) from workgroup w
-    uint64_t *off;   // [n*nbk*G + 1] start of each (s, b, w) region of ent
+    uint32_t *cnt;   // [n][NBK][G] entries of list (s, b) from workgroup w
+    uint64_t *off;   // [n*NBK*G + 1] start of each (s, b, w) region of ent
     uint16_t *ent;   // entries
     uint32_t *stage; // [n][4^k]
     int32_t *sum;
     int64_t ld;
     int32_t *invalid;
     // sampled mode (radix_count_kernel<SAMPLE>): regions sized from a 1-in-16 tile sample
-    uint32_t *capv;      // [n][nbk][G] region capacities (multiples of 32); null: exact offsets
+    uint32_t *capv;      // [n][NBK][G] region capacities (multiples of 32); null: exact offsets
     uint32_t *flag;      // overflow lists full (or capacities beyond ent_cap): exact rerun
     const uint32_t *gate;  // non-null: the kernel runs only if *gate != 0 (the exact rerun)
     uint64_t ent_cap;    // entries ent holds
@@ -89,6 +87,8 @@ struct RParams {
     float cap_scale;     // test hook: capacities scaled (< 1 forces overflows)
     uint32_t *status;    // the call's status word (kmc_dense_args::status, set by kmc_count_dense_ex)
 };
+
+template <int K> constexpr int kNBK = 1 << (2 * K - low_bits(K));  // buckets per record
 
 // A launch of the exact rerun returns at once unless the sampled pass overflowed.
 __device__ __forceinline__ bool gated_off(const RParams &p) {
@@ -161,14 +161,14 @@ __device__ __forceinline__ void sample_tiles(const char *__restrict__ data, int6
     }
 }
 
-// R1: the piece walk of the dense kernel, counting per record piece the windows
+// R1: the tile piece walk (for_each_tile_piece, kmc_stream.h), counting per record piece the windows
 // of each bucket in LDS -> cnt[(s*NBK + b)*G + w].  SAMPLE: the sampled walk
 // (sample_tiles), whose weighted counts estimate the same numbers.
-template <int K, class Idx, bool SAMPLE = false>
+template <int K, bool SAMPLE = false>
 __global__ __launch_bounds__(1024) void radix_count_kernel(RParams p) {
     constexpr int BLOCK = 1024;
     constexpr int NWAVES = BLOCK / 64;
-    constexpr int NBK = 1 << (2 * K - low_bits(K));
+    constexpr int NBK = kNBK<K>;
     __shared__ uint32_t s_cnt[NBK * kCountRep];
     __shared__ int64_t s_first;
 
@@ -176,34 +176,21 @@ __global__ __launch_bounds__(1024) void radix_count_kernel(RParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = blockIdx.x;
     if (gated_off(p)) return;
-    const Geom g = make_geom<Idx>(p);
-    const int64_t tb = g.T0 + (int64_t)w * g.tpw;
-    const int64_t te = (tb + g.tpw) < g.T1 ? (tb + g.tpw) : g.T1;
-    if (tb >= te) return;
-    const int64_t R0 = (tb << kTileShift) > g.wl ? (tb << kTileShift) : g.wl;
-    const int64_t R1 = (te << kTileShift) < g.wh ? (te << kTileShift) : g.wh;
-    if (tid == 0) s_first = first_record_at<Idx>(p, R0);
+    const Geom g = tile_geom(p);
+    const WgRange rng = wg_range(g, w);
+    if (rng.empty()) return;
+    if (tid == 0) s_first = first_record_at<int64_t>(p, rng.R0);
     __syncthreads();
-    for (int64_t s = s_first; s < p.n; ++s) {
-        if (rec_off<Idx>(p, s) >= R1) break;
-        int64_t ca, ce;
-        record_windows<K, Idx>(p, g, s, ca, ce);
-        const int64_t ps = ca > R0 ? ca : R0;
-        const int64_t pe = ce < R1 ? ce : R1;
-        if (ps >= pe) continue;
+    const auto piece = [&](int64_t s, int64_t ps, int64_t pe, bool) __attribute__((always_inline)) {
         const int64_t lbase = (s * NBK) * p.G + w;  // cnt index of (s, b=0, w); stride G per bucket
         for (int i = tid; i < NBK * kCountRep; i += BLOCK) s_cnt[i] = 0u;
         __syncthreads();
-        const int64_t tp0 = ps >> kTileShift;
-        const int64_t tp1 = ((pe - 1) >> kTileShift) + 1;
-        const int64_t per = (tp1 - tp0 + NWAVES - 1) / NWAVES;
-        const int64_t a0 = tp0 + (int64_t)wave * per;
-        const int64_t a1 = (a0 + per) < tp1 ? (a0 + per) : tp1;
+        const WaveRun wr = wave_run(ps, pe, NWAVES, wave);
         RCountOp<K> op{s_cnt + (lane & (kCountRep - 1)), 1u};
         if constexpr (SAMPLE) {
-            sample_tiles<K>(p.data, a0, a1, ps, pe, g.rl, g.rh, lane, (uint32_t)(w * 16 + wave) ^ (uint32_t)s, op);
+            sample_tiles<K>(p.data, wr.a0, wr.a1, ps, pe, g.rl, g.rh, lane, (uint32_t)(w * 16 + wave) ^ (uint32_t)s, op);
         } else {
-            stream_tiles<K, RCountOp<K>, kRCountPF, kRCountNT>(p.data, a0, a1, per, ps, pe, g.rl, g.rh, lane, op);
+            stream_tiles<K, RCountOp<K>, kRCountPF, kRCountNT>(p.data, wr.a0, wr.a1, wr.per, ps, pe, g.rl, g.rh, lane, op);
         }
         __syncthreads();
         for (int b = tid; b < NBK; b += BLOCK) {
@@ -217,7 +204,8 @@ __global__ __launch_bounds__(1024) void radix_count_kernel(RParams p) {
             p.cnt[lbase + (int64_t)b * p.G] = t;
         }
         __syncthreads();
-    }
+    };
+    for_each_tile_piece<K, int64_t>(p, g, rng, s_first, piece);
 }
 
 // Sampled mode: the region capacity of every (s, b, w) from the weighted sample
@@ -226,24 +214,19 @@ __global__ __launch_bounds__(1024) void radix_count_kernel(RParams p) {
 // 64-byte segments: regions stay segment-aligned) and at most the piece's windows;
 // 0 where workgroup w holds no piece of record s (whatever cnt held there).  Clears
 // cnt: R3 writes the fills, an exact rerun's R1 the counts.
-template <int K, class Idx>
+template <int K>
 __global__ __launch_bounds__(256) void radix_cap_kernel(RParams p) {
-    const int64_t m = p.n * p.nbk * p.G;
-    const Geom g = make_geom<Idx>(p);
+    const int64_t m = p.n * kNBK<K> * p.G;
+    const Geom g = tile_geom(p);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) {
-        const int64_t w = i % p.G, s = i / ((int64_t)p.nbk * p.G);
-        const int64_t tb = g.T0 + w * g.tpw;
-        const int64_t te = (tb + g.tpw) < g.T1 ? (tb + g.tpw) : g.T1;
-        int64_t ca, ce;
-        record_windows<K, Idx>(p, g, s, ca, ce);
-        const int64_t R0 = (tb << kTileShift) > g.wl ? (tb << kTileShift) : g.wl;
-        const int64_t R1 = (te << kTileShift) < g.wh ? (te << kTileShift) : g.wh;
-        const int64_t ps = ca > R0 ? ca : R0, pe = ce < R1 ? ce : R1;
+        const int64_t w = i % p.G, s = i / ((int64_t)kNBK<K> * p.G);
+        const WgRange rng = wg_range(g, w);
+        const Piece pc = piece_of<K, int64_t>(p, g, rng, s);
         uint32_t cap = 0u;
-        if (tb < te && ps < pe) {
+        if (!rng.empty() && !pc.empty()) {
             const float c = (float)p.cnt[i];
             const float x = (1.05f * c + 6.0f * sqrtf((float)kSampleStride * c) + 64.0f) * p.cap_scale;
-            const int64_t pmax = (pe - ps + 31) & ~(int64_t)31;
+            const int64_t pmax = (pc.pe - pc.ps + 31) & ~(int64_t)31;
             cap = x >= (float)pmax ? (uint32_t)pmax : (((uint32_t)x + 31u) & ~31u);
         }
         p.capv[i] = cap;
@@ -285,7 +268,7 @@ __global__ __launch_bounds__(256) void radix_cap_kernel(RParams p) {
 template <int K>
 struct RingGeom {
     static constexpr int LOW = low_bits(K);
-    static constexpr int NBK = 1 << (2 * K - LOW);
+    static constexpr int NBK = kNBK<K>;
     static constexpr int BLOCK = 1024;
     static constexpr int TPB = BLOCK / NBK;     // threads per bucket in phase B
     static constexpr int RING = 65536 / NBK;    // entries per bucket ring (128 KB in all)
@@ -547,10 +530,10 @@ struct RRingOp {
     }
 };
 
-// R3 launch: the piece walk of radix_count_kernel with the ring scatter (the whole
+// R3 launch: the same walk as radix_count_kernel with the ring scatter (the whole
 // LDS of a CU: one 1024-thread workgroup per CU).  SAMPLED: into the capacity
 // regions (p.capv), entries past them to the overflow lists (p.ovf).
-template <int K, class Idx, bool SAMPLED>
+template <int K, bool SAMPLED>
 __global__ __launch_bounds__(1024) void radix_ring_kernel(RParams p) {
     using RG = RingGeom<K>;
     constexpr int NWAVES = RG::BLOCK / 64;
@@ -571,25 +554,16 @@ __global__ __launch_bounds__(1024) void radix_ring_kernel(RParams p) {
     }
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = blockIdx.x;
-    const Geom g = make_geom<Idx>(p);
-    const int64_t tb = g.T0 + (int64_t)w * g.tpw;
-    const int64_t te = (tb + g.tpw) < g.T1 ? (tb + g.tpw) : g.T1;
-    if (tb >= te) return;
-    const int64_t R0 = (tb << kTileShift) > g.wl ? (tb << kTileShift) : g.wl;
-    const int64_t R1 = (te << kTileShift) < g.wh ? (te << kTileShift) : g.wh;
+    const Geom g = tile_geom(p);
+    const WgRange rng = wg_range(g, w);
+    if (rng.empty()) return;
     if (tid == 0) {
-        s_first = first_record_at<Idx>(p, R0);
+        s_first = first_record_at<int64_t>(p, rng.R0);
         s_ovf_n = 0u;
     }
     __syncthreads();
     const uint32_t b = (uint32_t)tid / RG::TPB;
-    for (int64_t s = s_first; s < p.n; ++s) {
-        if (rec_off<Idx>(p, s) >= R1) break;
-        int64_t ca, ce;
-        record_windows<K, Idx>(p, g, s, ca, ce);
-        const int64_t ps = ca > R0 ? ca : R0;
-        const int64_t pe = ce < R1 ? ce : R1;
-        if (ps >= pe) continue;
+    const auto piece = [&](int64_t s, int64_t ps, int64_t pe, bool) __attribute__((always_inline)) {
         RRingOp<K, SAMPLED> op;
         op.ring = s_ring;
         op.W = s_W;
@@ -607,15 +581,12 @@ __global__ __launch_bounds__(1024) void radix_ring_kernel(RParams p) {
         op.sbase = (unsigned long long)s << (2 * K);
         op.begin(b, p.off[li], SAMPLED ? p.capv[li] : 0u, (uint32_t)tid % RG::TPB == 0);  // this workgroup's segment of list (s, b)
         __syncthreads();
-        const int64_t tp0 = ps >> kTileShift;
-        const int64_t tp1 = ((pe - 1) >> kTileShift) + 1;
-        const int64_t per = (tp1 - tp0 + NWAVES - 1) / NWAVES;
-        const int64_t a0 = tp0 + (int64_t)wave * per;
-        const int64_t a1 = (a0 + per) < tp1 ? (a0 + per) : tp1;
-        stream_tiles<K, RRingOp<K, SAMPLED>, kRScatPF, 0>(p.data, a0, a1, per, ps, pe, g.rl, g.rh, lane, op);
+        const WaveRun wr = wave_run(ps, pe, NWAVES, wave);
+        stream_tiles<K, RRingOp<K, SAMPLED>, kRScatPF, 0>(p.data, wr.a0, wr.a1, wr.per, ps, pe, g.rl, g.rh, lane, op);
         op.finish(p.cnt + li);
         __syncthreads();
-    }
+    };
+    for_each_tile_piece<K, int64_t>(p, g, rng, s_first, piece);
     if (SAMPLED && tid == 0) {
         p.ovf_cnt[w] = s_ovf_n;
         if (s_ovf_n > p.ovf_cap) __hip_atomic_store(p.flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -804,7 +775,8 @@ __global__ __launch_bounds__(1024) void radix_hist_kernel(RParams p, int64_t nbi
     __shared__ unsigned long long s_rb[REG ? kMaxRegions : 1];
     __shared__ uint32_t s_rn[REG ? kMaxRegions : 1];
     __shared__ uint64_t s_scan[kScanBlock / 64];
-    const int64_t nlists = p.n * p.nbk;
+    constexpr int NBK = kNBK<K>;
+    const int64_t nlists = p.n * NBK;
     // sampled mode: did the exact rerun run (then every region is exact and whole)?
     const bool rerun = REG && __hip_atomic_load(p.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
     // REG: thread t < G holds region t of the next list, loaded one list ahead so
@@ -821,16 +793,10 @@ __global__ __launch_bounds__(1024) void radix_hist_kernel(RParams p, int64_t nbi
     };
     fetch(blockIdx.x);
     bool dirty = true;  // (the list-end pass leaves the bins cleared, but for a recount)
-    for (int64_t list = blockIdx.x; list < nlists; list += gridDim.x) {  // list = s*nbk + b
-        const int64_t s = list / p.nbk, b = list % p.nbk;
-        if (b == 0 && threadIdx.x == 0 && p.status) {  // int32 bins of >= 2^31 windows could wrap
-            const Geom g = make_geom<int64_t>(p);
-            int64_t ca, ce;
-            record_windows<K, int64_t>(p, g, s, ca, ce);
-            if (ce - ca >= ((int64_t)1 << 31))
-                __hip_atomic_store(p.status, (uint32_t)KMC_ERR_RECORD_TOO_LONG, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+    for (int64_t list = blockIdx.x; list < nlists; list += gridDim.x) {  // list = s*NBK + b
+        const int64_t s = list / NBK, b = list % NBK;
+        if (b == 0 && threadIdx.x == 0 && p.status)
+            check_record_windows(p.status, windows_in_range<K, int64_t>(p, tile_geom(p), s).count());
         if (dirty)
             for (int i = threadIdx.x; i < kWords; i += 1024) h[i] = 0u;
         if (threadIdx.x == 0) s_sum = 0ull;
@@ -956,9 +922,9 @@ __global__ __launch_bounds__(256) void radix_place_contig_kernel(RParams p, int6
 
 // invalid[s] = windows in range - sum of the record's bucket counts; records
 // blockIdx.x, blockIdx.x + gridDim.x, ...
-template <int K, class Idx>
+template <int K>
 __global__ __launch_bounds__(256) void radix_invalid_kernel(RParams p) {
-    const int64_t m = (int64_t)p.nbk * p.G;
+    const int64_t m = (int64_t)kNBK<K> * p.G;
     __shared__ uint64_t red[256];
     for (int64_t s = blockIdx.x; s < p.n; s += gridDim.x) {
         uint64_t acc = 0;
@@ -970,10 +936,7 @@ __global__ __launch_bounds__(256) void radix_invalid_kernel(RParams p) {
             __syncthreads();
         }
         if (threadIdx.x == 0) {
-            const Geom g = make_geom<Idx>(p);
-            int64_t ca, ce;
-            record_windows<K, Idx>(p, g, s, ca, ce);
-            const int64_t nw = ce > ca ? ce - ca : 0;
+            const int64_t nw = windows_in_range<K, int64_t>(p, tile_geom(p), s).count();
             p.invalid[s] = (int32_t)(nw - (int64_t)red[0]);
         }
         __syncthreads();
@@ -997,20 +960,31 @@ struct RLayout {
     int64_t m, nscan;
 };
 
-inline RLayout r_layout(void *base, int k, int64_t n, int G, int64_t ent_cap, bool sampled, uint32_t ovf_cap) {
+// Everything decided before a launch.
+struct RadixPlan {
+    int device;
+    int G;             // workgroups of R1/R3: one 16-wave workgroup per CU (fewer open lists than more, smaller groups)
+    bool sampled;
+    int64_t ent_cap;   // entries ent holds
+    uint32_t ovf_cap;  // entries per overflow list
+    int mode;          // kmc_diag_radix_mode, read once with cap_scale
+    float cap_scale;
+};
+
+inline RLayout r_layout(void *base, int k, int64_t n, const RadixPlan &pl) {
     RLayout L;
     const int64_t nbk = (int64_t)1 << (2 * k - low_bits(k));
-    L.m = n * nbk * G;
+    L.m = n * nbk * pl.G;
     L.nscan = (L.m + kScanTile - 1) / kScanTile;
     Carver c(base);
     L.cnt = c.take<uint32_t>((size_t)L.m);
     L.off = c.take<uint64_t>((size_t)(L.m + 1));
     L.bsum = c.take<uint64_t>((size_t)(L.nscan + 1));
-    L.capv = c.take_if<uint32_t>(sampled, (size_t)L.m);
-    L.flag = c.take_if<uint32_t>(sampled, 1);
-    L.ovf_cnt = c.take_if<uint32_t>(sampled, (size_t)G);
-    L.ovf = c.take_if<unsigned long long>(sampled, (size_t)G * ovf_cap);
-    L.ent = c.take<uint16_t>((size_t)ent_cap + 8);
+    L.capv = c.take_if<uint32_t>(pl.sampled, (size_t)L.m);
+    L.flag = c.take_if<uint32_t>(pl.sampled, 1);
+    L.ovf_cnt = c.take_if<uint32_t>(pl.sampled, (size_t)pl.G);
+    L.ovf = c.take_if<unsigned long long>(pl.sampled, (size_t)pl.G * pl.ovf_cap);
+    L.ent = c.take<uint16_t>((size_t)pl.ent_cap + 8);
     L.stage = c.take<uint32_t>((size_t)n * ((size_t)1 << (2 * k)));
     L.total = c.total();
     return L;
@@ -1034,113 +1008,113 @@ constexpr double kSampledMinPerList = 256.0 * 1024.0;
 DeviceCache r_ws;  // library-owned workspace
 
 template <int K>
-int run_radix(const kmc_dense_args *a, int64_t ibias, hipStream_t st, bool size_only, size_t *size_out) {
-    int device = 0;
-    hipError_t he = hipGetDevice(&device);
-    if (he != hipSuccess) return (int)he;
-    int G = 0;  // one 16-wave workgroup per CU: fewer open lists than more, smaller groups
-    int e = device_cus(device, &G);
-    if (e) return e;
+int radix_plan(const kmc_dense_args *a, RadixPlan &pl) {
+    if (int e = current_device_cus(&pl.device, &pl.G)) return e;
     const int64_t wl = (int64_t)a->win_lo, wh = (int64_t)a->win_hi;
     const int64_t tiles = wh > wl ? ((wh + kTile - 1) >> kTileShift) - (wl >> kTileShift) : 0;
-    if (tiles < G) G = tiles > 0 ? (int)tiles : 1;
-    const int64_t n = (int64_t)a->num_seqs;
-    constexpr int64_t NBK = (int64_t)1 << (2 * K - low_bits(K));
-    const double win = wh > wl ? (double)(wh - wl) : 0.0;       // >= valid windows in range
-    const double regions = (double)(G + n) * (double)NBK;       // >= (s, b, w) with a piece
-    int mode;
-    float cap_scale;
+    if (tiles < pl.G) pl.G = tiles > 0 ? (int)tiles : 1;
+    const double n = (double)a->num_seqs;
+    const double win = wh > wl ? (double)(wh - wl) : 0.0;     // >= valid windows in range
+    const double regions = ((double)pl.G + n) * kNBK<K>;      // >= (s, b, w) with a piece
     {
         std::lock_guard<std::mutex> lk(r_mu);
-        mode = g_radix_mode;
-        cap_scale = g_cap_scale;
+        pl.mode = g_radix_mode;
+        pl.cap_scale = g_cap_scale;
     }
-    const bool sampled = G <= kMaxRegions &&
-                         (mode == 2 || (mode == 0 && win >= kSampledMinPerList * (double)n * (double)NBK));
+    pl.sampled = pl.G <= kMaxRegions &&
+                 (pl.mode == 2 || (pl.mode == 0 && win >= kSampledMinPerList * n * kNBK<K>));
     // sampled capacities: sum over regions of 1.05 c + 6 sqrt(16 c) + 64 (+ 31 rounding),
     // c summing to the windows; Cauchy-Schwarz bounds the square roots
-    const int64_t ent_cap = sampled ? (int64_t)(1.05 * win + 95.0 * regions + 6.0 * std::sqrt((double)kSampleStride * win * regions) + 64.0)
-                                    : (int64_t)win;
+    pl.ent_cap = pl.sampled ? (int64_t)(1.05 * win + 95.0 * regions + 6.0 * std::sqrt((double)kSampleStride * win * regions) + 64.0)
+                            : (int64_t)win;
     // overflow lists: 1/32 of the windows in all (past that, the exact rerun)
-    const uint32_t ovf_cap = (uint32_t)std::min<double>(std::max<double>(4096.0, win / 32.0 / G), 1 << 30);
-    const size_t total = r_layout(nullptr, K, n, G, ent_cap, sampled, ovf_cap).total;
-    if (size_only) {
-        *size_out = total;
-        return 0;
-    }
-    void *ws = nullptr;
-    if ((e = bind_workspace(r_ws, device, total, a->workspace, a->workspace_bytes, 0, &ws))) return e;
-    const RLayout L = r_layout(ws, K, n, G, ent_cap, sampled, ovf_cap);
-    RParams p;
+    pl.ovf_cap = (uint32_t)std::min<double>(std::max<double>(4096.0, win / 32.0 / pl.G), 1 << 30);
+    return 0;
+}
+
+// The parameter block of the exact pass, R4, R5 and the invalid kernel.
+RParams exact_params(const kmc_dense_args *a, int64_t ibias, const RadixPlan &pl, const RLayout &L) {
+    RParams p{};  // no capacities, no overflow lists, no gate
     p.data = a->data;
     p.indices = a->indices;
     p.ibias = ibias;
-    p.n = n;
-    p.wl = wl;
-    p.wh = wh;
+    p.n = (int64_t)a->num_seqs;
+    p.wl = (int64_t)a->win_lo;
+    p.wh = (int64_t)a->win_hi;
     p.rl = (int64_t)a->read_lo;
     p.rh = (int64_t)a->read_hi;
-    p.derive = 0;
-    p.G = G;
-    p.nbk = 1 << (2 * K - low_bits(K));
+    p.G = pl.G;
     p.cnt = L.cnt;
     p.off = L.off;
     p.ent = L.ent;
     p.stage = L.stage;
     p.sum = a->sum;
-    p.ld = a->sum_ld ? (int64_t)a->sum_ld : n;
+    p.ld = a->sum_ld ? (int64_t)a->sum_ld : p.n;
     p.invalid = a->invalid;
-    p.capv = nullptr;
-    p.flag = nullptr;
-    p.gate = nullptr;
-    p.ovf = nullptr;
-    p.ovf_cnt = nullptr;
-    p.ovf_cap = 0;
-    p.ent_cap = (uint64_t)ent_cap;
-    p.cap_scale = cap_scale;
+    p.ent_cap = (uint64_t)pl.ent_cap;
+    p.cap_scale = pl.cap_scale;
     p.status = reinterpret_cast<uint32_t *>(a->status);
-    uint64_t *bsum = L.bsum;
-    const int64_t nbins = (int64_t)1 << (2 * K);
-    const unsigned hist_grid = (unsigned)std::min<int64_t>(n * p.nbk, kMaxGridX);
+    return p;
+}
+// The sampled pass: p with the capacity regions, the rerun flag and the overflow lists.
+RParams with_regions(RParams p, const RadixPlan &pl, const RLayout &L) {
+    p.capv = L.capv;
+    p.flag = L.flag;
+    p.ovf = L.ovf;
+    p.ovf_cnt = L.ovf_cnt;
+    p.ovf_cap = pl.ovf_cap;
+    return p;
+}
+// The exact rerun behind a sampled pass: p, running only if *flag was raised.
+RParams gated_by(RParams p, const uint32_t *flag) {
+    p.gate = flag;
+    return p;
+}
 
-    if (t_trace_before) {
-        he = hipEventRecord(t_trace_before, st);
-        if (he != hipSuccess) return (int)he;
-    }
-    if (sampled) {
-        // S1 sample -> capacities -> region starts -> R3 into the regions; if one
-        // overflowed (or they exceed ent_cap) the gated exact path reruns R1 + scan +
-        // R3 on the device (no host sync); R4 reads (off, cnt) regions either way
-        RParams ps = p;
-        ps.capv = L.capv;
-        ps.flag = L.flag;
-        ps.ovf = L.ovf;
-        ps.ovf_cnt = L.ovf_cnt;
-        ps.ovf_cap = ovf_cap;
-        he = hipMemsetAsync(ps.flag, 0, sizeof(uint32_t), st);
-        if (he == hipSuccess) he = hipMemsetAsync(ps.ovf_cnt, 0, (size_t)G * 4, st);
-        if (he != hipSuccess) return (int)he;
-        hipLaunchKernelGGL((radix_count_kernel<K, int64_t, true>), dim3(G), dim3(1024), 0, st, ps);
-        const int64_t cap_blocks = std::min<int64_t>((L.m + 255) / 256, 4096);
-        hipLaunchKernelGGL((radix_cap_kernel<K, int64_t>), dim3((unsigned)(cap_blocks > 0 ? cap_blocks : 1)), dim3(256),
-                           0, st, ps);
-        excl_scan_u32(ps.capv, L.m, bsum, p.off, st);
-        hipLaunchKernelGGL((radix_ring_kernel<K, int64_t, true>), dim3(G), dim3(1024), 0, st, ps);
-        RParams px = p;  // (no capacities, no overflow lists)
-        px.gate = ps.flag;
-        hipLaunchKernelGGL((radix_count_kernel<K, int64_t>), dim3(G), dim3(1024), 0, st, px);
-        excl_scan_u32(p.cnt, L.m, bsum, p.off, st, ps.flag);
-        hipLaunchKernelGGL((radix_ring_kernel<K, int64_t, false>), dim3(G), dim3(1024), 0, st, px);
-        hipLaunchKernelGGL((radix_hist_kernel<K, true>), dim3(hist_grid), dim3(1024), 0, st, ps, nbins);
-        hipLaunchKernelGGL(radix_overflow_kernel, dim3((unsigned)G, 16), dim3(256), 0, st, ps);
-    } else {
-        he = hipMemsetAsync(p.cnt, 0, (size_t)L.m * 4, st);
-        if (he != hipSuccess) return (int)he;
-        hipLaunchKernelGGL((radix_count_kernel<K, int64_t>), dim3(G), dim3(1024), 0, st, p);
-        excl_scan_u32(p.cnt, L.m, bsum, p.off, st);
-        hipLaunchKernelGGL((radix_ring_kernel<K, int64_t, false>), dim3(G), dim3(1024), 0, st, p);
-        hipLaunchKernelGGL((radix_hist_kernel<K, false>), dim3(hist_grid), dim3(1024), 0, st, p, nbins);
-    }
+template <int K> constexpr int64_t kBins = (int64_t)1 << (2 * K);
+template <int K>
+unsigned hist_grid(const RParams &p) {
+    return (unsigned)std::min<int64_t>(p.n * kNBK<K>, kMaxGridX);
+}
+
+// R1 count, R2 scan, R3 scatter, R4 hist.
+template <int K>
+hipError_t launch_exact(const RParams &p, const RLayout &L, hipStream_t st) {
+    const hipError_t he = hipMemsetAsync(p.cnt, 0, (size_t)L.m * 4, st);
+    if (he != hipSuccess) return he;
+    hipLaunchKernelGGL((radix_count_kernel<K>), dim3(p.G), dim3(1024), 0, st, p);
+    excl_scan_u32(p.cnt, L.m, L.bsum, p.off, st);
+    hipLaunchKernelGGL((radix_ring_kernel<K, false>), dim3(p.G), dim3(1024), 0, st, p);
+    hipLaunchKernelGGL((radix_hist_kernel<K, false>), dim3(hist_grid<K>(p)), dim3(1024), 0, st, p, kBins<K>);
+    return hipSuccess;
+}
+
+// S1 sample -> capacities -> region starts -> R3 into the regions; if one
+// overflowed (or they exceed ent_cap) the gated exact path reruns R1 + scan +
+// R3 on the device (no host sync); R4 reads (off, cnt) regions either way
+template <int K>
+hipError_t launch_sampled(const RParams &p, const RadixPlan &pl, const RLayout &L, hipStream_t st) {
+    const RParams ps = with_regions(p, pl, L), px = gated_by(p, L.flag);
+    hipError_t he = hipMemsetAsync(ps.flag, 0, sizeof(uint32_t), st);
+    if (he == hipSuccess) he = hipMemsetAsync(ps.ovf_cnt, 0, (size_t)p.G * 4, st);
+    if (he != hipSuccess) return he;
+    hipLaunchKernelGGL((radix_count_kernel<K, true>), dim3(p.G), dim3(1024), 0, st, ps);
+    const int64_t cap_blocks = std::min<int64_t>((L.m + 255) / 256, 4096);
+    hipLaunchKernelGGL((radix_cap_kernel<K>), dim3((unsigned)(cap_blocks > 0 ? cap_blocks : 1)), dim3(256), 0, st, ps);
+    excl_scan_u32(ps.capv, L.m, L.bsum, p.off, st);
+    hipLaunchKernelGGL((radix_ring_kernel<K, true>), dim3(p.G), dim3(1024), 0, st, ps);
+    hipLaunchKernelGGL((radix_count_kernel<K>), dim3(p.G), dim3(1024), 0, st, px);
+    excl_scan_u32(p.cnt, L.m, L.bsum, p.off, st, ps.flag);
+    hipLaunchKernelGGL((radix_ring_kernel<K, false>), dim3(p.G), dim3(1024), 0, st, px);
+    hipLaunchKernelGGL((radix_hist_kernel<K, true>), dim3(hist_grid<K>(p)), dim3(1024), 0, st, ps, kBins<K>);
+    hipLaunchKernelGGL(radix_overflow_kernel, dim3((unsigned)p.G, 16), dim3(256), 0, st, ps);
+    return hipSuccess;
+}
+
+// R5 place, the trace event behind the pipeline, the invalid counts.
+template <int K>
+hipError_t launch_tail(const RParams &p, hipStream_t st) {
+    const int64_t n = p.n, nbins = kBins<K>;
     if (p.ld == n && n > kPlaceS && n <= kPlaceMaxN) {  // n <= 16: one tile row covers every record
         const int64_t blocks = (nbins * n + kPlaceO - 1) / kPlaceO;
         hipLaunchKernelGGL(radix_place_contig_kernel, dim3((unsigned)std::min<int64_t>(blocks, kMaxGridX)), dim3(256),
@@ -1152,13 +1126,28 @@ int run_radix(const kmc_dense_args *a, int64_t ibias, hipStream_t st, bool size_
                            dim3(256), 0, st, p, nbins);
     }
     if (t_trace_after) {
-        he = hipEventRecord(t_trace_after, st);
-        if (he != hipSuccess) return (int)he;
+        const hipError_t he = hipEventRecord(t_trace_after, st);
+        if (he != hipSuccess) return he;
     }
-    if (a->invalid)
-        hipLaunchKernelGGL((radix_invalid_kernel<K, int64_t>), dim3((unsigned)std::min<int64_t>(n, kMaxGridX)),
-                           dim3(256), 0, st, p);
-    he = hipGetLastError();
+    if (p.invalid)
+        hipLaunchKernelGGL((radix_invalid_kernel<K>), dim3((unsigned)std::min<int64_t>(n, kMaxGridX)), dim3(256), 0, st,
+                           p);
+    return hipGetLastError();
+}
+
+template <int K>
+int run_radix(const kmc_dense_args *a, int64_t ibias, hipStream_t st) {
+    RadixPlan pl;
+    if (int e = radix_plan<K>(a, pl)) return e;
+    const int64_t n = (int64_t)a->num_seqs;
+    void *ws = nullptr;
+    if (int e = bind_workspace(r_ws, pl.device, r_layout(nullptr, K, n, pl).total, a->workspace, a->workspace_bytes, 0, &ws))
+        return e;
+    const RLayout L = r_layout(ws, K, n, pl);
+    const RParams p = exact_params(a, ibias, pl, L);
+    hipError_t he = t_trace_before ? hipEventRecord(t_trace_before, st) : hipSuccess;
+    if (he == hipSuccess) he = pl.sampled ? launch_sampled<K>(p, pl, L, st) : launch_exact<K>(p, L, st);
+    if (he == hipSuccess) he = launch_tail<K>(p, st);
     return (int)he;
 }
 
@@ -1175,16 +1164,15 @@ extern "C" KMC_DIAG_API int kmc_diag_radix_mode(int mode, float cap_scale) {
 }
 #endif
 
-// Entry used by kmc_dense.hip for 9 <= k <= KMC_DENSE_MAX_K.
-int radix_dense(const kmc_dense_args *a, int64_t ibias, hipStream_t st, bool size_only, size_t *size_out) {
-    switch (a->k) {
-        case 9: return run_radix<9>(a, ibias, st, size_only, size_out);
-        case 10: return run_radix<10>(a, ibias, st, size_only, size_out);
-        case 11: return run_radix<11>(a, ibias, st, size_only, size_out);
-        case 12: return run_radix<12>(a, ibias, st, size_only, size_out);
-        case 13: return run_radix<13>(a, ibias, st, size_only, size_out);
-        default: return KMC_ERR_UNSUPPORTED_K;
-    }
+// Entries used by kmc_dense.hip for 9 <= k <= KMC_DENSE_MAX_K.
+size_t radix_workspace_size(const kmc_dense_args *a) {
+    RadixPlan pl;
+    const int e = with_k<9, KMC_DENSE_MAX_K>(a->k, [&](auto k) { return radix_plan<decltype(k)::value>(a, pl); });
+    return e == 0 ? r_layout(nullptr, a->k, (int64_t)a->num_seqs, pl).total : 0;
+}
+
+int radix_dense(const kmc_dense_args *a, int64_t ibias, hipStream_t st) {
+    return with_k<9, KMC_DENSE_MAX_K>(a->k, [&](auto k) { return run_radix<decltype(k)::value>(a, ibias, st); });
 }
 
 }  // namespace kmc

@@ -8,11 +8,16 @@
 // bases, hi = the next 16, W = 16-bit mask of the windows to count (MASKED ==
 // false: all 16).  The functor decides what a window does (LDS histogram add,
 // bucket count, bucket scatter, ...).
+// Also the walk that feeds it in the dense and radix kernels (k <= 13): wg_range,
+// for_each_tile_piece, wave_run.  The canonical counter and the sequence sketcher
+// walk 16-byte chunks instead (for_each_piece, kmc_canon_walk.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "kmc.h"
 
 namespace kmc {
 
@@ -152,11 +157,48 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-// Geometry of a counting launch.  P carries indices, n, derive, wl/wh/rl/rh, G.
+// The tile piece walk of the dense and radix kernels: the counted range [wl, wh) is
+// cut into 1 KiB tiles, workgroup w owns a contiguous tile range (wg_range), visits
+// the pieces of the records that intersect it (for_each_tile_piece) and gives each
+// wave a run of a piece's tiles (wave_run).  The slab reduce, the capacity kernel
+// and R4 find a record's partial results from this geometry alone, so every kernel
+// takes it from here.  P carries indices, ibias, n (tile_geom(p): wl, wh, rl, rh, G).
 struct Geom {
     int64_t wl, wh, rl, rh;
     int64_t T0, T1, tpw;
 };
+
+// Windows [wl, wh) as tiles [T0, T1), tpw per workgroup of G; readable bytes [rl, rh).
+__device__ __forceinline__ Geom tile_geom(int64_t wl, int64_t wh, int64_t rl, int64_t rh, int G) {
+    Geom g{wl, wh, rl, rh, 0, 0, 1};  // (an empty range: no tiles)
+    if (wh > wl) {
+        g.T0 = wl >> kTileShift;
+        g.T1 = (wh + kTile - 1) >> kTileShift;
+        g.tpw = (g.T1 - g.T0 + G - 1) / G;
+    }
+    return g;
+}
+
+// Workgroup w's tiles [tb, te) and the windows [R0, R1) of the counted range in them.
+struct WgRange {
+    int64_t tb, te, R0, R1;
+    __device__ __forceinline__ bool empty() const { return tb >= te; }
+};
+__device__ __forceinline__ WgRange wg_range(const Geom &g, int64_t w) {
+    WgRange r;
+    r.tb = g.T0 + w * g.tpw;
+    r.te = (r.tb + g.tpw) < g.T1 ? (r.tb + g.tpw) : g.T1;
+    r.R0 = (r.tb << kTileShift) > g.wl ? (r.tb << kTileShift) : g.wl;
+    r.R1 = (r.te << kTileShift) < g.wh ? (r.te << kTileShift) : g.wh;
+    return r;
+}
+// Its inverse: the workgroup whose range holds window pos (g.wl <= pos < g.wh).
+__device__ __forceinline__ int64_t wg_of(const Geom &g, int64_t pos) {
+    return ((pos >> kTileShift) - g.T0) / g.tpw;
+}
+
+template <class P>
+__device__ __forceinline__ Geom tile_geom(const P &p) { return tile_geom(p.wl, p.wh, p.rl, p.rh, p.G); }
 
 // Record offset i as a position in p.data: indices[i] + p.ibias (the bias is the
 // misalignment of the caller's data pointer, which the library rounds down to 16
@@ -166,42 +208,42 @@ __device__ __forceinline__ int64_t rec_off(const P &p, int64_t i) {
     return (int64_t)((const Idx *)p.indices)[i] + p.ibias;
 }
 
-template <class Idx, class P>
-__device__ __forceinline__ Geom make_geom(const P &p) {
-    Geom g;
-    if (p.derive) {
-        g.wl = rec_off<Idx>(p, 0);
-        g.wh = rec_off<Idx>(p, p.n);
-        g.rl = g.wl;
-        g.rh = g.wh;
-    } else {
-        g.wl = p.wl;
-        g.wh = p.wh;
-        g.rl = p.rl;
-        g.rh = p.rh;
-    }
-    if (g.wh <= g.wl) {
-        g.T0 = g.T1 = 0;
-        g.tpw = 1;
-    } else {
-        g.T0 = g.wl >> kTileShift;
-        g.T1 = (g.wh + kTile - 1) >> kTileShift;
-        g.tpw = (g.T1 - g.T0 + p.G - 1) / p.G;
-    }
-    return g;
-}
-
 // Window range of record s clipped to the counted range: [ca, ce).
+struct Windows {
+    int64_t ca, ce;
+    __device__ __forceinline__ int64_t count() const { return ce > ca ? ce - ca : 0; }
+};
 template <int K, class Idx, class P>
-__device__ __forceinline__ void record_windows(const P &p, const Geom &g, int64_t s, int64_t &ca,
-                                               int64_t &ce) {
+__device__ __forceinline__ Windows windows_in_range(const P &p, const Geom &g, int64_t s) {
     const int64_t a = rec_off<Idx>(p, s);
     const int64_t e = rec_off<Idx>(p, s + 1);
     const int64_t nw = e - a - K > 0 ? e - a - K : 0;  // kernels.h:133 generalised
-    ca = a > g.wl ? a : g.wl;
-    ce = (a + nw) < g.wh ? (a + nw) : g.wh;
+    return {a > g.wl ? a : g.wl, (a + nw) < g.wh ? (a + nw) : g.wh};
 }
 
+// Store a kmc_status code in the call's status word (a plain system-scope store:
+// the word may be host-mapped; any nonzero code marks the call failed).
+__device__ __forceinline__ void raise_status(uint32_t *st, uint32_t code) {
+    if (st) __hip_atomic_store(st, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// int32 bins (and invalid counts) of a record with >= 2^31 windows in range could
+// wrap (the reference's int counters, main.cu:637, never see one).
+__device__ __forceinline__ void check_record_windows(uint32_t *st, int64_t nw) {
+    if (nw >= ((int64_t)1 << 31)) raise_status(st, (uint32_t)KMC_ERR_RECORD_TOO_LONG);
+}
+
+// Record s's windows clipped to the counted range and, [ps, pe), to a workgroup's.
+struct Piece {
+    Windows rw;
+    int64_t ps, pe;
+    __device__ __forceinline__ bool empty() const { return ps >= pe; }
+    __device__ __forceinline__ bool entire() const { return ps == rw.ca && pe == rw.ce; }
+};
+template <int K, class Idx, class P>
+__device__ __forceinline__ Piece piece_of(const P &p, const Geom &g, const WgRange &r, int64_t s) {
+    const Windows rw = windows_in_range<K, Idx>(p, g, s);
+    return {rw, rw.ca > r.R0 ? rw.ca : r.R0, rw.ce < r.R1 ? rw.ce : r.R1};
+}
 
 // Last record s with indices[s] <= pos (records before it end at or before pos).
 template <class Idx, class P>
@@ -215,6 +257,30 @@ __device__ __forceinline__ int64_t first_record_at(const P &p, int64_t pos) {
         }
     }
     return lo;
+}
+
+// The piece loop of a non-empty range r: f(s, ps, pe, entire), workgroup-uniform,
+// for every non-empty piece in record order from s0 = first_record_at(r.R0) on (the
+// caller's search: the kernels share its barrier with their own set-up).  f may
+// hold barriers and must inline (an always_inline lambda: its captures stay in
+// registers).  Not for_each_piece of kmc_canon_walk.h, which cuts 16-byte chunks.
+template <int K, class Idx, class P, class F>
+__device__ __forceinline__ void for_each_tile_piece(const P &p, const Geom &g, const WgRange &r, int64_t s0, F &&f) {
+    for (int64_t s = s0; s < p.n; ++s) {
+        if (rec_off<Idx>(p, s) >= r.R1) break;
+        const Piece c = piece_of<K, Idx>(p, g, r, s);
+        if (c.empty()) continue;
+        f(s, c.ps, c.pe, c.entire());
+    }
+}
+
+// The tiles [tp0, tp1) of a piece and wave `wave`'s run [a0, a1) of them; per, the
+// longest run, is workgroup-uniform (stream_tiles counts its barriers by it).
+struct WaveRun { int64_t tp0, tp1, per, a0, a1; };
+__device__ __forceinline__ WaveRun wave_run(int64_t ps, int64_t pe, int nwaves, int wave) {
+    const int64_t tp0 = ps >> kTileShift, tp1 = ((pe - 1) >> kTileShift) + 1;
+    const int64_t per = (tp1 - tp0 + nwaves - 1) / nwaves, a0 = tp0 + (int64_t)wave * per;
+    return {tp0, tp1, per, a0, (a0 + per) < tp1 ? (a0 + per) : tp1};
 }
 
 // Prefetch form of load_lane, as a raw buffer load.  The resource covers the

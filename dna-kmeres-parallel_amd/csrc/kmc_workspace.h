@@ -1,7 +1,7 @@
 // kmc_workspace.h — host-side workspace plumbing shared by the .hip translation
 // units (no kernels, no device code): the 256-byte rounding of every layout, the
 // carver that lays a workspace out, the per-device grow-only scratch buffer, the
-// choice between it and a caller's workspace, the cached CU count of a device, and
+// choice between it and a caller's workspace, the dispatch on k, the cached CU count of a device, and
 // the two steps most entry points open with: the current device with its CU count,
 // and a layout sized, bound and laid out (bind_layout).
 #pragma once
@@ -10,6 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "kmc.h"
@@ -84,6 +85,14 @@ inline int bind_workspace(DeviceCache &cache, int device, size_t need, void *cal
     if (align && (reinterpret_cast<uintptr_t>(caller) & (align - 1))) return KMC_ERR_ALIGNMENT;
     *out = caller;
     return 0;
+}
+
+// f(std::integral_constant<int, k>{}) for LO <= k <= HI: the one runtime-to-template
+// dispatch on k of a path; KMC_ERR_UNSUPPORTED_K outside.
+template <int LO, int HI, class F>
+inline int with_k(int k, F &&f) {
+    if constexpr (LO > HI) return KMC_ERR_UNSUPPORTED_K;
+    else return k == LO ? f(std::integral_constant<int, LO>{}) : with_k<LO + 1, HI>(k, f);
 }
 
 // Compute units of `device`, asked of the runtime once per device and process

@@ -757,6 +757,68 @@ def test_first_record_search_at_block_size(kmc, oracle, cuda, k, n):
     np.testing.assert_array_equal(inv.cpu().numpy(), exp_inv)
 
 
+_WALK_CASES = {}  # k -> (data, idx, expected, expected invalid, window, expected of the window): made once, never written
+
+
+def _radix_walk_case(oracle, k, n):
+    if k not in _WALK_CASES:
+        rng = np.random.default_rng(900 + k)
+        lens = rng.integers(0, 9001, size=n)
+        if k == 12:  # 12 records are all the expected matrix allows: two long ones bring the buffer to 0.5 MB
+            lens[5], lens[11] = 250_000, 300_001
+        lens[::7] = 0
+        lens[1:4] = (k - 1, k, k + 1)
+        # records of 1023 bytes (1024 with the terminator) in a row, the first starting on a tile
+        # edge: the record two before (the one before is empty) is stretched up to that edge
+        r, nrun = (64, 4) if n > 64 else (8, 3)
+        lens[r - 2] += -(int(lens[:r].sum()) + r) % 1024
+        lens[r:r + nrun] = 1023
+        data, idx = random_records(rng, lens, 0.002, 0.002, 0.0005)
+        assert idx[r] % 1024 == 0 and (np.diff(idx[r:r + nrun + 1]) == 1024).all()
+        assert 400_000 < data.size < 1_000_000  # roughly 0.5-1 MB: 2-3 tiles per workgroup of a 256-CU device
+        exp, exp_inv = oracle.count_dense(data, idx, k)
+        win = exp_win = None
+        if k == 9:  # a window range that cuts two records of >= 4000 bytes, each in the middle of a tile
+            long_ = np.flatnonzero(lens >= 4000)
+            a, b = long_[1], long_[-2]
+            win = ((((int(idx[a]) >> 10) + 2) << 10) + 512, (((int(idx[b]) >> 10) + 2) << 10) + 300)
+            assert idx[a] < win[0] < idx[a + 1] - k and idx[b] < win[1] < idx[b + 1] - k
+            exp_win = oracle.count_dense(data, idx, k, win=win)
+        _WALK_CASES[k] = (data, idx, exp, exp_inv, win, exp_win)
+    return _WALK_CASES[k]
+
+
+@pytest.mark.parametrize("k,n", [(9, 120), (12, 12)])
+@pytest.mark.parametrize("mode,scale", [(0, 1.0), (2, 1.0), (2, 0.25)])
+def test_radix_piece_walk_at_range_edges(kmc, oracle, cuda, radix_mode, k, n, mode, scale):
+    """The radix twin of test_first_record_search_at_block_size: R1, the capacity
+    kernel, R3 and R4 share one piece walk, here over a 0.5-1 MB buffer, so that a
+    workgroup's range is a few tiles holding several records and records of a few
+    thousand bytes are cut across ranges: random lengths in 0..9000, every seventh
+    record empty, lengths k - 1, k and k + 1, and a run of 1023-byte records whose
+    starts fall on tile and range edges.  k = 9, and k = 12 (R4's 16 low bits); the
+    default partition, the sampled one, and the sampled one overflowing into the gated
+    exact rerun; outputs pre-filled with -1.  At k = 9 also a window range that cuts
+    two records in the middle of a tile."""
+    import torch
+    data, idx, exp, exp_inv, win, exp_win = _radix_walk_case(oracle, k, n)
+    assert radix_mode(mode, scale) == 0
+    d, di = dev(data, cuda), dev(idx, cuda)
+    out = torch.full((1 << (2 * k), n), -1, dtype=torch.int32, device=cuda)
+    inv = torch.full((n,), -1, dtype=torch.int32, device=cuda)
+    kmc.count_dense_ex(kmc.dense_args(d, di, k, out, invalid=inv))
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(out.cpu().numpy(), exp)
+    np.testing.assert_array_equal(inv.cpu().numpy(), exp_inv)
+    if win:
+        out.fill_(-1)
+        inv.fill_(-1)
+        kmc.count_dense_ex(kmc.dense_args(d, di, k, out, read=(win[0], win[1] + k - 1), win=win, invalid=inv))
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(out.cpu().numpy(), exp_win[0])
+        np.testing.assert_array_equal(inv.cpu().numpy(), exp_win[1])
+
+
 @pytest.mark.parametrize("k,n", [(8, 70_000), (9, 65_600)])
 def test_many_short_records(kmc, oracle, cuda, k, n):
     """More records than one grid dimension of the per-record helper kernels can

@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "workspace_sizes.json")
 
-# radix (9 <= k <= 13): run_radix takes sampled mode from kSampledMinPerList * n * NBK
+# radix (9 <= k <= 13): radix_plan takes sampled mode from kSampledMinPerList * n * NBK
 # windows on, NBK = 4^k >> low_bits(k) buckets per record (kmc_radix.hip)
 SAMPLED_MIN_PER_LIST = 256 * 1024
 
