@@ -21,7 +21,9 @@
 // kmc_sketch_from_sequences instead, no canonical count; --per-file: one sketch per input file,
 // kmc_sketch_from_sequences_grouped; --query FILE: the input files are references that FILE's
 // sketches are searched in, kmc_sketch_nearest -> query_results.tsv, or with --top 0
-// kmc_sketch_distances_rect -> query_distances.csv).  GPU only: there is no CPU counting path here.
+// kmc_sketch_distances_rect -> query_distances.csv; --screen FILE: the input files are references
+// looked for among all k-mers of FILE, a read set or metagenome, kmc_sketch_screen_* ->
+// screen_results.tsv).  GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -66,6 +68,7 @@ struct Options {
     long top = 10;        // --top T: hits per query; 0: the whole rectangle
     long min_shared = 1;  // --min-shared M
     bool top_set = false, min_shared_set = false;
+    std::vector<std::string> screen;  // --screen FILE (repeatable): the mixtures the inputs are looked for in
     std::vector<std::string> more_inputs;  // the input files after the first
 };
 
@@ -74,6 +77,7 @@ void usage(FILE *f) {
             "usage: kmc [options] <input.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --per-file [options] <a.fasta> <b.fasta> ...\n"
             "       kmc --canonical --sketch S --sketch-direct --query q.fasta [--top T] [options] <refs.fasta>\n"
+            "       kmc --canonical --sketch S --sketch-direct --screen reads.fasta [--screen ...] [options] <refs.fasta>\n"
             "       kmc synth OUT.fa RECORDS LENGTH [SEED]   (benchmark input, SURVEY.md 8(d))\n"
             "  -k K              k-mer length (default %d, the reference's K); dense path 1..%d,\n"
             "                    --canonical 1..%d\n"
@@ -124,6 +128,17 @@ void usage(FILE *f) {
             "                    one distance per line, to <out>/query_distances.csv\n"
             "  --min-shared M    with --query: only references that share at least M sketch values with\n"
             "                    the query are hits (default 1; 0: unrelated references too, at distance 1)\n"
+            "  --screen FILE     with --canonical --sketch S --sketch-direct, may be repeated, not with --query:\n"
+            "                    the input file(s) are the references, sketched as without it (per record,\n"
+            "                    or per file with --per-file); every FILE is a mixture (a read set, a\n"
+            "                    metagenome) read whole (--max-seqs 0), and the hashes of ALL its k-mers are\n"
+            "                    looked up among the references' sketch values (kmc_sketch_screen_build,\n"
+            "                    _count once per FILE into one index, _results): containment, which a sketch\n"
+            "                    of the mixture cannot give.  <out>/screen_results.tsv gets one line per\n"
+            "                    reference, in reference order: index<TAB>shared<TAB>size<TAB>median<TAB>identity\n"
+            "                    (shared: sketch values found; median: their median multiplicity; identity:\n"
+            "                    (shared/size)^(1/k)), and <TAB>path with --per-file; sketch_results.csv is\n"
+            "                    not written\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
@@ -185,6 +200,8 @@ int parse(int argc, char **argv, Options &o) {
                 return fprintf(stderr, "kmc: --min-count out of range\n"), 2;
         } else if (a == "--query") {
             o.query = next("--query");
+        } else if (a == "--screen") {
+            o.screen.push_back(next("--screen"));
         } else if (a == "--top") {
             o.top = atol(next("--top"));
             o.top_set = true;
@@ -234,6 +251,14 @@ int parse(int argc, char **argv, Options &o) {
     if (o.per_file && !o.max_seqs_set) o.max_seqs = 0;
     if (!o.query.empty() && !(o.canonical && o.sketch > 0 && o.sketch_direct)) {
         fprintf(stderr, "kmc: --query needs --canonical --sketch S --sketch-direct\n");
+        return usage(stderr), 2;
+    }
+    if (!o.screen.empty() && !(o.canonical && o.sketch > 0 && o.sketch_direct)) {
+        fprintf(stderr, "kmc: --screen needs --canonical --sketch S --sketch-direct\n");
+        return usage(stderr), 2;
+    }
+    if (!o.screen.empty() && !o.query.empty()) {
+        fprintf(stderr, "kmc: --screen and --query exclude each other\n");
         return usage(stderr), 2;
     }
     if ((o.top_set || o.min_shared_set) && o.query.empty()) {
@@ -572,6 +597,75 @@ int run_query(const Options &o, hipStream_t st) {
     return fclose(f) == 0 ? 0 : 1;
 }
 
+// --screen FILE ...: the inputs are the references; every FILE's k-mers are counted into one
+// index of the references' sketch values, one file resident at a time
+int run_screen(const Options &o, hipStream_t st) {
+    std::vector<std::string> files{o.input};
+    files.insert(files.end(), o.more_inputs.begin(), o.more_inputs.end());
+    const uint32_t s = (uint32_t)o.sketch;
+    const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
+    Rows R;
+    if (int e = make_rows(o, files, "Reference", true, st, R)) return e;
+    const uint64_t n = R.n;
+    const size_t index_bytes = kmc_sketch_screen_index_size(n, s);
+    if (index_bytes == 0) return fprintf(stderr, "kmc: too many reference sketch values for one screen index\n"), 1;
+    DevBuf<char> d_index;
+    DevBuf<uint32_t> d_sh, d_med;
+    DevBuf<float> d_id;
+    Event b0 = make_event(), b1 = make_event(), c0 = make_event(), c1 = make_event(), r1 = make_event();
+    HIPCHK(dev_alloc(d_index, index_bytes));
+    HIPCHK(dev_alloc(d_sh, n));
+    HIPCHK(dev_alloc(d_med, n));
+    HIPCHK(dev_alloc(d_id, n));
+    HIPCHK(hipEventRecord(b0.get(), st));
+    KMCCHK(kmc_sketch_screen_build(R.sk.get(), R.sz.get(), n, s, d_index.get(), index_bytes, st));
+    HIPCHK(hipEventRecord(b1.get(), st));
+    HIPCHK(hipEventSynchronize(b1.get()));
+    if (!o.quiet)
+        printf("Screen index (%" PRIu64 " references, s=%u, %zu bytes): %.3f ms\n", n, s, index_bytes,
+               ms_between(b0.get(), b1.get()));
+    for (const std::string &path : o.screen) {
+        Options of = o;
+        of.input = path;
+        of.max_seqs = 0;
+        of.host_loader = false;
+        of.quiet = true;
+        Records r;
+        if (int e = load(of, st, r)) return e;
+        HIPCHK(hipEventRecord(c0.get(), st));
+        KMCCHK(kmc_sketch_screen_count(d_index.get(), index_bytes, r.data.get(), r.idx.get(), r.n, r.bytes, o.k, flags,
+                                       KMC_SKETCH_DEFAULT_SEED, st));
+        HIPCHK(hipEventRecord(c1.get(), st));
+        HIPCHK(hipStreamSynchronize(st));  // before the file's buffers go
+        if (!o.quiet)
+            printf("Screen: %s: %" PRIu64 " records, %" PRIu64 " bytes: %.3f ms\n", path.c_str(), r.n, r.bytes,
+                   ms_between(c0.get(), c1.get()));
+    }
+    HIPCHK(hipEventRecord(c1.get(), st));
+    KMCCHK(kmc_sketch_screen_results(d_index.get(), index_bytes, R.sk.get(), R.sz.get(), n, s, o.k, d_sh.get(),
+                                     d_med.get(), d_id.get(), st));
+    HIPCHK(hipEventRecord(r1.get(), st));
+    HIPCHK(hipEventSynchronize(r1.get()));
+    if (!o.quiet) printf("Screen results: %.3f ms\n", ms_between(c1.get(), r1.get()));
+    std::vector<uint32_t> sh(n), med(n), sz(n);
+    std::vector<float> ident(n);
+    if (n > 0) {
+        HIPCHK(hipMemcpy(sh.data(), d_sh.get(), n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(med.data(), d_med.get(), n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(sz.data(), R.sz.get(), n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ident.data(), d_id.get(), n * 4, hipMemcpyDeviceToHost));
+    }
+    const std::string path = o.out_dir + "/screen_results.tsv";
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return fprintf(stderr, "kmc: cannot write %s\n", path.c_str()), 1;
+    for (uint64_t r = 0; r < n; ++r) {
+        fprintf(f, "%" PRIu64 "\t%u\t%u\t%u\t%f", r, sh[r], std::min(sz[r], s), med[r], ident[r]);
+        if (o.per_file) fprintf(f, "\t%s", files[r].c_str());
+        fputc('\n', f);
+    }
+    return fclose(f) == 0 ? 0 : 1;
+}
+
 // --canonical: the sparse counts, then their dump, step 2 on them and their sketches
 int run_canonical(const Options &o, const Records &r, hipStream_t st) {
     const int k = o.k;
@@ -722,6 +816,7 @@ int run(const Options &o) {
     HIPCHK(hipStreamCreate(&s));
     const Stream st(s);
     if (!o.query.empty()) return run_query(o, s);
+    if (!o.screen.empty()) return run_screen(o, s);
     if (o.per_file) return run_per_file(o, s);
     Records r;  // (after the stream: released before it)
     if (int e = load(o, s, r)) return e;

@@ -1,0 +1,456 @@
+// kmc_sketch_screen.hip — containment of reference sketches in a sequence set (what Mash
+// calls a screen): for every reference row, how many of its values occur among the
+// hashes of ALL valid windows of a mixture, and how often.  Four steps, three of them
+// on the device, all asynchronous with no host read-back; the launches depend on the
+// host arguments only; no library-owned buffer (the index is the caller's).
+//
+// The index (an opaque blob of kmc_sketch_screen_index_size bytes):
+//   header  256 B   maxv      the largest indexed value other than UINT64_MAX
+//                   has_ff    UINT64_MAX is an indexed value (it is the empty marker of
+//                             the slots, so it lives here), ff_mult its multiplicity
+//                   log2cap   the slot count C = 2^log2cap as build laid it out
+//   mult    uint32[C]  the multiplicity of the value in the same slot
+//   slots   uint64[C]  open addressing, linear probing, the slot of v is the low
+//                      log2cap bits of v (sketch values are the smallest hashes of a
+//                      set: their low bits are the mixed ones); UINT64_MAX: empty
+// C is a power of two of at least kRoom * num_refs * sketch_size slots, so a probe
+// chain always ends at an empty slot.
+//
+//   build   the blob is cleared (two memsets: header and mult to 0, slots to
+//           UINT64_MAX; nothing a former use left is read), then one thread per row
+//           value inserts it with a 64-bit compare-and-swap: equal values of several
+//           rows meet in one slot.  The largest value goes through an LDS maximum per
+//           workgroup into one 64-bit atomic maximum.
+//   count   the sketcher's walk (kmc_canon_walk.h: for_each_piece, chunk_raw,
+//           chunk_keys with the hash functor) over the same ranges of the same launch
+//           shape (kmc_sketch_walk.h), with no per-record state, no LDS set, no
+//           barrier inside a piece and no cut merge: a record matters only for which
+//           windows exist.  A window's hash h leaves after one compare when h > maxv
+//           (reference rows are bottom-s sets: almost every window of a mixture);
+//           the others probe the table and add to the multiplicity with a vector
+//           global atomic (no return value).  A thread adds once per run of equal
+//           hashes among its 16 windows (a homopolymer run is one add of 16, not 16).
+//           The offsets are clamped to [0, data_bytes] and moved by data & 15 as they
+//           are read (Offsets), so the call needs no workspace.
+//   results one workgroup per reference row: each value is looked up, the found
+//           multiplicities (as 64-bit words, absent values as UINT64_MAX) are sorted
+//           in LDS (bitonic_sort of kmc_sketch_pair.h) and the lower median is taken.
+//
+// The device code trusts nothing in the blob: count and results read log2cap, check
+// that the layout of that many slots fits index_bytes and return otherwise; every
+// slot index is masked to the table and a probe chain is left after C steps, so a
+// blob that was never built gives an unspecified result and no stray access or hang.
+//
+// Constants, shipped / under -DKMC_DIAG_HOOKS (no new symbol):
+//   kBlock, kMinChunks, kWgPerCu   the sketcher's (kmc_sketch_walk.h): 64-thread
+//                                  workgroups and 256-byte ranges in the diag build
+//   kRoom   slots per indexed value, at least    4 / 2  (the diag table is only just
+//           large enough: chains are long and wrap round the table's end)
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "kmc.h"
+#include "kmc_canon_walk.h"
+#include "kmc_internal.h"
+#include "kmc_sketch_pair.h"
+#include "kmc_sketch_walk.h"
+#include "kmc_workspace.h"
+
+namespace kmc {
+namespace {
+
+#ifdef KMC_DIAG_HOOKS
+constexpr uint64_t kRoom = 2;
+#else
+constexpr uint64_t kRoom = 4;
+#endif
+constexpr uint64_t kMinSlots = 8;
+constexpr uint32_t kMaxLog2Cap = 32;  // KMC_SCREEN_MAX_VALUES * 4 slots
+constexpr size_t kHeaderBytes = 256;
+constexpr int kBuildBlock = 256;
+
+struct Header {
+    unsigned long long maxv;
+    uint32_t has_ff, ff_mult;
+    uint32_t log2cap;
+};
+static_assert(sizeof(Header) <= kHeaderBytes, "the header has its 256 bytes");
+
+// the one layout: header, mult[C], slots[C], each rounded up to 256 bytes
+__host__ __device__ inline size_t slots_offset(uint64_t cap) { return kHeaderBytes + (((size_t)cap * 4 + 255) & ~(size_t)255); }
+__host__ __device__ inline size_t layout_bytes(uint64_t cap) { return slots_offset(cap) + (size_t)cap * 8; }
+
+inline uint32_t log2cap_of(uint64_t num_refs, uint32_t sketch_size) {
+    const uint64_t want = kRoom * num_refs * sketch_size;
+    uint32_t lg = 3;  // kMinSlots
+    while ((1ull << lg) < want) ++lg;
+    return lg;
+}
+static_assert(kMinSlots == 8, "log2cap_of starts at 2^3 slots");
+
+inline bool screen_rows_ok(uint64_t num_refs, uint32_t sketch_size) {
+    return sketch_size_ok(sketch_size) && num_refs <= KMC_SCREEN_MAX_VALUES &&
+           num_refs * sketch_size <= KMC_SCREEN_MAX_VALUES;
+}
+
+// The table as the device sees it; ok: the header's slot count fits the blob.
+struct Table {
+    Header *hd;
+    uint32_t *mult;
+    unsigned long long *slots;
+    uint64_t cap;
+    uint32_t mask;
+    bool ok;
+};
+
+__device__ __forceinline__ Table open_table(void *index, uint64_t index_bytes) {
+    Table T;
+    T.hd = static_cast<Header *>(index);
+    const uint32_t lg = T.hd->log2cap;
+    T.ok = lg >= 3 && lg <= kMaxLog2Cap;
+    T.cap = 1ull << (T.ok ? lg : 3);
+    T.ok = T.ok && layout_bytes(T.cap) <= index_bytes;
+    T.mask = (uint32_t)(T.cap - 1);
+    T.mult = reinterpret_cast<uint32_t *>(static_cast<char *>(index) + kHeaderBytes);
+    T.slots = reinterpret_cast<unsigned long long *>(static_cast<char *>(index) + slots_offset(T.cap));
+    return T;
+}
+
+// Where the multiplicity of v is kept, or null when v is not indexed.
+__device__ __forceinline__ uint32_t *find(const Table &T, uint64_t v, bool has_ff) {
+    if (v == kFill) return has_ff ? &T.hd->ff_mult : nullptr;
+    uint32_t i = (uint32_t)v & T.mask;
+    for (uint64_t step = 0; step < T.cap; ++step) {  // (guard: a table with no empty slot)
+        const uint64_t x = T.slots[i];
+        if (x == v) return T.mult + i;
+        if (x == kFill) return nullptr;
+        i = (i + 1) & T.mask;
+    }
+    return nullptr;
+}
+
+// ---------------------------------------------------------------------------
+// build
+// ---------------------------------------------------------------------------
+struct BArgs {
+    const uint64_t *rows;
+    const uint32_t *sizes;
+    int64_t n;
+    uint32_t s, log2cap;
+    void *index;
+};
+
+__global__ __launch_bounds__(kBuildBlock) void screen_build_kernel(BArgs a) {
+    __shared__ unsigned long long s_max;
+    __shared__ uint32_t s_ff;
+    Header *hd = static_cast<Header *>(a.index);
+    if (threadIdx.x == 0) {
+        s_max = 0ull;
+        s_ff = 0u;
+        if (blockIdx.x == 0) hd->log2cap = a.log2cap;
+    }
+    __syncthreads();
+    const uint64_t cap = 1ull << a.log2cap;
+    const uint32_t mask = (uint32_t)(cap - 1);
+    unsigned long long *slots = reinterpret_cast<unsigned long long *>(static_cast<char *>(a.index) + slots_offset(cap));
+    const int64_t total = a.n * (int64_t)a.s;
+    unsigned long long mx = 0ull;
+    bool any = false, ff = false;
+    for (int64_t e = (int64_t)blockIdx.x * kBuildBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBuildBlock) {
+        const int64_t r = e / a.s;
+        const int i = (int)(e - r * a.s);
+        if (i >= row_size(a.sizes, r, (int)a.s)) continue;
+        const unsigned long long v = a.rows[e];
+        if (v == kFill) {
+            ff = true;
+            continue;
+        }
+        any = true;
+        mx = v > mx ? v : mx;
+        uint32_t at = (uint32_t)v & mask;
+        for (uint64_t step = 0; step < cap; ++step) {  // (guard; cap >= 2 x the values: an empty slot exists)
+            const unsigned long long was = atomicCAS(slots + at, (unsigned long long)kFill, v);
+            if (was == kFill || was == v) break;
+            at = (at + 1) & mask;
+        }
+    }
+    if (any) atomicMax(&s_max, mx);
+    if (ff) s_ff = 1u;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_max) atomicMax(&hd->maxv, s_max);
+        if (s_ff) hd->has_ff = 1u;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// count
+// ---------------------------------------------------------------------------
+// record offsets as kmc_sketch_from_sequences' prep writes them, computed as they are
+// read: clamp(indices[r], 0, data_bytes) + (data & 15)
+struct Offsets {
+    const int64_t *p;
+    int64_t bytes, mis;
+    __device__ __forceinline__ int64_t operator[](int64_t r) const {
+        const int64_t x = p[r];
+        return (x < 0 ? 0 : (x > bytes ? bytes : x)) + mis;
+    }
+};
+using Walk = WalkOf<Offsets>;
+
+struct CArgs {
+    const char *data;  // rounded down to 16 bytes
+    Offsets idx;
+    int64_t n;
+    int k;
+    uint32_t flags;
+    int G;
+    uint64_t seed;
+    void *index;
+    uint64_t index_bytes;
+};
+
+__device__ __forceinline__ Walk make_walk(const CArgs &a) {
+    Walk W;
+    W.data = a.data;
+    W.idx = a.idx;
+    W.n = a.n;
+    W.lo = a.idx[0];
+    W.hi = a.idx[a.n];
+    if (W.hi < W.lo) W.hi = W.lo;
+    W.k = a.k;
+    W.flags = a.flags;
+    W.c_lo = W.lo >> 4;
+    const int64_t chunks = W.hi > W.lo ? ((W.hi + 15) >> 4) - W.c_lo : 0;
+    const int64_t cpw = (chunks + a.G - 1) / a.G;
+    W.cpw = cpw > 1 ? cpw : 1;
+    return W;
+}
+
+// The windows of record piece [ps, pe): every hash at or below maxv (or UINT64_MAX,
+// when that is indexed) is looked up and counted.
+template <bool FWD, bool BIGK>
+__device__ __forceinline__ void count_piece(const Table &T, uint64_t maxv, bool has_ff, const Walk &W, const HashOf hf,
+                                            int64_t ps, int64_t pe, int64_t rend) {
+    const int tid = threadIdx.x;
+    const int64_t c0 = ps >> 4, c1 = ((pe - 1) >> 4) + 1;
+    ChunkRaw nx = chunk_raw(W, (c0 + tid) << 4);
+    for (int64_t cb = c0; cb < c1; cb += kBlock) {
+        const int64_t c = cb + tid;
+        unsigned long long h[16];
+        const ChunkRaw cr = nx;
+        nx = chunk_raw(W, (c + kBlock) << 4);  // next round's chunk
+        uint32_t pend = chunk_keys<FWD, BIGK>(W, cr, c << 4, ps, pe, rend, hf, h);  // (past the piece: 0)
+        uint32_t cm = 0u;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) cm |= (uint32_t)(h[j] <= maxv) << j;
+        if (has_ff) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) cm |= (uint32_t)(h[j] == kFill) << j;
+        }
+        pend &= cm;
+        if (pend == 0u) continue;
+        uint64_t last = 0;
+        uint32_t *at = nullptr;
+        uint32_t run = 0u;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            if (!((pend >> j) & 1u)) continue;
+            if (run && h[j] == last) {
+                ++run;
+                continue;
+            }
+            if (run && at) __hip_atomic_fetch_add(at, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            last = h[j];
+            at = find(T, last, has_ff);
+            run = 1u;
+        }
+        if (run && at) __hip_atomic_fetch_add(at, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+template <bool FWD, bool BIGK>
+__global__ __launch_bounds__(kBlock) void screen_count_kernel(CArgs a) {
+    __shared__ int64_t s_first;
+    const Table T = open_table(a.index, a.index_bytes);
+    if (!T.ok) return;
+    const uint64_t maxv = T.hd->maxv;
+    const bool has_ff = T.hd->has_ff != 0u;
+    const Walk W = make_walk(a);
+    const HashOf hf{a.seed};
+    for_each_piece(W, &s_first, [&](int64_t, int64_t ps, int64_t pe, int64_t rend) {
+        count_piece<FWD, BIGK>(T, maxv, has_ff, W, hf, ps, pe, rend);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// results
+// ---------------------------------------------------------------------------
+struct RArgs {
+    void *index;  // (read only)
+    uint64_t index_bytes;
+    const uint64_t *rows;
+    const uint32_t *sizes;
+    int64_t n;
+    uint32_t s;
+    int k;
+    uint32_t *shared, *median;
+    float *identity;
+};
+
+__device__ __forceinline__ float containment_identity(uint32_t shared, uint32_t size, int k) {
+    if (size == 0) return __uint_as_float(0x7fc00000u);
+    if (shared == 0) return 0.0f;
+    if (shared == size) return 1.0f;
+    return (float)pow((double)shared / (double)size, 1.0 / (double)k);
+}
+
+template <int CAP>
+__global__ __launch_bounds__(kBlock) void screen_results_kernel(RArgs a) {
+    __shared__ uint64_t buf[CAP];  // the multiplicities of the row's values, UINT64_MAX: absent
+    __shared__ uint32_t s_shared;
+    const Table T = open_table(a.index, a.index_bytes);
+    const bool has_ff = T.ok && T.hd->has_ff != 0u;
+    const int tid = threadIdx.x, s = (int)a.s;
+    for (int64_t r = blockIdx.x; r < a.n; r += gridDim.x) {
+        const int n = row_size(a.sizes, r, s);
+        const int P = n > 2 ? pow2_at_least(n) : 2;  // <= CAP
+        const uint64_t *row = a.rows + r * (int64_t)s;
+        if (tid == 0) s_shared = 0u;
+        __syncthreads();  // (and the last row's readers of buf are done)
+        uint32_t found = 0u;
+        for (int i = tid; i < P; i += kBlock) {
+            uint64_t m = kFill;
+            if (i < n && T.ok) {
+                const uint32_t *at = find(T, row[i], has_ff);
+                const uint32_t c = at ? *at : 0u;
+                if (c) {
+                    m = c;
+                    ++found;
+                }
+            }
+            buf[i] = m;
+        }
+        if (found) atomicAdd(&s_shared, found);
+        __syncthreads();
+        const uint32_t shared = s_shared;
+        uint32_t med = 0u;
+        if (a.median) {  // (uniform)
+            bitonic_sort<kBlock>(buf, 1, P, tid, [] { __syncthreads(); });
+            if (shared) med = (uint32_t)buf[(shared - 1) / 2];
+        }
+        if (tid == 0) {
+            a.shared[r] = shared;
+            if (a.median) a.median[r] = med;
+            if (a.identity) a.identity[r] = containment_identity(shared, (uint32_t)n, a.k);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------
+// what the three device calls ask of the blob, in this order; `need`: the bytes it must hold
+inline int index_check(const void *index, size_t index_bytes, size_t need) {
+    if (!index) return KMC_ERR_INVALID_ARG;
+    if (index_bytes < need) return KMC_ERR_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(index) & 255u) return KMC_ERR_ALIGNMENT;
+    return KMC_OK;
+}
+
+}  // namespace
+}  // namespace kmc
+
+using namespace kmc;
+
+extern "C" size_t kmc_sketch_screen_index_size(uint64_t num_refs, uint32_t sketch_size) {
+    if (!screen_rows_ok(num_refs, sketch_size)) return 0;
+    return layout_bytes(1ull << log2cap_of(num_refs, sketch_size));
+}
+
+extern "C" int kmc_sketch_screen_build(const uint64_t *r_sketches, const uint32_t *r_sizes, uint64_t num_refs,
+                                       uint32_t sketch_size, void *index, size_t index_bytes, hipStream_t stream) {
+    if (!screen_rows_ok(num_refs, sketch_size)) return KMC_ERR_INVALID_ARG;
+    if (num_refs == 0 && !index) return KMC_OK;
+    if (num_refs > 0 && (!r_sketches || !r_sizes)) return KMC_ERR_INVALID_ARG;
+    const uint32_t lg = log2cap_of(num_refs, sketch_size);
+    const uint64_t cap = 1ull << lg;
+    if (int e = index_check(index, index_bytes, layout_bytes(cap))) return e;
+    char *base = static_cast<char *>(index);
+    if (hipError_t he = hipMemsetAsync(base, 0, slots_offset(cap), stream)) return (int)he;
+    if (hipError_t he = hipMemsetAsync(base + slots_offset(cap), 0xFF, (size_t)cap * 8, stream)) return (int)he;
+    BArgs a;
+    a.rows = r_sketches;
+    a.sizes = r_sizes;
+    a.n = (int64_t)num_refs;
+    a.s = sketch_size;
+    a.log2cap = lg;
+    a.index = index;
+    const int64_t blocks = ceil_div(a.n * (int64_t)a.s, kBuildBlock);
+    const unsigned grid = (unsigned)(blocks < 1 ? 1 : (blocks < kMaxGridX ? blocks : kMaxGridX));
+    hipLaunchKernelGGL(screen_build_kernel, dim3(grid), dim3(kBuildBlock), 0, stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int kmc_sketch_screen_count(void *index, size_t index_bytes, const char *data, const int64_t *indices,
+                                       uint64_t num_seqs, uint64_t data_bytes, int k, unsigned flags, uint64_t seed,
+                                       hipStream_t stream) {
+    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
+    if (num_seqs > kMaxSeqs || data_bytes >= (1ull << 62)) return KMC_ERR_INVALID_ARG;
+    if (flags & ~(KMC_CANON_SOFTMASK | KMC_CANON_FORWARD)) return KMC_ERR_INVALID_ARG;
+    if (num_seqs == 0) return KMC_OK;
+    if (!indices || (data_bytes > 0 && !data)) return KMC_ERR_INVALID_ARG;
+    if (int e = index_check(index, index_bytes, layout_bytes(kMinSlots))) return e;
+    int device = 0, cus = 0;
+    if (int e = current_device_cus(&device, &cus)) return e;
+    // any `data` pointer: rounded down to 16 bytes, every offset moved up by the difference
+    const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
+    CArgs a;
+    a.data = data - mis;
+    a.idx = Offsets{indices, (int64_t)data_bytes, (int64_t)mis};
+    a.n = (int64_t)num_seqs;
+    a.k = k;
+    a.flags = flags;
+    a.G = walk_groups(data_bytes, cus);
+    a.seed = seed;
+    a.index = index;
+    a.index_bytes = index_bytes;
+    const bool fwd = flags & KMC_CANON_FORWARD, big = k >= 16;
+    const dim3 g((unsigned)a.G), b(kBlock);
+    if (fwd) {
+        if (big) hipLaunchKernelGGL((screen_count_kernel<true, true>), g, b, 0, stream, a);
+        else hipLaunchKernelGGL((screen_count_kernel<true, false>), g, b, 0, stream, a);
+    } else {
+        if (big) hipLaunchKernelGGL((screen_count_kernel<false, true>), g, b, 0, stream, a);
+        else hipLaunchKernelGGL((screen_count_kernel<false, false>), g, b, 0, stream, a);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int kmc_sketch_screen_results(const void *index, size_t index_bytes, const uint64_t *r_sketches,
+                                         const uint32_t *r_sizes, uint64_t num_refs, uint32_t sketch_size, int k,
+                                         uint32_t *shared, uint32_t *median_mult, float *identity,
+                                         hipStream_t stream) {
+    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
+    if (!screen_rows_ok(num_refs, sketch_size)) return KMC_ERR_INVALID_ARG;
+    if (num_refs == 0) return KMC_OK;
+    if (!r_sketches || !r_sizes || !shared) return KMC_ERR_INVALID_ARG;
+    if (int e = index_check(index, index_bytes, layout_bytes(kMinSlots))) return e;
+    RArgs a;
+    a.index = const_cast<void *>(index);
+    a.index_bytes = index_bytes;
+    a.rows = r_sketches;
+    a.sizes = r_sizes;
+    a.n = (int64_t)num_refs;
+    a.s = sketch_size;
+    a.k = k;
+    a.shared = shared;
+    a.median = median_mult;
+    a.identity = identity;
+    const dim3 g((unsigned)(a.n < kMaxGridX ? a.n : kMaxGridX)), b(kBlock);
+    for_cap(sketch_size, [&](auto cap) {
+        hipLaunchKernelGGL((screen_results_kernel<decltype(cap)::value>), g, b, 0, stream, a);
+    });
+    return (int)hipGetLastError();
+}

@@ -76,7 +76,8 @@
 //   wave-uniform (uniform64): the unit search and the span are scalar loads and SGPRs.
 //
 // Constants, shipped / under -DKMC_DIAG_HOOKS (libkmc_diag.so: a few thousand bases
-// pass through many ranges, merges and partial sets; no new symbol):
+// pass through many ranges, merges and partial sets; no new symbol; the first, third
+// and fourth are the walk geometry of kmc_sketch_walk.h, shared with the screen):
 //   kBlock      threads of a workgroup                     1024 / 64
 //   kStage      staged candidates per merge (= kBlock)     1024 / 64
 //   kMinChunks  16-byte chunks per range, at least         1024 / 16  (16 KB / 256 B)
@@ -98,23 +99,15 @@
 #include "kmc_canon_walk.h"
 #include "kmc_internal.h"
 #include "kmc_sketch_pair.h"
+#include "kmc_sketch_walk.h"
 #include "kmc_workspace.h"
 
 namespace kmc {
 namespace {
 
-#ifdef KMC_DIAG_HOOKS
-constexpr int kBlock = 64;
-constexpr int64_t kMinChunks = 16;
-constexpr int kWgPerCu = 2;
-#else
-constexpr int kBlock = 1024;
-constexpr int64_t kMinChunks = 1024;
-constexpr int kWgPerCu = 1;
-#endif
+// (kBlock, kMinChunks, kWgPerCu, kMaxSeqs: kmc_sketch_walk.h)
 constexpr int kStage = kBlock;
 constexpr int kWaves = kBlock / 64;
-constexpr uint64_t kMaxSeqs = 1ull << 40;
 
 struct Args {
     const char *data;        // rounded down to 16 bytes
@@ -198,15 +191,8 @@ struct Groups {
     static __device__ __forceinline__ int64_t end(const Args &a, int64_t u) { return a.gofs[u + 1]; }
 };
 
-// The walk's view (kmc_canon_walk.h) with the geometry of this call
-struct Walk {
-    const char *data;
-    const int64_t *idx;
-    int64_t n, lo, hi;
-    int k;
-    uint32_t flags;
-    int64_t c_lo, cpw;
-};
+// The walk's view (kmc_canon_walk.h) with the geometry of this call, over the offsets prep wrote
+using Walk = WalkOf<const int64_t *>;
 
 // over the records of the call's units
 template <class Units>
@@ -255,11 +241,6 @@ __device__ __forceinline__ void span_ranges(const Walk &W, int G, const Span &S,
     w0 = w0 < 0 ? 0 : (w0 > top ? top : w0);
     w1 = w1 < w0 ? w0 : (w1 > top ? top : w1);
 }
-
-struct HashOf {
-    uint64_t seed;
-    __device__ __forceinline__ unsigned long long operator()(uint64_t key) const { return sketch_hash(key, seed); }
-};
 
 // ng < 0: no groups
 __global__ __launch_bounds__(256) void sketch_prep_kernel(Args a) {
@@ -584,16 +565,7 @@ struct SLayout {
     size_t bytes;
 };
 
-// walking workgroups: one range of at least kMinChunks chunks each over the chunks
-// data_bytes can hold (for any alignment of `data`), kWgPerCu per CU at most
-inline int walk_groups(uint64_t data_bytes, int cus) {
-    const uint64_t chunks = data_bytes / 16 + 3;
-    const uint64_t cap = (uint64_t)kWgPerCu * (uint64_t)(cus > 0 ? cus : 1);
-    uint64_t g = (chunks + kMinChunks - 1) / kMinChunks;
-    if (g > cap) g = cap;
-    return (int)(g < 1 ? 1 : g);
-}
-
+// (walk_groups, the walking workgroups of a call: kmc_sketch_walk.h)
 // the one layout behind the size queries (base = null) and the binds; ng < 0: no groups
 inline SLayout layout(void *base, int64_t n, int G, uint32_t s, int64_t ng = -1) {
     Carver c(base);

@@ -207,6 +207,12 @@ def _load(path):
     L.kmc_sketch_nearest_workspace_size.argtypes = [_U64, _U64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
     L.kmc_sketch_nearest.argtypes = [_P, _P, _U64, _P, _P, _U64, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
                                      ctypes.c_uint32, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
+    L.kmc_sketch_screen_index_size.restype = ctypes.c_size_t
+    L.kmc_sketch_screen_index_size.argtypes = [_U64, ctypes.c_uint32]
+    L.kmc_sketch_screen_build.argtypes = [_P, _P, _U64, ctypes.c_uint32, _P, ctypes.c_size_t, _P]
+    L.kmc_sketch_screen_count.argtypes = [_P, ctypes.c_size_t, _P, _P, _U64, _U64, ctypes.c_int, ctypes.c_uint, _U64, _P]
+    L.kmc_sketch_screen_results.argtypes = [_P, ctypes.c_size_t, _P, _P, _U64, ctypes.c_uint32, ctypes.c_int, _P, _P,
+                                            _P, _P]
     L.minKmeres2_hip.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.kmc_count_canonical_hash.argtypes = [_P, _P, _U64, ctypes.c_int, ctypes.c_uint, _P, _P, _U64, _P,
                                            ctypes.POINTER(_U64), _P]
@@ -609,6 +615,59 @@ def sketch_nearest(q, qs, r, rs, k, top, min_shared=1, workspace=None, out=None,
                                   _stream(stream))
     _check(rc, "kmc_sketch_nearest")
     return refs, sh, dn, dist, counts
+
+
+SCREEN_MAX_VALUES = 1 << 30
+
+
+def sketch_screen_index_size(num_refs, sketch_size):
+    return int(lib().kmc_sketch_screen_index_size(num_refs, sketch_size))
+
+
+def sketch_screen_build(r, rs, index=None, stream=None):
+    """The screen index (kmc_sketch_screen_build) of reference rows r [n, s] with sizes
+    rs [n]: a uint8 device tensor of sketch_screen_index_size(n, s) bytes, or the
+    caller's own `index` (a larger one is fine).  Every multiplicity starts at 0."""
+    import torch
+    with _on(stream):
+        r = r.contiguous()
+        n, s = int(r.shape[0]), int(r.shape[1])
+        if index is None:
+            index = torch.empty(sketch_screen_index_size(n, s), dtype=torch.uint8, device=r.device)
+    rc = lib().kmc_sketch_screen_build(_dptr(r), _dptr(rs), n, s, *_ws(index), _stream(stream))
+    _check(rc, "kmc_sketch_screen_build")
+    return index
+
+
+def sketch_screen_count(index, data, indices, k, flags=0, seed=SKETCH_DEFAULT_SEED, data_bytes=None, stream=None):
+    """Adds the windows of the records (data, indices: as sketch_from_sequences) to the
+    multiplicities of `index` (kmc_sketch_screen_count); calls accumulate."""
+    n = int(indices.numel() - 1)
+    if data_bytes is None:
+        data_bytes = data.numel()
+    rc = lib().kmc_sketch_screen_count(*_ws(index), _dptr(data), _dptr(indices), n, int(data_bytes), k, flags,
+                                       int(seed) & _M64, _stream(stream))
+    _check(rc, "kmc_sketch_screen_count")
+
+
+def sketch_screen_results(index, r, rs, k, median=True, identity=True, out=None, stream=None):
+    """What `index` holds of the rows r [n, s] with sizes rs [n]
+    (kmc_sketch_screen_results): (shared int32 [n], median multiplicity int32 [n] or
+    None, containment identity float32 [n] or None); `out`: the caller's own triple."""
+    import torch
+    with _on(stream):
+        r = r.contiguous()
+        n, s = int(r.shape[0]), int(r.shape[1])
+        if out is not None:
+            sh, med, ident = out
+        else:
+            sh = torch.empty(n, dtype=torch.int32, device=r.device)
+            med = torch.empty(n, dtype=torch.int32, device=r.device) if median else None
+            ident = torch.empty(n, dtype=torch.float32, device=r.device) if identity else None
+    rc = lib().kmc_sketch_screen_results(*_ws(index), _dptr(r), _dptr(rs), n, s, k, _dptr(sh), _dptr(med),
+                                         _dptr(ident), _stream(stream))
+    _check(rc, "kmc_sketch_screen_results")
+    return sh, med, ident
 
 
 def min_kmeres2(sums, mins, num_seqs, current_seq, indexes, stream=None):

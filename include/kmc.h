@@ -548,6 +548,87 @@ KMC_API int kmc_sketch_nearest(const uint64_t *q_sketches, const uint32_t *q_siz
                                uint32_t *hit_counts, void *workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* Screening a sequence set for the references it contains (containment; what Mash
+ * calls a screen).  The entry points above compare sketches with sketches; a
+ * bottom-s sketch of a mixture (a read set, a metagenome) holds only its most
+ * abundant members, so a genome wholly contained in it still has a Jaccard estimate
+ * near zero.  Here the values of every reference row are looked for among the hashes
+ * of ALL valid windows of the mixture.  Four steps:
+ *
+ * kmc_sketch_screen_index_size: bytes of the index of num_refs rows of sketch_size
+ * values, an opaque device blob the caller allocates (256-byte aligned; hipMalloc's
+ * pointers are):
+ *     256 + round256(4 C) + 8 C,   C = max(8, 4 num_refs sketch_size rounded up to a
+ *                                  power of two)
+ * a header, a uint32 multiplicity per slot and C 64-bit slots of an open-addressing
+ * table, each array rounded up to 256 bytes.  It depends on the two numbers only and
+ * needs no device; 0 on bad arguments (sketch_size outside 1..KMC_SKETCH_MAX_SIZE,
+ * num_refs * sketch_size above KMC_SCREEN_MAX_VALUES).  num_refs == 0 gives the size
+ * of the empty index (C = 8), so the size is monotone in both arguments.
+ *
+ * kmc_sketch_screen_build: fills the index with the distinct values among the first
+ * min(r_sizes[r], sketch_size) values of every row (rows as the sketch entry points
+ * write them; their order within a row does not matter here) and a zeroed
+ * multiplicity per distinct value.  Values are opaque 64-bit numbers; UINT64_MAX
+ * inside a row's size is a real value and is indexed like any other.  A value that
+ * several rows hold is indexed once and shared by all of them.  Nothing a former use
+ * left in the blob is read; building again zeroes the multiplicities.  index_bytes
+ * below the size above: KMC_ERR_WORKSPACE.  num_refs == 0: KMC_OK; given an index
+ * (checked as otherwise) it is made the empty index, and the row pointers may be NULL.
+ *
+ * kmc_sketch_screen_count: one pass over the records.  data, indices, num_seqs,
+ * data_bytes, k, flags, the window rules and validity are kmc_sketch_from_sequences';
+ * every valid window's hash (the hash above of its canonical key, with `seed`) that
+ * is in the index adds 1 to that value's multiplicity.  It accumulates: several calls
+ * on batches of a sample equal one call on their concatenation, so a read set larger
+ * than device memory is screened batch by batch against one index (and shards
+ * screened on several devices add up).  k, flags and seed must be those the
+ * references were sketched with; that is the caller's business.  Multiplicities are
+ * exact while fewer than 2^32 windows have been accumulated into an index; beyond
+ * that they are modulo 2^32, with no stray access.  No workspace.  num_seqs == 0:
+ * KMC_OK, the index is left as it is.
+ *
+ * kmc_sketch_screen_results: per row r of a row set (the one given to build, or any
+ * other rows of any sketch_size: values not in the index count as absent; values are
+ * assumed distinct within a row), with size = min(r_sizes[r], sketch_size):
+ *   shared[r]       the number of the row's values with multiplicity > 0
+ *   median_mult[r]  the lower median of the multiplicities of those found values
+ *                   (ascending, element (shared - 1) / 2); 0 when shared == 0.  May
+ *                   be NULL.
+ *   identity[r]     Mash's containment identity.  May be NULL.
+ *                     size == 0        NaN
+ *                     shared == 0      +0.0f
+ *                     shared == size   1.0f
+ *                     otherwise        pow((double)shared / size, 1.0 / k), rounded to float
+ * It does not modify the index: count, results, count, results is a valid sequence.
+ * num_refs == 0: KMC_OK, nothing written.
+ *
+ * All three device calls are asynchronous on `stream`, with no host read-back; the
+ * work launched depends on the host arguments only; no library-owned buffer is used,
+ * so calls on different indexes may overlap (calls on one index are ordered by the
+ * caller).  count and results learn the table's extent from the header build wrote
+ * and check it against index_bytes on the device: on a blob that was never built the
+ * result is unspecified, with no stray access.  On the host they refuse index_bytes
+ * below the smallest index (kmc_sketch_screen_index_size(0, 1)) with
+ * KMC_ERR_WORKSPACE.  Errors, judged before any device is touched: k outside
+ * 1..KMC_CANON_MAX_K: KMC_ERR_UNSUPPORTED_K (count, results); KMC_ERR_INVALID_ARG
+ * for a sketch_size outside 1..KMC_SKETCH_MAX_SIZE, num_refs * sketch_size above
+ * KMC_SCREEN_MAX_VALUES, unknown flag bits, num_seqs above 2^40, a null index, null
+ * rows or sizes with num_refs > 0, null shared, null indices, null data with
+ * data_bytes > 0; then KMC_ERR_WORKSPACE; then KMC_ERR_ALIGNMENT for an index that
+ * is not 256-byte aligned. */
+#define KMC_SCREEN_MAX_VALUES 1073741824ull
+KMC_API size_t kmc_sketch_screen_index_size(uint64_t num_refs, uint32_t sketch_size);
+KMC_API int kmc_sketch_screen_build(const uint64_t *r_sketches, const uint32_t *r_sizes, uint64_t num_refs,
+                                    uint32_t sketch_size, void *index, size_t index_bytes, hipStream_t stream);
+KMC_API int kmc_sketch_screen_count(void *index, size_t index_bytes, const char *data, const int64_t *indices,
+                                    uint64_t num_seqs, uint64_t data_bytes, int k, unsigned flags, uint64_t seed,
+                                    hipStream_t stream);
+KMC_API int kmc_sketch_screen_results(const void *index, size_t index_bytes, const uint64_t *r_sketches,
+                                      const uint32_t *r_sizes, uint64_t num_refs, uint32_t sketch_size, int k,
+                                      uint32_t *shared, uint32_t *median_mult, float *identity, hipStream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* Tracing (the reference times step 1 with cudaEvents, main.cu:262-300): when set,
  * every following dense count call on this host thread records `before` right
  * before its histogram kernel and `after` right after it, on the call's stream,

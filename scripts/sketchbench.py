@@ -11,6 +11,10 @@ distances on group rows and on record rows (profiles/pr_sketch_grouped.jsonl).
 With --query: kmc_sketch_nearest and kmc_sketch_distances_rect (alone and followed by
 torch.topk) beside kmc_sketch_distances over the concatenation of queries and
 references, on synthetic rows (profiles/pr_sketch_query.jsonl).
+With --screen: kmc_sketch_screen_build, _count and _results of 1000 references of
+1 Mbase (and of 100 of 5 kbase) in a mixture of 1000 x 1 Mbase, beside
+kmc_sketch_from_sequences_grouped over the same mixture as one group, the same walk
+plus the set upkeep (profiles/pr_sketch_screen.jsonl).
 
 Inputs (synthetic, generated on the device):
   iid          8 x 50 Mbase independent records, k = 31
@@ -259,6 +263,56 @@ def query_main(args, dev):
             torch.cuda.empty_cache()
 
 
+def screen_main(args, dev):
+    """--screen: references in a mixture.  Half of the references are cut from the
+    mixture (reference r, r even, is the head of mixture record r); shared == size is
+    asserted for them, and no more than chance hits for the others, before anything is
+    timed.  The
+    yardstick for count is the grouped sketch of the whole mixture, on the same buffer."""
+    k, s, records = 21, 1000, 1000
+    record_len = max(int(1_000_000 * args.scale), 5000)
+    mix = torch.empty(records * (record_len + 1), dtype=torch.uint8, device=dev)
+    kmc.synth_fill(mix, records, record_len, 0x5EED0008)
+    midx = torch.from_numpy(kmc.synth_indices(records, record_len)).to(dev)
+    one_group = torch.tensor([0, records], dtype=torch.int64, device=dev)
+    grouped = timed(lambda: kmc.sketch_from_sequences_grouped(mix, midx, one_group, k, s), args.runs)
+    with open(args.out, "a") as out:
+        for name, nrefs, ref_len in (("genomes", 1000, record_len), ("viruses", 100, 5000)):
+            refs = torch.empty(nrefs * (ref_len + 1), dtype=torch.uint8, device=dev)
+            kmc.synth_fill(refs, nrefs, ref_len, 0x5EED0009)
+            refs.view(nrefs, ref_len + 1)[::2] = mix.view(records, record_len + 1)[:nrefs:2, :ref_len + 1]
+            refs.view(nrefs, ref_len + 1)[:, ref_len] = 0
+            ridx = torch.from_numpy(kmc.synth_indices(nrefs, ref_len)).to(dev)
+            sk, sz = kmc.sketch_from_sequences(refs, ridx, k, s)
+            del refs
+            index = kmc.sketch_screen_build(sk, sz)
+            kmc.sketch_screen_count(index, mix, midx, k)
+            sh, med, ident = kmc.sketch_screen_results(index, sk, sz, k)
+            torch.cuda.synchronize()
+            assert torch.equal(sh[::2], sz[::2]) and int(sz.min()) == s, name
+            # (chance hits: 10^9 windows against 2.2 x 10^12 canonical 21-mers, 0.45 expected per reference)
+            assert int(sh[1::2].max()) <= 10, (name, "a reference that is not in the mixture shares", int(sh[1::2].max()))
+            assert int(med[::2].min()) == 1 and float(ident[::2].min()) == 1.0, (name, int(med[::2].min()))
+            # the share of the mixture's windows at or below the largest indexed value: what the prefilter passes
+            top = int(sk.max()) if int(sk.min()) >= 0 else None  # (as int64: every value below 2^63)
+            rec = {
+                "input": name, "refs": nrefs, "ref_len": ref_len, "mixture_records": records,
+                "mixture_record_len": record_len, "k": k, "sketch_size": s, "contained_found_whole": True,
+                "chance_hits_max": int(sh[1::2].max()),
+                "index_bytes": int(index.numel()),
+                "prefilter_pass_fraction": None if top is None else top / 2.0 ** 64,
+                "kmc_sketch_screen_build": timed(lambda: kmc.sketch_screen_build(sk, sz, index=index), args.runs),
+                "kmc_sketch_screen_count": timed(lambda: kmc.sketch_screen_count(index, mix, midx, k), args.runs),
+                "kmc_sketch_screen_results": timed(lambda: kmc.sketch_screen_results(index, sk, sz, k), args.runs),
+                "kmc_sketch_from_sequences_grouped": grouped,
+            }
+            out.write(json.dumps(rec) + "\n")
+            out.flush()
+            print(json.dumps(rec), flush=True)
+            del sk, sz, index
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(HERE), "profiles", "pr_sketch.jsonl"))
@@ -279,8 +333,16 @@ def main():
                          "queries and references together: 64 queries in 4096 and 65536 references of s = 1000 and "
                          "in 4096 of s = 10000, synthetic rows (hits asserted equal to the rectangle's; 2 warm-ups, "
                          "median of --runs); --out profiles/pr_sketch_query.jsonl")
+    ap.add_argument("--screen", action="store_true",
+                    help="time kmc_sketch_screen_build, _count and _results of 1000 references of 1 Mbase and of "
+                         "100 of 5 kbase (s = 1000, k = 21, half of them cut from the mixture: asserted found "
+                         "whole) in a synthetic mixture of 1000 x 1 Mbase, beside kmc_sketch_from_sequences_grouped "
+                         "over the mixture as one group (2 warm-ups, median of --runs); appends to "
+                         "--out profiles/pr_sketch_screen.jsonl")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.screen:
+        return screen_main(args, dev)
     if args.query:
         return query_main(args, dev)
     if args.grouped:
