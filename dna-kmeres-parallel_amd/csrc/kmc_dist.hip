@@ -85,6 +85,8 @@ __global__ __launch_bounds__(256) void pair_min_kernel(DParams p) {
         }
         __syncthreads();
         const uint32_t(*Bs)[TT] = diag ? A : B;
+        // 32 bits cannot overflow under the header's contract: a pair's minima add up to
+        // no more than either record's bins, which sum to its windows, fewer than 2^32
         uint32_t part[TM][TN];
 #pragma unroll
         for (int a = 0; a < TM; ++a)
