@@ -34,8 +34,8 @@
 //               cleared
 //   K5 place    exclusive scan of the distinct counts; each list's pairs are copied
 //               to their final place; records are contiguous runs of lists (K4
-//               writes 8 bytes per pair: counts 1..3 in the key's two spare top
-//               bits, larger ones in a side array)
+//               writes 8 bytes per pair, encode_pair: counts 1..3 in the key's two
+//               spare top bits, larger ones in a side array)
 // Bytes per window: the input twice (K1, K3a), an 8-byte h written and read twice
 // (K3a -> K3b -> K4), 12 bytes of pairs written, read and written again.
 //
@@ -47,6 +47,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <mutex>
 #include <vector>
@@ -88,6 +89,15 @@ constexpr uint32_t kErrBound = 2u;   // a queue count, list id, range or output 
                                      // allocation: the access is skipped (KMC_ERR_INTERNAL)
 static_assert(kPassDistinct <= kWaves4 * kClaimW && kTableSlots < 65536 , "K4 sizes");
 
+// A list left to another kernel: its id and its keys ent[begin, end).  A queue of
+// them has room for one entry per list (each list is queued there at most once);
+// push_list writes it, list_count reads its count and list_ref_ok checks an entry.
+struct ListRef { uint64_t list, begin, end; };
+struct ListQueue { ListRef *at; unsigned long long *n; };  // [lists] entries, and how many were pushed
+// Pairs left in pk[src, src + pairs), to be copied to offset `off` of record rec
+// (direct output; queue_copy writes them, canon_fallback_kernel reads them)
+struct CopyRef { uint64_t src, rec, off, pairs; };
+
 struct HParams {
     const char *data;        // global offsets (data[p] is byte p)
     const int64_t *idx;      // device, n + 1
@@ -122,11 +132,10 @@ struct HParams {
     uint32_t claim_cap;      // K4 claims per wave and pass (kClaimW; smaller only in tests)
     uint32_t sort_cap;       // K4s takes lists of at most this many keys (kSortCap; 0 in tests: none)
     uint32_t sort_cap_big;   // the big K4s instance takes the longer ones up to this (kSortCapBig; 0: none)
-    uint64_t *big;           // [lists][3] (list, begin, end) handed by K4s to its big instance
-    unsigned long long *nbig;  // their number
-    uint64_t *defer;         // [lists][3] (list, begin, end) for the table kernel: without direct output
-    unsigned long long *ndefer;  // the lists either K4s instance hands back; with it, only the lists longer
-                                 // than the big instance's cap (canon_classify_kernel; the first launch)
+    ListQueue big;           // the lists K4s hands to its big instance
+    ListQueue defer;         // for the table kernel: without direct output the lists either K4s instance
+                             // hands back; with it, only the lists longer than the big instance's cap
+                             // (canon_classify_kernel; the first launch)
     uint64_t *rec_off;       // [n + 1] output offsets
     uint64_t *out_keys;
     uint32_t *out_counts;
@@ -139,12 +148,11 @@ struct HParams {
     unsigned long long *rstate;   // [n] bits 0-39: pairs reserved in r; 40-63: lists of r not yet reserved,
                                   // counted up from 2^24 - lists(r) (0 once every list has reserved)
     unsigned long long *rbase;    // [n + 1] start of record r's pairs once known (~0 before)
-    uint64_t *fq;                 // [2 lists][4] (pk offset, record, offset in the record, pairs) to copy
+    CopyRef *fq;                  // [2 lists] the copies canon_fallback_kernel makes
     unsigned long long *nfq;      // their number
-    uint64_t *tq;                 // the queue this canon_table_kernel launch drains (defer or defer2)
-    unsigned long long *ntq;
-    uint64_t *defer2;             // [lists][3] direct mode: the lists either K4s instance hands back (too
-    unsigned long long *ndefer2;  // many crowded slots), drained by the table kernel's second launch
+    ListQueue tq;                 // the queue this canon_table_kernel launch drains (defer or defer2)
+    ListQueue defer2;             // direct mode: the lists either K4s instance hands back (too many
+                                  // crowded slots), drained by the table kernel's second launch
     int64_t l_lo, l_hi;           // direct mode: the lists of this launch of the common instance
 };
 
@@ -156,6 +164,29 @@ struct HParams {
 // (section 4.4 of DESIGN.md, "The round-5 memory-aperture fault").
 __device__ __forceinline__ void raise_err(const HParams &p, uint32_t b) {
     __hip_atomic_fetch_or(p.err, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Appends list l and its key range to q (one thread).
+__device__ __forceinline__ void push_list(const HParams &p, const ListQueue &q, int64_t l, uint64_t b, uint64_t e) {
+    const unsigned long long i = atomicAdd(q.n, 1ull);
+    if (i >= (uint64_t)p.lists) {  // (guard)
+        raise_err(p, kErrBound);
+        return;
+    }
+    q.at[i] = ListRef{(uint64_t)l, b, e};
+}
+
+// A count of queued lists taken from the workspace (every thread of the launch
+// passes the same word), or -1: (guard) a queue holds at most one entry per list.
+__device__ __forceinline__ int64_t list_count(const HParams &p, unsigned long long n) {
+    if (n <= (uint64_t)p.lists) return (int64_t)n;
+    if (blockIdx.x == 0 && threadIdx.x == 0) raise_err(p, kErrBound);
+    return -1;
+}
+
+// (guard) a queue entry's list id and key range inside the call's lists and entries
+__device__ __forceinline__ bool list_ref_ok(const HParams &p, const ListRef &r) {
+    return r.list < (uint64_t)p.lists && r.begin <= r.end && r.end <= p.win_cap;
 }
 
 // Partition value of a key: K1 / K3a / K3b bucket and list by its top bits.  A
@@ -189,6 +220,31 @@ __device__ __forceinline__ uint64_t part_of(uint64_t key) { return key * kMulC; 
 
 __device__ __forceinline__ uint64_t list_value(uint64_t m) {  // partition value -> list value
     return feistel(m * kMulCinv);
+}
+
+// The pair format (K4s, K4 -> K5 or the fallback copy): pk[o] is a list value h
+// with its count in the two spare top bits -- tag 0..2 for 1..3 occurrences, tag 3
+// for more, and only then is the count itself in pc[o].  One test decides both the
+// tag and the escape.
+static_assert(2 * KMC_CANON_MAX_K <= 62, "pair format: keys must leave the top two bits free");
+struct Pair { unsigned long long word; bool escaped; };  // for pk; whether the count goes to pc
+__device__ __forceinline__ Pair encode_pair(unsigned long long h, uint32_t cnt) {
+    const uint32_t c = cnt - 1u;
+    const bool small = c < 3u;
+    return Pair{h | ((unsigned long long)(small ? c : 3u) << 62), !small};
+}
+// the store form: (h, cnt) at pair offset o
+__device__ __forceinline__ void emit_pair(const HParams &p, uint64_t o, unsigned long long h, uint32_t cnt) {
+    const Pair e = encode_pair(h, cnt);
+    p.pk[o] = e.word;
+    if (e.escaped) p.pc[o] = cnt;
+}
+// the pair at offset o, whose word x the caller has loaded: its key (the list
+// value mapped back) and count
+struct KeyCount { uint64_t key; uint32_t count; };
+__device__ __forceinline__ KeyCount decode_pair(const HParams &p, uint64_t o, unsigned long long x) {
+    const uint32_t tag = (uint32_t)(x >> 62);
+    return KeyCount{feistel(x & kM62), tag < 3u ? tag + 1u : p.pc[o]};
 }
 
 // The input walk (chunk_raw / chunk_keys / for_each_piece) is kmc_canon_walk.h's;
@@ -667,12 +723,12 @@ __device__ __forceinline__ void chain_from(const HParams &p, int64_t r, unsigned
 }
 
 // Reserve `cnt` pairs for one list of record r (one thread): returns the list's
-// offset in the record and sets *F to the record's start, or kUnknown.
+// offset in the record and sets F to the record's start, or kUnknown.
 __device__ __forceinline__ unsigned long long reserve_pairs(const HParams &p, int64_t r, uint32_t cnt,
-                                                            unsigned long long *F) {
+                                                            unsigned long long &F) {
     if ((uint64_t)r >= (uint64_t)p.n) {  // (guard) not a record of this call
         raise_err(p, kErrBound);
-        *F = kUnknown;
+        F = kUnknown;
         return 0;
     }
     const unsigned long long old = __hip_atomic_fetch_add(&p.rstate[r], (unsigned long long)cnt + (1ull << kPairsBits),
@@ -683,7 +739,7 @@ __device__ __forceinline__ unsigned long long reserve_pairs(const HParams &p, in
         const unsigned long long fr = ld_agent(&p.rbase[r]);        // (after the add)
         if (fr != kUnknown) chain_from(p, r, fr);
     }
-    *F = f;
+    F = f;
     return old & kPairsMask;
 }
 
@@ -695,10 +751,46 @@ __device__ __forceinline__ void queue_copy(const HParams &p, uint64_t src, int64
         raise_err(p, kErrBound);
         return;
     }
-    p.fq[4 * i] = src;
-    p.fq[4 * i + 1] = (uint64_t)r;
-    p.fq[4 * i + 2] = c;
-    p.fq[4 * i + 3] = cnt;
+    p.fq[i] = CopyRef{src, (uint64_t)r, c, cnt};
+}
+
+// A counted list l whose pairs lie in pk[b0, b0 + pairs) (one thread): its count
+// for K5's scan, or with direct output reserved in its record and queued for the
+// copy at the end.
+__device__ __forceinline__ void finish_list(const HParams &p, int64_t l, uint64_t b0, uint32_t pairs) {
+    if (p.direct) {
+        unsigned long long F;
+        const int64_t r = p.lrec[l];
+        queue_copy(p, b0, r, reserve_pairs(p, r, pairs, F), pairs);
+    } else {
+        p.ndist[l] = pairs;
+    }
+}
+
+// The workgroup's per-wave totals w[0 .. NW): their sum over the waves before
+// wave wv, and over all
+template <int NW>
+__device__ __forceinline__ void wave_totals(const uint32_t (&w)[NW], int wv, uint32_t &before, uint32_t &total) {
+    before = total = 0u;
+#pragma unroll
+    for (int v = 0; v < NW; ++v) {
+        const uint32_t x = w[v];
+        before += v < wv ? x : 0u;
+        total += x;
+    }
+}
+
+// Wave-aggregated reservation on an LDS counter: n (wave-uniform) entries for the
+// wave by one add of lane 0; returns their start
+__device__ __forceinline__ uint32_t wave_reserve_n(uint32_t *counter, uint32_t n) {
+    uint32_t wb = 0u;
+    if ((threadIdx.x & 63u) == 0u && n) wb = atomicAdd(counter, n);
+    return __builtin_amdgcn_readlane(wb, 0);  // (a v_readlane, where __shfl is a ds_bpermute)
+}
+// ... one entry for each lane of mask (a ballot): the lane's own
+__device__ __forceinline__ uint32_t wave_reserve(uint32_t *counter, uint64_t mask) {
+    const uint64_t lt = (1ull << (threadIdx.x & 63u)) - 1ull;
+    return wave_reserve_n(counter, (uint32_t)__popcll(mask)) + (uint32_t)__popcll(mask & lt);
 }
 
 // K4: lists counted in an LDS table, workgroups striding over the lists.  Its
@@ -831,51 +923,45 @@ __device__ __forceinline__ void wave_insert(const unsigned long long (&kh)[kRes]
     } while (next < kRes && ncl <= cap);
 }
 
+__device__ __forceinline__ void clear_table(K4Lds &L) {
+    for (int i = threadIdx.x; i < kTableSlots; i += kCountBlock) {
+        L.tk[i] = kEmptyH;
+        L.tc[i] = 0u;
+    }
+}
 
 __global__ __launch_bounds__(kCountBlock) __attribute__((amdgpu_waves_per_eu(4))) void canon_table_kernel(HParams p) {
     __shared__ K4Lds L;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    for (int i = tid; i < kTableSlots; i += kCountBlock) {
-        L.tk[i] = kEmptyH;
-        L.tc[i] = 0u;
-    }
+    clear_table(L);
     if (tid < 2) L.ovf[tid] = 0u;
     if (tid < 64) L.dummy[tid] = 0ull;
     lds_barrier();
     // the lists canon_sort_kernel left: longer than its capacity, or a key repeated
-    // more often than its dedup takes
-    const int64_t G = gridDim.x, nl = (int64_t)*p.ntq;
-    const uint64_t *dl = p.tq;  // (list, begin, end) triples (defer, or in direct mode defer2)
-    if ((uint64_t)nl > (uint64_t)p.lists) {  // (guard) the queue holds at most one entry per list
-        if (blockIdx.x == 0 && tid == 0) raise_err(p, kErrBound);
-        return;
-    }
+    // more often than its dedup takes (defer, or in direct mode defer2)
+    const int64_t G = gridDim.x, nl = list_count(p, *p.tq.n);
+    const ListRef *dl = p.tq.at;
     int64_t i = blockIdx.x;
     if (i >= nl) return;
-    // list bounds two lists ahead, keys one list ahead
-    uint64_t b0 = dl[3 * i + 1], e0 = dl[3 * i + 2], b1 = 0, e1 = 0;
-    if (i + G < nl) {
-        b1 = dl[3 * (i + G) + 1];
-        e1 = dl[3 * (i + G) + 2];
-    }
+    // list bounds two lists ahead, keys one list ahead: entry j's bounds (none: 0,
+    // 0), and one list on
+    const auto bounds = [&](int64_t j, uint64_t &b, uint64_t &e) {
+        b = e = 0;
+        if (j < nl) b = dl[j].begin, e = dl[j].end;
+    };
+    uint64_t b0, e0, b1, e1, b2, e2;
+    const auto advance = [&]() { b0 = b1, e0 = e1, b1 = b2, e1 = e2; };
+    bounds(i, b0, e0);
+    bounds(i + G, b1, e1);
     unsigned long long kr[kRes];
     int par = 0;
-    for (; i < nl; i += G) {
-        const int64_t l = (int64_t)dl[3 * i];
-        uint64_t b2 = 0, e2 = 0;
-        if (i + 2 * G < nl) {
-            b2 = dl[3 * (i + 2 * G) + 1];
-            e2 = dl[3 * (i + 2 * G) + 2];
-        }
-        // (guard, workgroup-uniform: every thread read the same triple) a list id
-        // and key range inside the call's lists and entries
-        if ((uint64_t)l >= (uint64_t)p.lists || b0 > e0 || e0 > p.win_cap) {
+    for (; i < nl; i += G, advance()) {
+        const int64_t l = (int64_t)dl[i].list;
+        bounds(i + 2 * G, b2, e2);
+        // (workgroup-uniform: every thread read the same entry)
+        if (!list_ref_ok(p, ListRef{(uint64_t)l, b0, e0})) {
             if (tid == 0) raise_err(p, kErrBound);
-            b0 = b1;
-            e0 = e1;
-            b1 = b2;
-            e1 = e2;
             continue;
         }
         if (e0 - b0 <= (uint64_t)kResKeys) load_keys(p.ent, b0, e0, kr);
@@ -904,10 +990,7 @@ __global__ __launch_bounds__(kCountBlock) __attribute__((amdgpu_waves_per_eu(4))
             if (ovf) {
                 // clear the table and redo with twice the passes (pass q -> passes 2q,
                 // 2q+1); the pairs of the passes already written stay, the split refines
-                for (int i = tid; i < kTableSlots; i += kCountBlock) {
-                    L.tk[i] = kEmptyH;
-                    L.tc[i] = 0u;
-                }
+                clear_table(L);
                 lds_barrier();
                 par ^= 1;
                 if (P >= kMaxPasses) {  // > 2^17 x 2 560 distinct keys in one list: out of pass bits
@@ -918,13 +1001,8 @@ __global__ __launch_bounds__(kCountBlock) __attribute__((amdgpu_waves_per_eu(4))
                 q <<= 1;
                 continue;
             }
-            uint32_t before = 0, total = 0;
-#pragma unroll
-            for (int w2 = 0; w2 < kWaves4; ++w2) {
-                const uint32_t v = L.ncl[par][w2];
-                before += w2 < wv ? v : 0u;
-                total += v;
-            }
+            uint32_t before, total;
+            wave_totals(L.ncl[par], wv, before, total);
             // the wave's claimed slots, in claim order (coalesced), cleared; the
             // pass's pairs stay inside the list's segment (guard: distinct <= keys)
             const bool fits = out + total <= e0;
@@ -936,32 +1014,14 @@ __global__ __launch_bounds__(kCountBlock) __attribute__((amdgpu_waves_per_eu(4))
                 const uint32_t c = L.tc[sl];
                 L.tk[sl] = kEmptyH;
                 L.tc[sl] = 0u;
-                if (fits) {
-                    // keys use at most 62 bits (k <= 31): occurrences 1..3 ride in the
-                    // top two bits, larger counts escape to pc (K5 reads it only then)
-                    const unsigned long long tag = c < 3u ? c : 3u;
-                    p.pk[out + before + i] = h | (tag << 62);
-                    if (c >= 3u) p.pc[out + before + i] = c + 1u;
-                }
+                if (fits) emit_pair(p, out + before + i, h, c + 1u);  // (tc holds occurrences - 1; the + 1 folds away)
             }
             out += total;
             lds_barrier();
             par ^= 1;
             ++q;
         }
-        if (tid == 0) {
-            if (p.direct) {  // the list's pairs stay in pk: reserved in the record, copied at the end
-                unsigned long long F;
-                const int64_t r = p.lrec[l];
-                queue_copy(p, b0, r, reserve_pairs(p, r, (uint32_t)(out - b0), &F), out - b0);
-            } else {
-                p.ndist[l] = (uint32_t)(out - b0);
-            }
-        }
-        b0 = b1;
-        e0 = e1;
-        b1 = b2;
-        e1 = e2;
+        if (tid == 0) finish_list(p, l, b0, (uint32_t)(out - b0));
     }
 }
 
@@ -988,8 +1048,10 @@ __global__ __launch_bounds__(kCountBlock) __attribute__((amdgpu_waves_per_eu(4))
 // 8 192-slot table, takes the lists of 6 081 .. 12 288 keys that the
 // first hands it (chromosome-sized records: 2^15 lists of ~7.6 K keys), which
 // until round 3 went to the probed table kernel.
-template <int BLOCK, int RES, uint32_t CAP, int SLOTS_LG, uint32_t SK, uint32_t RC>
+template <int BLOCK, int RES, uint32_t CAP, int SLOTS_LG, uint32_t SK, uint32_t RC, uint32_t HParams::*RUN_CAP>
 struct SortCfg {
+    // the call's cap on the lists this instance takes (kCap, or what the test hooks lowered it to)
+    static __device__ __forceinline__ uint32_t cap(const HParams &p) { return p.*RUN_CAP; }
     static constexpr uint32_t kSk = SK;                 // sk entries: the list's keys, then staged results
     static constexpr uint32_t kRc = RC;                 // direct output: staged results' counts
     static constexpr int kBlock = BLOCK;
@@ -1000,9 +1062,8 @@ struct SortCfg {
     static_assert(CAP <= (uint32_t)(BLOCK * RES) && CAP < 32768u && CAP <= SK, "K4s sizes");
     static_assert(kSlots == BLOCK * 8, "K4s scan: 8 slot words per thread");
 };
-constexpr uint32_t kSortCapBigCfg = 12288;  // the big instance's cap (sort_list tells the instances apart by it)
-using SortSmall = SortCfg<512, 12, 6080, 12, 7456, 1024>;   // LDS: 2 workgroups per CU
-using SortBig = SortCfg<1024, 12, kSortCapBigCfg, 13, 15232, 2048>;   // LDS: 1 workgroup per CU
+using SortSmall = SortCfg<512, 12, 6080, 12, 7456, 1024, &HParams::sort_cap>;       // LDS: 2 workgroups per CU
+using SortBig = SortCfg<1024, 12, 12288, 13, 15232, 2048, &HParams::sort_cap_big>;  // LDS: 1 workgroup per CU
 constexpr int kSortBlock = SortSmall::kBlock;
 constexpr uint32_t kSortCap = SortSmall::kCap;
 constexpr uint32_t kSortCapBig = SortBig::kCap;
@@ -1027,38 +1088,7 @@ struct K4sLds {
 static_assert(sizeof(K4sLds<SortBig>) <= 160 * 1024, "big K4s instance: one workgroup per CU");
 static_assert(sizeof(K4sLds<SortSmall>) <= 80 * 1024, "common K4s instance: two workgroups per CU");
 
-// a list left to another kernel: its id and key range, appended to (q, nq), a
-// queue of p.lists entries (each list is queued at most once)
-__device__ __forceinline__ void queue_list(const HParams &p, uint64_t *q, unsigned long long *nq, int64_t l,
-                                           uint64_t b, uint64_t e) {
-    const unsigned long long i = atomicAdd(nq, 1ull);
-    if (i >= (uint64_t)p.lists) {  // (guard)
-        raise_err(p, kErrBound);
-        return;
-    }
-    q[3 * i] = (uint64_t)l;
-    q[3 * i + 1] = b;
-    q[3 * i + 2] = e;
-}
-__device__ __forceinline__ void defer_list(const HParams &p, int64_t l, uint64_t b, uint64_t e) {
-    queue_list(p, p.defer, p.ndefer, l, b, e);
-}
-
-// The pair format (K4s, K4 -> K5): a canonical key of k <= 31 bases uses at most
-// 62 bits, so occurrences 1..3 ride in its top two bits and larger counts escape
-// to pc.
-static_assert(2 * KMC_CANON_MAX_K <= 62, "pair format: keys must leave the top two bits free");
-
-// emits (h, cnt) at list offset o (the table kernel's pair format)
-__device__ __forceinline__ void emit_pair(const HParams &p, uint64_t o, unsigned long long h, uint32_t cnt) {
-    const uint32_t c = cnt - 1u;  // occurrences - 1, as the table kernel stores them
-    const unsigned long long tag = c < 3u ? c : 3u;
-    p.pk[o] = h | (tag << 62);
-    if (c >= 3u) p.pc[o] = cnt;
-}
-
 __device__ __forceinline__ uint32_t half16(uint32_t w, uint32_t hi) { return hi ? (w >> 16) : (w & 0xFFFFu); }
-
 
 // A slot word after the scan: the slot's start in sk (bits 0-15), its key count
 // (16-30) and bit 31 set when its keys are known to be distinct (section 4.4).
@@ -1083,7 +1113,6 @@ __device__ __forceinline__ void sort_list(const HParams &p, K4sLds<C> &S, int64_
     constexpr int kRes = C::kRes, kBlk = C::kBlock, kSlots = C::kSlots;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint64_t lt = (1ull << lane) - 1ull;
     const int64_t rec = DIRECT ? (int64_t)p.lrec[l] : 0;  // (loaded with the keys)
     unsigned long long kh[kRes];
 #pragma unroll
@@ -1125,7 +1154,7 @@ __device__ __forceinline__ void sort_list(const HParams &p, K4sLds<C> &S, int64_
         // (a list this instance will not take -- longer than its cap, which the test
         // hooks may lower below kCap -- is another kernel's: not prefetched, so no
         // DMA into this workgroup's LDS is left in flight by a list it skips)
-        const uint64_t lim = C::kCap == kSortCapBigCfg ? p.sort_cap_big : p.sort_cap;
+        const uint64_t lim = C::cap(p);
         const uint64_t nn = ne0 - nb0 <= (lim < (uint64_t)C::kCap ? lim : (uint64_t)C::kCap) ? ne0 - nb0 : 0;
         if ((uint64_t)tid * 16u < nn) {
             const uint64_t a = (uint64_t)(p.ent + nb0 + (uint64_t)tid * 16u);
@@ -1186,13 +1215,9 @@ __device__ __forceinline__ void sort_list(const HParams &p, K4sLds<C> &S, int64_
     const uint32_t incl = wave_incl_scan(run);
     if (lane == 63) S.wsum[wv] = incl;
     lds_barrier();  // C1: wave totals
-    uint32_t base = incl - run, nsk = 0u;  // nsk: keys of the slots that failed the test
-#pragma unroll
-    for (int v = 0; v < kBlk / 64; ++v) {
-        const uint32_t x = S.wsum[v];
-        base += v < wv ? x : 0u;
-        nsk += x;
-    }
+    uint32_t before, nsk;  // nsk: keys of the slots that failed the test
+    wave_totals(S.wsum, wv, before, nsk);
+    const uint32_t base = incl - run + before;
 #pragma unroll
     for (int i = 0; i < 8; ++i) w[i] += base;  // starts < 2^15: no carry into the count
     reinterpret_cast<uint4 *>(S.sc)[2 * tid] = make_uint4(w[0], w[1], w[2], w[3]);
@@ -1200,18 +1225,26 @@ __device__ __forceinline__ void sort_list(const HParams &p, K4sLds<C> &S, int64_
     lds_barrier();  // C2: slot starts
     const uint32_t nhot = S.nhot;
     if (nhot > kHotMax) {  // too many crowded slots: the probed table counts this list (uniform)
-        if (tid == 0) {
-            // (direct output: to the table kernel's second launch, after every other
-            // list; its first takes the lists too long for the big instance)
-            if (DIRECT) queue_list(p, p.defer2, p.ndefer2, l, b0, e0);
-            else defer_list(p, l, b0, e0);
-        }
+        // (direct output: to the table kernel's second launch, after every other
+        // list; its first takes the lists too long for the big instance)
+        if (tid == 0) push_list(p, DIRECT ? p.defer2 : p.defer, l, b0, e0);
         return;  // (the next list's barrier A orders the LDS reuse)
     }
     const uint32_t na = n - nsk;  // keys of the distinct slots (each a pair of count 1)
     constexpr bool staged = DIRECT;  // (the distinct slots' keys always fit: n <= kCap <= kSk)
     // results staged in LDS (the rest to pk[b0 + na + o])
     const uint32_t rcap = DIRECT ? (C::kSk - n < C::kRc ? C::kSk - n : C::kRc) : 0u;
+    // result o of the failing slots (counted in nres_at): staged after the distinct
+    // slots' keys (its count in rc), or as a pair in pk
+    uint32_t *const nres_at = DIRECT ? &S.nres : &S.out;
+    const auto put_result = [&](uint32_t o, unsigned long long h, uint32_t cnt) {
+        if (DIRECT && o < rcap) {
+            S.sk[n + o] = h;
+            S.rc[o] = cnt;
+        } else {
+            emit_pair(p, b0 + (DIRECT ? na : 0u) + o, h, cnt);
+        }
+    };
     // scatter: a key of a distinct slot (alone in it, or all its keys on
     // different subs: ~94 % of the keys of distinct 2-4 K-key lists over 4 096
     // slots) is a key of count 1 and leaves at once; the others go to sk
@@ -1225,11 +1258,8 @@ __device__ __forceinline__ void sort_list(const HParams &p, K4sLds<C> &S, int64_
         }
         const uint64_t am = __ballot(alone);
         if (am) {
-            uint32_t wb = 0u;
-            if (lane == 0) wb = atomicAdd(&S.out, (uint32_t)__popcll(am));
-            wb = __builtin_amdgcn_readlane(wb, 0);  // (a v_readlane, where __shfl is a ds_bpermute)
+            const uint32_t o = wave_reserve(&S.out, am);
             if (alone) {
-                const uint32_t o = wb + (uint32_t)__popcll(am & lt);
                 if (staged) S.sk[nsk + o] = kh[j];  // (sk[0, nsk): the failing slots' keys)
                 else emit_pair(p, b0 + o, kh[j], 1u);
             }
@@ -1275,19 +1305,8 @@ __device__ __forceinline__ void sort_list(const HParams &p, K4sLds<C> &S, int64_
                 }
             }
         }
-        const uint64_t m = __ballot(first);
-        uint32_t wb = 0u;
-        if (lane == 0 && m) wb = atomicAdd(DIRECT ? &S.nres : &S.out, (uint32_t)__popcll(m));
-        wb = __builtin_amdgcn_readlane(wb, 0);
-        if (first) {
-            const uint32_t o = wb + (uint32_t)__popcll(m & lt);
-            if (DIRECT && o < rcap) {
-                S.sk[n + o] = h;  // (after the distinct slots' keys)
-                S.rc[o] = cnt;
-            } else {
-                emit_pair(p, b0 + (DIRECT ? na : 0u) + o, h, cnt);
-            }
-        }
+        const uint32_t o = wave_reserve(nres_at, __ballot(first));
+        if (first) put_result(o, h, cnt);
     }
     if (nhot) lds_barrier();  // (uniform) the loop above has read sk before the crowded slots' marks
     // crowded slots (a key repeated more than kSortMaxM times hashes there), one
@@ -1327,17 +1346,8 @@ __device__ __forceinline__ void sort_list(const HParams &p, K4sLds<C> &S, int64_
             const bool last = nx >= e;
             if ((nd & 63u) == 0u || last) {  // (uniform) this batch of results out
                 const uint32_t nb = ((nd - 1u) & 63u) + 1u;
-                uint32_t wb = 0u;
-                if (lane == 0) wb = atomicAdd(DIRECT ? &S.nres : &S.out, nb);
-                wb = __builtin_amdgcn_readlane(wb, 0);
-                if ((uint32_t)lane < nb) {
-                    if (DIRECT && wb + (uint32_t)lane < rcap) {
-                        S.sk[n + wb + (uint32_t)lane] = myk;
-                        S.rc[wb + (uint32_t)lane] = myc;
-                    } else {
-                        emit_pair(p, b0 + (DIRECT ? na : 0u) + wb + (uint32_t)lane, myk, myc);
-                    }
-                }
+                const uint32_t wb = wave_reserve_n(nres_at, nb);
+                if ((uint32_t)lane < nb) put_result(wb + (uint32_t)lane, myk, myc);
             }
             if (last) break;
             c = nx;
@@ -1352,7 +1362,7 @@ __device__ __forceinline__ void sort_list(const HParams &p, K4sLds<C> &S, int64_
         const uint32_t nres = S.nres, D = na + nres, Ds = na + (nres < rcap ? nres : rcap);
         if (tid == 0) {
             unsigned long long F;
-            const unsigned long long c = reserve_pairs(p, rec, D, &F);
+            const unsigned long long c = reserve_pairs(p, rec, D, F);
             bool fin = F != kUnknown;
             if (fin && F + c + D > p.win_cap) {  // (guard) past the caller's arrays: not written there
                 raise_err(p, kErrBound);
@@ -1372,7 +1382,9 @@ __device__ __forceinline__ void sort_list(const HParams &p, K4sLds<C> &S, int64_
                 // instead of one with a per-pair select of source and count, on
                 // pointers set up once (round 5, same box: C4 32.5-32.6 -> 31.9-32.0 ms,
                 // C4R 42.6-42.7 -> 41.9-42.0 ms, profiles/r05ax_k4s_writeout_loops_ab.txt;
-                // the issue-bound tail pays for every VALU op per pair)
+                // the issue-bound tail pays for every VALU op per pair).  A staged (h, cnt)
+                // never takes the pair format: what decode_pair gives of its encoding is
+                // feistel(h) and cnt, stored as such
                 uint64_t *ko = p.out_keys + g;
                 uint32_t *co = p.out_counts + g;
                 const unsigned long long *sa = S.sk + nsk;
@@ -1418,10 +1430,7 @@ __global__ __launch_bounds__(SortSmall::kBlock) __attribute__((amdgpu_waves_per_
         const uint32_t n = (uint32_t)(e0 - b0 < 0xFFFFFFFFull ? e0 - b0 : 0xFFFFFFFFull);
         const uint64_t *nxt = l + gridDim.x < l_hi ? p.list_start + l + gridDim.x : nullptr;
         if (n > p.sort_cap) {  // workgroup-uniform
-            if (!DIRECT && threadIdx.x == 0) {
-                if (n <= p.sort_cap_big) queue_list(p, p.big, p.nbig, l, b0, e0);
-                else defer_list(p, l, b0, e0);
-            }
+            if (!DIRECT && threadIdx.x == 0) push_list(p, n <= p.sort_cap_big ? p.big : p.defer, l, b0, e0);
             if (nxt) {
                 b0 = nxt[0];
                 e0 = nxt[1];
@@ -1444,17 +1453,18 @@ __global__ __launch_bounds__(SortBig::kBlock) void canon_sort_big_kernel(HParams
     __shared__ __attribute__((aligned(16))) K4sLds<SortBig> S;
     // DIRECT: one group of records per launch, its segment of the (list-ordered) queue
     const int64_t q_lo = DIRECT ? (int64_t)p.dist_off[p.l_lo] : 0;
-    const int64_t nl = DIRECT ? (int64_t)p.dist_off[p.l_hi] : (int64_t)*p.nbig;
-    if ((uint64_t)nl > (uint64_t)p.lists || q_lo > nl) {  // (guard)
+    const int64_t nl = list_count(p, DIRECT ? p.dist_off[p.l_hi] : *p.big.n);
+    if (q_lo > nl) {  // (guard; also where list_count refused the count)
         if (blockIdx.x == 0 && threadIdx.x == 0) raise_err(p, kErrBound);
         return;
     }
+    static_assert(offsetof(ListRef, end) == offsetof(ListRef, begin) + 8, "sort_list reads nxt[0], nxt[1]");
     for (int64_t i = q_lo + blockIdx.x; i < nl; i += gridDim.x) {
-        const uint64_t b0 = p.big[3 * i + 1], e0 = p.big[3 * i + 2];
+        const ListRef r = p.big.at[i];
         const int64_t in = i + gridDim.x;
         uint64_t nb0, ne0;  // (few lists here: the entries are reloaded per list)
-        sort_list<SortBig, DIRECT>(p, S, (int64_t)p.big[3 * i], b0, e0, (uint32_t)(e0 - b0),
-                                   in < nl ? p.big + 3 * in + 1 : nullptr, nb0, ne0);
+        sort_list<SortBig, DIRECT>(p, S, (int64_t)r.list, r.begin, r.end, (uint32_t)(r.end - r.begin),
+                                   in < nl ? &p.big.at[in].begin : nullptr, nb0, ne0);
     }
 }
 
@@ -1476,11 +1486,9 @@ __global__ __launch_bounds__(256) void canon_place_kernel(HParams p) {
         for (int u = 0; u < kPlaceU; ++u) {
             const uint64_t i = i0 + 256u * u;
             if (i < m) {
-                const uint32_t tag = (uint32_t)(x[u] >> 62);
-                const uint64_t key = feistel(x[u] & kM62);
-                const uint32_t cnt = tag < 3u ? tag + 1u : p.pc[src + i];
-                p.out_keys[dst + i] = key;
-                p.out_counts[dst + i] = cnt;
+                const KeyCount kc = decode_pair(p, src + i, x[u]);
+                p.out_keys[dst + i] = kc.key;
+                p.out_counts[dst + i] = kc.count;
             }
         }
     }
@@ -1512,48 +1520,36 @@ __global__ void canon_classify_kernel(HParams p) {
     const uint64_t b = p.list_start[l], e = p.list_start[l + 1];
     const bool big = e - b > (uint64_t)p.sort_cap && e - b <= (uint64_t)p.sort_cap_big;
     p.ndist[l] = big ? 1u : 0u;
-    if (e - b > (uint64_t)p.sort_cap && !big) defer_list(p, l, b, e);
+    if (e - b > (uint64_t)p.sort_cap && !big) push_list(p, p.defer, l, b, e);
 }
 
 __global__ void canon_big_queue_kernel(HParams p) {
     const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (l == p.lists) *p.nbig = p.dist_off[l];
+    if (l == p.lists) *p.big.n = p.dist_off[l];
     if (l >= p.lists || !p.ndist[l]) return;
-    const uint64_t i = p.dist_off[l];
-    p.big[3 * i] = (uint64_t)l;
-    p.big[3 * i + 1] = p.list_start[l];
-    p.big[3 * i + 2] = p.list_start[l + 1];
+    p.big.at[p.dist_off[l]] = ListRef{(uint64_t)l, p.list_start[l], p.list_start[l + 1]};
 }
 
 // Direct output, after every list: each record's start (exclusive scan of the
 // records' pair counts: the same values the chain published) -> rbase, rec_off.
-// One workgroup of 1 024 threads, 1 024 records per step.
-__global__ __launch_bounds__(1024) void canon_direct_final_kernel(HParams p) {
-    __shared__ unsigned long long ws[16];
-    __shared__ unsigned long long carry;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+// One workgroup of kScanBlock threads, that many records per step.
+__global__ __launch_bounds__(kScanBlock) void canon_direct_final_kernel(HParams p) {
+    __shared__ uint64_t ws[kScanBlock / 64];
+    __shared__ unsigned long long carry;  // the pairs of the steps before this one
+    const int tid = threadIdx.x;
     if (tid == 0) carry = 0ull;
     __syncthreads();
-    for (int64_t r0 = 0; r0 <= p.n; r0 += 1024) {
+    for (int64_t r0 = 0; r0 <= p.n; r0 += kScanBlock) {
         const int64_t r = r0 + tid;
-        const unsigned long long d = r < p.n ? (p.rstate[r] & kPairsMask) : 0ull;
-        unsigned long long x = d;  // inclusive scan over the wave
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long y = __shfl_up(x, o);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) ws[wv] = x;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (int v = 0; v < wv; ++v) before += ws[v];
-        const unsigned long long start = before + x - d;
+        const uint64_t d = r < p.n ? (p.rstate[r] & kPairsMask) : 0ull;
+        const unsigned long long before = carry;  // (every thread, ahead of the scan's barriers)
+        uint64_t total;
+        const unsigned long long start = before + block_excl_scan(d, ws, total);
         if (r <= p.n) {
             p.rbase[r] = start;
             p.rec_off[r] = start;
         }
-        __syncthreads();
-        if (tid == 1023) carry = start + d;
+        if (tid == 0) carry = before + total;
         __syncthreads();
     }
 }
@@ -1567,18 +1563,18 @@ __global__ __launch_bounds__(256) void canon_fallback_kernel(HParams p) {
         nq = 2 * p.lists;
     }
     for (int64_t q = blockIdx.x; q < nq; q += gridDim.x) {
-        const uint64_t src = p.fq[4 * q], r = p.fq[4 * q + 1], c = p.fq[4 * q + 2], m = p.fq[4 * q + 3];
+        const CopyRef c = p.fq[q];
+        const uint64_t src = c.src, r = c.rec, m = c.pairs;
         // (guard, workgroup-uniform) a record of the call, source and target inside their arrays
-        const uint64_t dst = r < (uint64_t)p.n ? p.rbase[r] + c : ~0ull;
+        const uint64_t dst = r < (uint64_t)p.n ? p.rbase[r] + c.off : ~0ull;
         if (r >= (uint64_t)p.n || src > p.win_cap || m > p.win_cap - src || dst > p.win_cap || m > p.win_cap - dst) {
             if (threadIdx.x == 0) raise_err(p, kErrBound);
             continue;
         }
         for (uint64_t i = threadIdx.x; i < m; i += 256) {
-            const unsigned long long x = p.pk[src + i];
-            const uint32_t tag = (uint32_t)(x >> 62);
-            p.out_keys[dst + i] = feistel(x & kM62);
-            p.out_counts[dst + i] = tag < 3u ? tag + 1u : p.pc[src + i];
+            const KeyCount kc = decode_pair(p, src + i, p.pk[src + i]);
+            p.out_keys[dst + i] = kc.key;
+            p.out_counts[dst + i] = kc.count;
         }
     }
 }
@@ -1790,22 +1786,21 @@ size_t canon_carve(const CanonPlan &P, int64_t n, void *base, HParams &p, uint64
     p.ndist = c.take<uint32_t>(L);
     p.dist_off = c.take<uint64_t>(L + 1);
     p.err = c.take<uint32_t>(1);
-    p.ndefer = c.take<unsigned long long>(1);
-    p.defer = c.take<uint64_t>(3 * L1);
-    p.nbig = c.take<unsigned long long>(1);
-    p.big = c.take<uint64_t>(3 * L1);
+    p.defer.n = c.take<unsigned long long>(1);
+    p.defer.at = c.take<ListRef>(L1);
+    p.big.n = c.take<unsigned long long>(1);
+    p.big.at = c.take<ListRef>(L1);
     // direct output (round 5)
     p.lrec = c.take<int32_t>(L1);
     p.rstate = c.take<unsigned long long>(n);
     p.rbase = c.take<unsigned long long>(n + 1);
     // (at most two copies per list: its distinct slots' keys and its results; a
     // list the table kernel counts has one)
-    p.fq = c.take<uint64_t>(2 * 4 * L1);
+    p.fq = c.take<CopyRef>(2 * L1);
     p.nfq = c.take<unsigned long long>(1);
-    p.ndefer2 = c.take<unsigned long long>(1);
-    p.defer2 = c.take<uint64_t>(3 * L1);
+    p.defer2.n = c.take<unsigned long long>(1);
+    p.defer2.at = c.take<ListRef>(L1);
     p.tq = p.defer;  // the table kernel's first launch
-    p.ntq = p.ndefer;
     return c.total();
 }
 
@@ -1846,8 +1841,8 @@ int upload_plan(const HParams &p, const CanonPlan &P, const std::vector<int64_t>
         (NF && (he = hipMemcpyAsync((void *)p.fsplit, P.fsplit.data(), NF * sizeof(int2), hipMemcpyHostToDevice,
                                     stream))))
         return (int)he;
-    if ((he = hipMemsetAsync(p.err, 0, 4, stream)) || (he = hipMemsetAsync(p.ndefer, 0, 8, stream)) ||
-        (he = hipMemsetAsync(p.nbig, 0, 8, stream)) || (he = hipMemsetAsync(p.ndefer2, 0, 8, stream)))
+    if ((he = hipMemsetAsync(p.err, 0, 4, stream)) || (he = hipMemsetAsync(p.defer.n, 0, 8, stream)) ||
+        (he = hipMemsetAsync(p.big.n, 0, 8, stream)) || (he = hipMemsetAsync(p.defer2.n, 0, 8, stream)))
         return (int)he;
 #ifdef KMC_DIAG_HOOKS
     {
@@ -1855,7 +1850,7 @@ int upload_plan(const HParams &p, const CanonPlan &P, const std::vector<int64_t>
         std::lock_guard<std::mutex> lk(h_mu);
         if (h_stale_queue >= 0) {
             stale = (unsigned long long)h_stale_queue;
-            if ((he = hipMemcpyAsync(p.ndefer2, &stale, 8, hipMemcpyHostToDevice, stream))) return (int)he;
+            if ((he = hipMemcpyAsync(p.defer2.n, &stale, 8, hipMemcpyHostToDevice, stream))) return (int)he;
         }
     }
 #endif
@@ -1907,18 +1902,18 @@ int diag_read_back(const HParams &p) {
     hipError_t he;
     unsigned long long ne = 0;
     if ((he = hipMemcpy(&ne, p.nfq, 8, hipMemcpyDeviceToHost))) return (int)he;
-    std::vector<uint64_t> q(4 * ne);
-    if (ne && (he = hipMemcpy(q.data(), p.fq, 32 * ne, hipMemcpyDeviceToHost))) return (int)he;
+    std::vector<CopyRef> q(ne);
+    if (ne && (he = hipMemcpy(q.data(), p.fq, sizeof(CopyRef) * ne, hipMemcpyDeviceToHost))) return (int)he;
     unsigned long long np = 0;
     std::vector<unsigned long long> per(p.n, 0);
-    for (unsigned long long i = 0; i < ne; ++i) {
-        np += q[4 * i + 3];
-        per[q[4 * i + 1]] += q[4 * i + 3];
+    for (const CopyRef &c : q) {
+        np += c.pairs;
+        per[c.rec] += c.pairs;
     }
     unsigned long long dq[3] = {0, 0, 0};
-    if ((he = hipMemcpy(&dq[0], p.nbig, 8, hipMemcpyDeviceToHost)) ||
-        (he = hipMemcpy(&dq[1], p.ndefer, 8, hipMemcpyDeviceToHost)) ||
-        (he = hipMemcpy(&dq[2], p.ndefer2, 8, hipMemcpyDeviceToHost)))
+    if ((he = hipMemcpy(&dq[0], p.big.n, 8, hipMemcpyDeviceToHost)) ||
+        (he = hipMemcpy(&dq[1], p.defer.n, 8, hipMemcpyDeviceToHost)) ||
+        (he = hipMemcpy(&dq[2], p.defer2.n, 8, hipMemcpyDeviceToHost)))
         return (int)he;
     std::lock_guard<std::mutex> lk(h_mu);
     h_fb_entries = ne;
@@ -1972,9 +1967,8 @@ int run_direct(const HParams &p, const CanonPlan &P, const std::vector<int64_t> 
     }
     HParams p2 = p;  // the lists both K4s instances handed back (defer2)
     p2.tq = p.defer2;
-    p2.ntq = p.ndefer2;
     hipLaunchKernelGGL(canon_table_kernel, g_table, dim3(kCountBlock), 0, stream, p2);
-    hipLaunchKernelGGL(canon_direct_final_kernel, dim3(1), dim3(1024), 0, stream, p);
+    hipLaunchKernelGGL(canon_direct_final_kernel, dim3(1), dim3(kScanBlock), 0, stream, p);
     hipLaunchKernelGGL(canon_fallback_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(L, 4096))),
                        dim3(256), 0, stream, p);
     uint64_t distinct = 0;
