@@ -17,6 +17,7 @@ extern "C" const char *kmc_error_string(int code) {
         case KMC_ERR_CAPACITY: return "output capacity smaller than the result";
         case KMC_ERR_RECORD_TOO_LONG: return "a record has 2^31 or more windows in one call: int32 counts could wrap";
         case KMC_ERR_INTERNAL: return "a device-side bound check fired (library defect): outputs not valid";
+        case KMC_ERR_FORMAT: return "input is not well-formed FASTQ";
         default: return hipGetErrorString(static_cast<hipError_t>(code));
     }
 }

@@ -19,23 +19,19 @@
 // kept-byte count, write.
 #include <hip/hip_runtime.h>
 
-#include <fcntl.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <cstdint>
 
 #include "kmc.h"
 #include "kmc_scan.h"
+#include "kmc_stage.h"
 #include "kmc_stream.h"
+#include "kmc_text.h"
 #include "kmc_workspace.h"
 
 namespace kmc {
 namespace {
 
-constexpr int kFpBlock = 256;
-constexpr int kFpPer = 64;                        // raw bytes per thread
-constexpr int64_t kFpTile = kFpBlock * kFpPer;    // 16 KiB per block
 constexpr int kLsPer = 16;                        // lines per thread in the line scan
 constexpr int64_t kLsTile = (int64_t)kFpBlock * kLsPer;
 
@@ -88,61 +84,11 @@ struct FParams {
     uint64_t *result;     // [2]: records, data bytes
 };
 
-// a thread's 64 raw bytes as 16 little-endian words (bytes past n read as 0)
-__device__ __forceinline__ void load64(const FParams &p, int64_t q, uint32_t w[16]) {
-    if (q + kFpPer <= p.n) {
-        const uint4 *s = reinterpret_cast<const uint4 *>(p.raw + q);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint4 v = s[i];
-            w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) w[i] = 0u;
-        for (int i = 0; i < kFpPer; ++i)
-            if (q + i < p.n) w[i >> 2] |= (uint32_t)p.raw[q + i] << (8 * (i & 3));
-    }
-}
-
-__device__ __forceinline__ uint32_t nl_bits(uint32_t x) {  // bit 8i+7 set iff byte i == '\n'
-    const uint32_t y = x ^ 0x0A0A0A0Au;
-    return ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y) & 0x80808080u;
-}
-
-__device__ __forceinline__ uint32_t count_nl(const uint32_t w[16]) {
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) c += __popc(nl_bits(w[i]));
-    return c;
-}
-
-// block exclusive sum of a per-thread value (kFpBlock threads); total returned
-__device__ __forceinline__ uint32_t block_excl_u32(uint32_t v, uint32_t *sh, uint32_t &total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) sh[wid] = x;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-    for (int i = 0; i < kFpBlock / 64; ++i) {
-        if (i < wid) before += sh[i];
-        total += sh[i];
-    }
-    __syncthreads();
-    return before + x - v;
-}
-
 // 1. newlines per tile
 __global__ __launch_bounds__(kFpBlock) void fp_count_kernel(FParams p) {
     __shared__ uint32_t sh[kFpBlock / 64];
     uint32_t w[16];
-    load64(p, (int64_t)blockIdx.x * kFpTile + (int64_t)threadIdx.x * kFpPer, w);
+    load64(p.raw, p.n, (int64_t)blockIdx.x * kFpTile + (int64_t)threadIdx.x * kFpPer, w);
     uint32_t total;
     block_excl_u32(count_nl(w), sh, total);
     if (threadIdx.x == 0) p.tile_nl[blockIdx.x] = total;
@@ -174,7 +120,7 @@ __global__ __launch_bounds__(kFpBlock) void fp_class_kernel(FParams p) {
     __shared__ uint32_t sh[kFpBlock / 64];
     const int64_t q = (int64_t)blockIdx.x * kFpTile + (int64_t)threadIdx.x * kFpPer;
     uint32_t w[16];
-    load64(p, q, w);
+    load64(p.raw, p.n, q, w);
     const uint64_t l0 = thread_first_line(p, w, sh);
     const uint32_t hdr = p.dialect == 1 ? kFnHdr1 : kFnHdr0;
     walk(p, q, w, l0, [&](int64_t, uint32_t b, uint64_t line, bool start) {
@@ -271,7 +217,7 @@ __global__ __launch_bounds__(kFpBlock) void fp_keep_kernel(FParams p) {
     __shared__ uint32_t sh[kFpBlock / 64];
     const int64_t q = (int64_t)blockIdx.x * kFpTile + (int64_t)threadIdx.x * kFpPer;
     uint32_t w[16];
-    load64(p, q, w);
+    load64(p.raw, p.n, q, w);
     const uint64_t l0 = thread_first_line(p, w, sh);
     uint32_t kept, opens, tk, to;
     keep_counts(p, q, w, l0, kept, opens);
@@ -290,7 +236,7 @@ __global__ __launch_bounds__(kFpBlock) void fp_write_kernel(FParams p) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[kFpTile + 8];
     const int64_t q = (int64_t)blockIdx.x * kFpTile + (int64_t)threadIdx.x * kFpPer;
     uint32_t w[16];
-    load64(p, q, w);
+    load64(p.raw, p.n, q, w);
     const uint64_t l0 = thread_first_line(p, w, sh);
     uint32_t kept, opens, tk, to;
     keep_counts(p, q, w, l0, kept, opens);
@@ -315,19 +261,7 @@ __global__ __launch_bounds__(kFpBlock) void fp_write_kernel(FParams p) {
         }
     });
     __syncthreads();
-    // stage[shift + i] is output byte ob + i, i < tk
-    const uint64_t gbeg = ob, gend = ob + tk;
-    const uint64_t d0 = (gbeg + 3) >> 2, d1 = gend >> 2;  // whole output dwords [d0, d1)
-    const uint32_t *st32 = reinterpret_cast<const uint32_t *>(stage);
-    uint32_t *out32 = reinterpret_cast<uint32_t *>(p.out);
-    const uint64_t sbase = gbeg & ~(uint64_t)3;  // output address of stage[0]
-    for (uint64_t d = d0 + threadIdx.x; d < d1; d += kFpBlock) out32[d] = st32[(d * 4 - sbase) >> 2];
-    if (threadIdx.x == 0) {
-        const uint64_t hend = std::min<uint64_t>(d0 * 4, gend);
-        for (uint64_t g = gbeg; g < hend; ++g) p.out[g] = stage[g - sbase];
-        const uint64_t tbeg = std::max<uint64_t>(d1 * 4, hend);
-        for (uint64_t g = tbeg; g < gend; ++g) p.out[g] = stage[g - sbase];
-    }
+    store_staged(p.out, stage, ob, tk);  // stage[shift + i] is output byte ob + i, i < tk
 }
 
 // 6. end of input: close a record left open (or closed by a last line without
@@ -476,58 +410,13 @@ extern "C" int kmc_fasta_load_device(const char *path, int dialect, int64_t max_
     *indices = nullptr;
     *data_bytes = 0;
     *num_seqs = 0;
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) return KMC_ERR_IO;
-    const off_t size = lseek(fd, 0, SEEK_END);
-    if (size < 0 || lseek(fd, 0, SEEK_SET) != 0) {
-        close(fd);
-        return KMC_ERR_IO;
-    }
-    const uint64_t n = (uint64_t)size;
     // the raw bytes -> device through two pinned staging buffers (the read of
     // chunk i+1 overlaps the copy of chunk i)
     char *raw = nullptr;
-    hipError_t he = hipMalloc(&raw, n + 16);
-    if (he != hipSuccess) {
-        close(fd);
-        return KMC_ERR_NOMEM;
-    }
-    constexpr size_t kChunk = 64u << 20;
-    char *pin[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
-    int rc = 0;
-    for (int b = 0; b < 2 && !rc; ++b) {
-        if (hipHostMalloc(&pin[b], kChunk, hipHostMallocDefault) != hipSuccess) rc = KMC_ERR_NOMEM;
-        else if (hipEventCreateWithFlags(&done[b], hipEventDisableTiming) != hipSuccess) rc = KMC_ERR_NOMEM;
-    }
-    uint64_t i = 0;
-    for (uint64_t off = 0; off < n && !rc; off += kChunk, ++i) {
-        const int b = (int)(i & 1);
-        if (i >= 2 && (he = hipEventSynchronize(done[b])) != hipSuccess) {
-            rc = (int)he;
-            break;
-        }
-        const size_t want = (size_t)std::min<uint64_t>(kChunk, n - off);
-        size_t got = 0;
-        while (got < want) {
-            const ssize_t r = read(fd, pin[b] + got, want - got);
-            if (r <= 0) {
-                rc = KMC_ERR_IO;
-                break;
-            }
-            got += (size_t)r;
-        }
-        if (rc) break;
-        if ((he = hipMemcpyAsync(raw + off, pin[b], want, hipMemcpyHostToDevice, stream)) ||
-            (he = hipEventRecord(done[b], stream)))
-            rc = (int)he;
-    }
-    close(fd);
-    if (!rc && (he = hipStreamSynchronize(stream))) rc = (int)he;
-    for (int b = 0; b < 2; ++b) {
-        if (done[b]) (void)hipEventDestroy(done[b]);
-        if (pin[b]) (void)hipHostFree(pin[b]);
-    }
+    uint64_t n = 0;
+    hipError_t he = hipSuccess;
+    int rc = stage_file(path, &raw, &n, stream);
+    if (rc) return rc;
     if (!rc && hipMalloc(data, n + 16) != hipSuccess) rc = KMC_ERR_NOMEM;
     bool capped = false;
     auto get_idx = [&](uint64_t nrec) -> int64_t * {

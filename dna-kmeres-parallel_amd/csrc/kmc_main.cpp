@@ -23,7 +23,10 @@
 // sketches are searched in, kmc_sketch_nearest -> query_results.tsv, or with --top 0
 // kmc_sketch_distances_rect -> query_distances.csv; --screen FILE: the input files are references
 // looked for among all k-mers of FILE, a read set or metagenome, kmc_sketch_screen_* ->
-// screen_results.tsv).  GPU only: there is no CPU counting path here.
+// screen_results.tsv).  Inputs may be FASTQ (--format, or a .fq / .fastq name):
+// kmc_fastq_load_device, and a --screen FILE in FASTQ is streamed batch by batch
+// (kmc_fastq_open / _next / _close), so its size is not bounded by device memory.
+// GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +35,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <strings.h>
 #include <memory>
 #include <string>
 #include <thread>
@@ -70,7 +74,19 @@ struct Options {
     bool top_set = false, min_shared_set = false;
     std::vector<std::string> screen;  // --screen FILE (repeatable): the mixtures the inputs are looked for in
     std::vector<std::string> more_inputs;  // the input files after the first
+    int format = 0;             // --format: 0 auto (by file name), 1 fasta, 2 fastq
+    uint64_t screen_batch = 0;  // --screen-batch BYTES (0: the reader's default, 256 MiB)
 };
+
+// auto: FASTQ exactly when the name ends in .fq or .fastq, whatever the case
+bool is_fastq(const Options &o, const std::string &path) {
+    if (o.format) return o.format == 2;
+    for (const char *ext : {".fq", ".fastq"}) {
+        const size_t n = strlen(ext);
+        if (path.size() >= n && strcasecmp(path.c_str() + path.size() - n, ext) == 0) return true;
+    }
+    return false;
+}
 
 void usage(FILE *f) {
     fprintf(f,
@@ -78,6 +94,7 @@ void usage(FILE *f) {
             "       kmc --canonical --sketch S --sketch-direct --per-file [options] <a.fasta> <b.fasta> ...\n"
             "       kmc --canonical --sketch S --sketch-direct --query q.fasta [--top T] [options] <refs.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --screen reads.fasta [--screen ...] [options] <refs.fasta>\n"
+            "       kmc --canonical --sketch S --sketch-direct --screen reads.fastq [--screen-batch BYTES] [options] <refs.fasta>\n"
             "       kmc synth OUT.fa RECORDS LENGTH [SEED]   (benchmark input, SURVEY.md 8(d))\n"
             "  -k K              k-mer length (default %d, the reference's K); dense path 1..%d,\n"
             "                    --canonical 1..%d\n"
@@ -139,6 +156,16 @@ void usage(FILE *f) {
             "                    (shared: sketch values found; median: their median multiplicity; identity:\n"
             "                    (shared/size)^(1/k)), and <TAB>path with --per-file; sketch_results.csv is\n"
             "                    not written\n"
+            "  --format F        auto (default), fasta or fastq, for every file of the command.  auto: a file\n"
+            "                    whose name ends in .fq or .fastq (any case) is FASTQ, every other FASTA.\n"
+            "                    FASTQ is strict four-line FASTQ (kmc_fastq_load_device: records are the\n"
+            "                    sequence lines verbatim; --max-seqs N keeps the first N records; --dialect\n"
+            "                    does not apply); a malformed file ends the run with its record index.\n"
+            "                    Not with --host-loader, --gpus above 1 or --dropin\n"
+            "  --screen-batch B  with --screen: a FASTQ FILE is streamed in batches of B raw bytes\n"
+            "                    (kmc_fastq_open / _next / _close, one kmc_sketch_screen_count per batch), so it\n"
+            "                    is never resident as a whole and may be a pipe (--format fastq --screen\n"
+            "                    /dev/stdin); default 0: 256 MiB.  FASTA FILEs are read whole as before\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
@@ -208,6 +235,16 @@ int parse(int argc, char **argv, Options &o) {
         } else if (a == "--min-shared") {
             o.min_shared = atol(next("--min-shared"));
             o.min_shared_set = true;
+        } else if (a == "--format") {
+            const std::string f = next("--format");
+            if (f == "auto") o.format = 0;
+            else if (f == "fasta") o.format = 1;
+            else if (f == "fastq") o.format = 2;
+            else return fprintf(stderr, "kmc: unknown format '%s' (auto, fasta, fastq)\n", f.c_str()), 2;
+        } else if (a == "--screen-batch") {
+            const long long b = atoll(next("--screen-batch"));
+            if (b < 0 || b >= (1ll << 32)) return fprintf(stderr, "kmc: --screen-batch must be in 0..2^32-1\n"), 2;
+            o.screen_batch = (uint64_t)b;
         } else if (a == "--softmask") {
             o.softmask = true;
         } else if (a == "--host-loader") {
@@ -269,7 +306,21 @@ int parse(int argc, char **argv, Options &o) {
         fprintf(stderr, "kmc: --top must be in 0..%d, --min-shared in 0..%u\n", KMC_NEAREST_MAX_TOP, UINT32_MAX);
         return usage(stderr), 2;
     }
+    if (o.screen_batch && o.screen.empty()) {
+        fprintf(stderr, "kmc: --screen-batch sets the batches of --screen\n");
+        return usage(stderr), 2;
+    }
     if (o.gpus < 1) return fprintf(stderr, "kmc: --gpus must be >= 1\n"), 2;
+    if (o.host_loader || o.gpus > 1 || o.dropin) {  // the paths that need the host FASTA loader's buffer
+        std::vector<std::string> files{o.input};
+        files.insert(files.end(), o.more_inputs.begin(), o.more_inputs.end());
+        files.insert(files.end(), o.screen.begin(), o.screen.end());
+        if (!o.query.empty()) files.push_back(o.query);
+        for (const std::string &f : files)
+            if (is_fastq(o, f))
+                return fprintf(stderr, "kmc: %s: FASTQ input is not read with --host-loader, --gpus above 1 or --dropin\n",
+                               f.c_str()), 2;
+    }
     if (o.gpus > 1 && (o.dropin || o.canonical))
         return fprintf(stderr, "kmc: --gpus > 1 is for the dense path\n"), 2;
     return 0;
@@ -344,11 +395,13 @@ struct DevFree { void operator()(void *p) const { (void)hipFree(p); } };
 struct StreamDestroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
 struct EventDestroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
 struct FastaFree { void operator()(kmc_fasta *f) const { kmc_fasta_free(f); } };
+struct FastqClose { void operator()(kmc_fastq_reader *r) const { kmc_fastq_close(r); } };
 template <class T>
 using DevBuf = std::unique_ptr<T, DevFree>;
 using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
 using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
 using Fasta = std::unique_ptr<kmc_fasta, FastaFree>;
+using FastqReader = std::unique_ptr<kmc_fastq_reader, FastqClose>;
 
 // max(count, 1) elements: an empty input still gets a pointer the entry points take
 template <class T>
@@ -374,11 +427,25 @@ struct Records {
     uint64_t n = 0, bytes = 0;
 };
 
-// parsed on the GPU from the raw file bytes, or parsed on the host and copied
+int malformed(const std::string &path, uint64_t record) {
+    return fprintf(stderr, "kmc: %s: malformed FASTQ at record %" PRIu64 "\n", path.c_str(), record), 1;
+}
+
+// parsed on the GPU from the raw file bytes (FASTA or FASTQ), or FASTA parsed on the host and copied
 int load(const Options &o, hipStream_t st, Records &r) {
     const bool host = o.host_loader || o.gpus > 1;
     const auto tl0 = std::chrono::steady_clock::now();
-    if (host) {
+    if (is_fastq(o, o.input)) {
+        char *d_data = nullptr;
+        int64_t *d_idx = nullptr;
+        const int rc = kmc_fastq_load_device(o.input.c_str(), o.max_seqs, &d_data, &r.bytes, &d_idx, &r.n, st);
+        if (rc == KMC_ERR_FORMAT) return malformed(o.input, r.n);
+        KMCCHK(rc);
+        r.data.reset(d_data);
+        r.idx.reset(d_idx);
+        r.hidx.resize(r.n + 1);
+        HIPCHK(hipMemcpy(r.hidx.data(), d_idx, (r.n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    } else if (host) {
         kmc_fasta *fa = nullptr;
         KMCCHK(kmc_fasta_load(o.input.c_str(), o.dialect, o.max_seqs, &fa));
         r.fa.reset(fa);
@@ -625,6 +692,36 @@ int run_screen(const Options &o, hipStream_t st) {
         printf("Screen index (%" PRIu64 " references, s=%u, %zu bytes): %.3f ms\n", n, s, index_bytes,
                ms_between(b0.get(), b1.get()));
     for (const std::string &path : o.screen) {
+        if (is_fastq(o, path)) {
+            // streamed: every batch is counted on st behind its parse, and the next batch's writes
+            // are ordered behind that count, so the host reads ahead while the GPU counts
+            kmc_fastq_reader *rd = nullptr;
+            const int orc = kmc_fastq_open(path.c_str(), o.screen_batch, &rd);
+            if (orc) return fprintf(stderr, "kmc: %s: %s\n", path.c_str(), kmc_error_string(orc)), 1;
+            const FastqReader reader(rd);
+            uint64_t records = 0, bytes = 0, batches = 0;
+            const auto w0 = std::chrono::steady_clock::now();
+            for (;;) {
+                const char *d_data = nullptr;
+                const int64_t *d_idx = nullptr;
+                uint64_t nb = 0, ns = 0;
+                const int rc = kmc_fastq_next(rd, &d_data, &nb, &d_idx, &ns, st);
+                if (rc == KMC_ERR_FORMAT) return malformed(path, ns);
+                KMCCHK(rc);
+                if (!d_data) break;
+                KMCCHK(kmc_sketch_screen_count(d_index.get(), index_bytes, d_data, d_idx, ns, nb, o.k, flags,
+                                               KMC_SKETCH_DEFAULT_SEED, st));
+                records += ns;
+                bytes += nb;
+                ++batches;
+            }
+            HIPCHK(hipStreamSynchronize(st));  // before the reader's buffers go
+            if (!o.quiet)
+                printf("Screen: %s: %" PRIu64 " records, %" PRIu64 " bytes, %" PRIu64 " batches: %.3f ms\n", path.c_str(),
+                       records, bytes, batches,
+                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count());
+            continue;
+        }
         Options of = o;
         of.input = path;
         of.max_seqs = 0;

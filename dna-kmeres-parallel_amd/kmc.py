@@ -42,12 +42,17 @@ DROPIN_K = 3
 KMC_ERR_CAPACITY = 1009
 KMC_ERR_RECORD_TOO_LONG = 1010
 KMC_ERR_INTERNAL = 1011
+KMC_ERR_FORMAT = 1012
 
 
 class KmcError(RuntimeError):
-    def __init__(self, code, what):
+    """`record`: with KMC_ERR_FORMAT the 0-based index of the malformed record, else None."""
+
+    def __init__(self, code, what, record=None):
         self.code = code
-        super().__init__("%s failed: %s (%d)" % (what, error_string(code), code))
+        self.record = record
+        at = " at record %d" % record if record is not None else ""
+        super().__init__("%s failed: %s%s (%d)" % (what, error_string(code), at, code))
 
 
 _P = ctypes.c_void_p
@@ -182,6 +187,15 @@ def _load(path):
                                          ctypes.POINTER(_U64), _P]
     L.kmc_fasta_load_device.argtypes = [ctypes.c_char_p, ctypes.c_int, _I64, ctypes.POINTER(_P),
                                         ctypes.POINTER(_U64), ctypes.POINTER(_P), ctypes.POINTER(_U64), _P]
+    L.kmc_fastq_parse_device.argtypes = [_P, _U64, ctypes.c_int, _P, _U64, _P, _U64, ctypes.POINTER(_U64),
+                                         ctypes.POINTER(_U64), ctypes.POINTER(_U64), _P]
+    L.kmc_fastq_load_device.argtypes = [ctypes.c_char_p, _I64, ctypes.POINTER(_P), ctypes.POINTER(_U64),
+                                        ctypes.POINTER(_P), ctypes.POINTER(_U64), _P]
+    L.kmc_fastq_open.argtypes = [ctypes.c_char_p, _U64, ctypes.POINTER(_P)]
+    L.kmc_fastq_next.argtypes = [_P, ctypes.POINTER(_P), ctypes.POINTER(_U64), ctypes.POINTER(_P),
+                                 ctypes.POINTER(_U64), _P]
+    L.kmc_fastq_close.argtypes = [_P]
+    L.kmc_fastq_close.restype = None
     L.kmc_pair_distances_workspace_size.restype = ctypes.c_size_t
     L.kmc_pair_distances_workspace_size.argtypes = [_U64, ctypes.c_int, ctypes.c_int]
     L.kmc_pair_distances.argtypes = [_P, _U64, _P, _U64, ctypes.c_int, _P, _P, ctypes.c_size_t, _P]
@@ -227,9 +241,9 @@ def error_string(code):
     return lib().kmc_error_string(int(code)).decode()
 
 
-def _check(rc, what):
+def _check(rc, what, record=None):
     if rc != 0:
-        raise KmcError(rc, what)
+        raise KmcError(rc, what, int(record) if rc == KMC_ERR_FORMAT and record is not None else None)
 
 
 def header_symbols(path=HEADER):
@@ -803,6 +817,144 @@ def load_fasta_device(path, dialect=DIALECT_BLANK, max_seqs=MAX_SEQS_REFERENCE, 
     hip.hipFree(d)
     hip.hipFree(ix)
     return data, idx
+
+
+def _copy_out(d, nbytes, ix, nseqs, free):
+    """New torch tensors (data uint8 [nbytes], indices int64 [nseqs + 1]) on the current
+    device holding the library's buffers d and ix, which are freed when `free`."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    data = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    idx = torch.empty(nseqs + 1, dtype=torch.int64, device=dev)
+    hip = _hip()
+    if nbytes:
+        _check(hip.hipMemcpy(_P(data.data_ptr()), d, nbytes, 3), "hipMemcpy")
+    _check(hip.hipMemcpy(_P(idx.data_ptr()), ix, (nseqs + 1) * 8, 3), "hipMemcpy")
+    if free:
+        hip.hipFree(d)
+        hip.hipFree(ix)
+    return data, idx
+
+
+# ---------------------------------------------------------------------------
+# FASTQ (strict four-line; include/kmc.h)
+# ---------------------------------------------------------------------------
+def parse_fastq_device(raw, final=True, stream=None):
+    """GPU FASTQ parse (kmc_fastq_parse_device) of raw bytes in a uint8 device tensor:
+    (data uint8 tensor, indices int64 tensor [n+1], consumed) for the complete
+    records of raw; without `final` the bytes from `consumed` on belong to a record
+    that is not complete yet.  KmcError.record tells where malformed input is."""
+    import torch
+    n = int(raw.numel())
+    with _on(stream):
+        if n % 16 or raw.data_ptr() % 16:  # the kernel reads whole 16-byte pieces of raw
+            pad = torch.zeros(n + 16 - n % 16, dtype=torch.uint8, device=raw.device)
+            pad[:n] = raw
+            raw = pad
+        cap_data = n // 2 + 1
+        data = torch.empty(cap_data + 16, dtype=torch.uint8, device=raw.device)
+    cap = 1024
+    while True:
+        with _on(stream):
+            idx = torch.empty(cap, dtype=torch.int64, device=raw.device)
+        ns, nb, used = _U64(0), _U64(0), _U64(0)
+        rc = lib().kmc_fastq_parse_device(_dptr(raw) if n else None, n, 1 if final else 0, _dptr(data), cap_data,
+                                          _dptr(idx), cap, ctypes.byref(ns), ctypes.byref(nb), ctypes.byref(used),
+                                          _stream(stream))
+        if rc == KMC_ERR_CAPACITY and ns.value + 1 > cap:
+            cap = int(ns.value) + 1
+            continue
+        _check(rc, "kmc_fastq_parse_device", ns.value)
+        return data[:nb.value], idx[:ns.value + 1], int(used.value)
+
+
+def load_fastq_device(path, max_seqs=0, stream=None):
+    """kmc_fastq_load_device: (data uint8 tensor, indices int64 tensor [n+1]) on the
+    current device (copies of the library's buffers, which are freed here);
+    max_seqs > 0 keeps the first max_seqs records."""
+    L = lib()
+    d, ix = _P(), _P()
+    nb, ns = _U64(0), _U64(0)
+    _check(L.kmc_fastq_load_device(os.fsencode(path), max_seqs, ctypes.byref(d), ctypes.byref(nb), ctypes.byref(ix),
+                                   ctypes.byref(ns), _stream(stream)), "kmc_fastq_load_device", ns.value)
+    return _copy_out(d, nb.value, ix, ns.value, True)
+
+
+class FastqReader:
+    """kmc_fastq_open / _next / _close: a FASTQ file of any size (or a pipe) as batches
+    of about batch_bytes raw bytes (0: 256 MiB).  next_batch() returns (data,
+    indices) or None after the last batch; iterating yields the batches.  By default
+    a batch is a pair of new tensors (copies); with copy=False it is a pair of views
+    of the reader's own buffers, valid until the next call, whose writes are ordered
+    on `stream` behind whatever the caller enqueued there.
+
+        with kmc.FastqReader(path, 1 << 28) as rd:
+            for data, indices in rd:
+                kmc.sketch_screen_count(index, data, indices, k)"""
+
+    def __init__(self, path, batch_bytes=0, stream=None, copy=True):
+        self._h = _P()
+        self._stream = stream
+        self._copy = copy
+        self._views = None
+        _check(lib().kmc_fastq_open(os.fsencode(path), int(batch_bytes), ctypes.byref(self._h)), "kmc_fastq_open")
+
+    def next_batch(self):
+        if not self._h:
+            raise ValueError("the reader is closed")
+        d, ix = _P(), _P()
+        nb, ns = _U64(0), _U64(0)
+        rc = lib().kmc_fastq_next(self._h, ctypes.byref(d), ctypes.byref(nb), ctypes.byref(ix), ctypes.byref(ns),
+                                  _stream(self._stream))
+        _check(rc, "kmc_fastq_next", ns.value)
+        if not d.value:
+            return None
+        if self._copy:
+            return _copy_out(d, nb.value, ix, ns.value, False)
+        self._views = (_DeviceView(d.value, nb.value, "|u1").tensor(), _DeviceView(ix.value, ns.value + 1, "<i8").tensor())
+        return self._views
+
+    def close(self):
+        if self._h:
+            lib().kmc_fastq_close(self._h)
+            self._h = _P()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        b = self.next_batch()
+        if b is None:
+            raise StopIteration
+        return b
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        self.close()
+
+
+class _DeviceView:
+    """A device buffer the library owns as a torch tensor, without a copy
+    (__cuda_array_interface__); count elements of numpy typestr `typestr`."""
+
+    def __init__(self, ptr, count, typestr):
+        self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": typestr, "data": (int(ptr), False),
+                                         "version": 2}
+        self._count = int(count)
+        self._typestr = typestr
+
+    def tensor(self):
+        import torch
+        if self._count == 0:
+            return torch.empty(0, dtype=torch.uint8 if self._typestr == "|u1" else torch.int64,
+                               device=torch.device("cuda", torch.cuda.current_device()))
+        return torch.as_tensor(self, device=torch.device("cuda", torch.cuda.current_device()))
 
 
 _hip_lib = None

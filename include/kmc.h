@@ -8,8 +8,9 @@
  * are >= 1000).  Every device entry point is asynchronous on the given stream
  * and never calls exit(); the ones that return a size to the host say
  * "Synchronous" in their own comment (kmc_count_canonical_hash[_ex],
- * kmc_fasta_parse_device, kmc_fasta_load_device, and kmc_count_multi, which
- * takes host buffers).
+ * kmc_fasta_parse_device, kmc_fasta_load_device, kmc_fastq_parse_device,
+ * kmc_fastq_load_device, kmc_fastq_next, and kmc_count_multi, which takes host
+ * buffers).
  *
  * Count layout (identical to the reference, kernels.h:142): int32
  * sum[s + ld*code] ("k-mer-major, record-minor"), ld = num_seqs unless stated,
@@ -69,8 +70,9 @@ enum kmc_status {
     KMC_ERR_NO_DEVICE = 1008,     /* no HIP device visible */
     KMC_ERR_CAPACITY = 1009,      /* caller output smaller than the result (size reported) */
     KMC_ERR_RECORD_TOO_LONG = 1010, /* a record has >= 2^31 windows in one dense call: int32 counts could wrap */
-    KMC_ERR_INTERNAL = 1011         /* a device-side bound check fired (a library defect): the access was
+    KMC_ERR_INTERNAL = 1011,        /* a device-side bound check fired (a library defect): the access was
                                        skipped and the call's outputs are not valid (kmc_count_canonical_hash) */
+    KMC_ERR_FORMAT = 1012           /* input is not well-formed FASTQ (kmc_fastq_*: the record's index is reported) */
 };
 
 /* Human-readable text for a kmc_status or hipError_t code (static storage). */
@@ -715,6 +717,96 @@ KMC_API int kmc_fasta_parse_device(const char *raw, uint64_t raw_bytes, int dial
  * Synchronous on `stream`. */
 KMC_API int kmc_fasta_load_device(const char *path, int dialect, int64_t max_seqs, char **data, uint64_t *data_bytes,
                           int64_t **indices, uint64_t *num_seqs, hipStream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* FASTQ (no reference counterpart: read sets come off sequencers in this format).
+ * Strict four-line FASTQ.  The input is split into lines on '\n'; one '\r' directly
+ * before the '\n' is not part of the line, nor is a '\r' at the very end of a final
+ * input that has no last '\n'.  Bytes after the last '\n' are a line when there are
+ * any.  Record r is lines 4r .. 4r+3:
+ *   4r    starts with '@' (the rest is ignored)
+ *   4r+1  the sequence; may be empty
+ *   4r+2  starts with '+' (the rest is ignored)
+ *   4r+3  the quality, as long as the sequence
+ * Multi-line FASTQ is refused, not guessed at: it breaks a rule above, or nobody can
+ * tell it from four-line FASTQ.  Output follows the record convention above: record
+ * r occupies data[indices[r] .. indices[r+1]), the sequence bytes verbatim, then one
+ * '\0'.  No case folding and no '|' mapping (that is the reference's FASTA quirk): N
+ * and lowercase bytes stay, and the counting rules and KMC_CANON_SOFTMASK decide
+ * about them.  A record is complete when its fourth line is ended by '\n'; in a
+ * final input also when that line runs to the end of the input.  In a final input
+ * the lines after the last complete record must all be empty.
+ *
+ * kmc_fastq_parse_device: the complete records of raw[0, raw_bytes), on the GPU.
+ *   raw       device, 16-byte aligned, raw_bytes < 2^33 bytes of FASTQ text
+ *   final     non-zero: no more input follows raw (the last piece of a file)
+ *   data      device, 4-byte aligned, capacity data_cap; data_cap >= raw_bytes / 2 + 1
+ *             always suffices (a record's raw text is at least 2 len + 5 bytes) and a
+ *             smaller one is refused: KMC_ERR_CAPACITY
+ *   indices   device int64[indices_cap]; *num_seqs + 1 entries are written
+ *   *consumed the raw offset just past the last complete record's last line;
+ *             raw_bytes on success when final.  Without `final`, what follows the
+ *             last complete record is left unconsumed and is not judged; no
+ *             complete record (*consumed == 0, *num_seqs == 0) is a valid result.
+ * KMC_ERR_CAPACITY, with *num_seqs set and nothing written, when indices_cap <
+ * *num_seqs + 1.  raw_bytes == 0: KMC_OK, no record, indices[0] = 0.  Every complete
+ * record is judged on the device before anything is written to data or indices, so
+ * malformed input never overruns data_cap: KMC_ERR_FORMAT, *num_seqs the smallest
+ * 0-based index of a record that breaks a rule, or the number of complete records
+ * when only the leftover lines of a final input are at fault; nothing else is
+ * promised about the outputs then.  KMC_ERR_INVALID_ARG (null pointers, raw_bytes
+ * of 2^33 or more), KMC_ERR_ALIGNMENT and the data_cap refusal are returned before
+ * any device is touched.  Synchronous on `stream`; library-owned scratch under
+ * kmc_fasta_parse_device's rule (calls on a device must not overlap), 8 B per line
+ * and 4 B per record. */
+KMC_API int kmc_fastq_parse_device(const char *raw, uint64_t raw_bytes, int final, char *data, uint64_t data_cap,
+                           int64_t *indices, uint64_t indices_cap, uint64_t *num_seqs, uint64_t *data_bytes,
+                           uint64_t *consumed, hipStream_t stream);
+
+/* File -> device record buffer, the whole-file twin of kmc_fasta_load_device on the
+ * same staging code: one parse with final = 1.  *data (*data_bytes + 16 bytes) and
+ * *indices (*num_seqs + 1 entries) are hipMalloc'ed; the caller hipFree's them.
+ * max_seqs > 0 keeps the first max_seqs records, a plain truncation: *num_seqs =
+ * max_seqs, *data_bytes = indices[max_seqs].  KMC_ERR_FORMAT: *num_seqs is the
+ * record's index and no buffer is returned.  The raw bytes and the records are both
+ * resident while it runs; files of 2^33 bytes and more (KMC_ERR_INVALID_ARG) and
+ * pipes go through the reader below.  Synchronous on `stream`. */
+KMC_API int kmc_fastq_load_device(const char *path, int64_t max_seqs, char **data, uint64_t *data_bytes,
+                          int64_t **indices, uint64_t *num_seqs, hipStream_t stream);
+
+/* Batch reader: a FASTQ file of any size as a sequence of record buffers, for
+ * consumers that accumulate (kmc_sketch_screen_count).
+ * kmc_fastq_open opens the file and touches no device (KMC_ERR_IO when it cannot).
+ * batch_bytes == 0 means 256 MiB; any other value is rounded up to a multiple of 16
+ * (2^32 and more: KMC_ERR_INVALID_ARG).  The reader only read()s until end of
+ * file: it never seeks and never asks the size, so `path` may be a pipe
+ * (/dev/stdin, a process substitution fed by zcat).
+ * kmc_fastq_next reads up to batch_bytes new raw bytes behind the unconsumed tail of
+ * the previous batch, copies them to the device through two pinned staging buffers
+ * (the read of one chunk overlapping the copy of the last) and parses them
+ * (kmc_fastq_parse_device, final exactly when end of file was reached).  It returns
+ * device pointers the reader owns: *indices, *num_seqs + 1 offsets, and *data,
+ * *data_bytes + 16 readable bytes.  A batch without a complete record before the
+ * end of the file makes the raw buffer grow (doubling) and the read go on, so a
+ * record longer than batch_bytes is handled; KMC_ERR_NOMEM when that fails.  After
+ * the last batch every call returns KMC_OK with *num_seqs = 0, *data_bytes = 0 and
+ * *data = NULL: the caller detects the end by *data == NULL.  KMC_ERR_FORMAT:
+ * *num_seqs is the record's index within the whole file.  A reader that failed
+ * returns the same code again.
+ * Ordering: all device work of a call (copies, parse) is issued on `stream`, and the
+ * returned buffers stay valid until the next call on the reader, whose writes are
+ * stream-ordered behind whatever the caller enqueued on the same stream.  A caller
+ * that counts each batch on that stream needs no synchronisation of its own, and
+ * the host reads the next chunk while the GPU counts the last.  The call itself is
+ * synchronous on `stream` (it returns sizes).  Device memory held: about 1.5 x
+ * batch_bytes (the raw bytes and half as much for the records) plus the offsets,
+ * unless a record forced growth; up to 128 MiB of pinned staging.
+ * kmc_fastq_close frees everything (NULL: nothing). */
+typedef struct kmc_fastq_reader kmc_fastq_reader;
+KMC_API int kmc_fastq_open(const char *path, uint64_t batch_bytes, kmc_fastq_reader **out);
+KMC_API int kmc_fastq_next(kmc_fastq_reader *rd, const char **data, uint64_t *data_bytes, const int64_t **indices,
+                   uint64_t *num_seqs, hipStream_t stream);
+KMC_API void kmc_fastq_close(kmc_fastq_reader *rd);
 
 #ifdef __cplusplus
 }
