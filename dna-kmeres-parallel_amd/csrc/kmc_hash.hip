@@ -1598,6 +1598,7 @@ unsigned long long h_fb_defer[3] = {0, 0, 0};  // lists queued: big instance, ta
 // call at this value instead of 0 (a counter left un-reset: entries it covers were
 // never written by this call); -1: off
 long long h_stale_queue = -1;
+int64_t h_list_target = kListTarget;  // windows per list canon_plan aims at (kmc_diag_canon_list_target)
 #endif
 
 // K1 / K3a instances by orientation and key width
@@ -1697,6 +1698,18 @@ extern "C" KMC_DIAG_API int kmc_diag_canon_sort_cap_big(unsigned cap) {
     h_sort_cap_big = cap > kSortCapBig ? kSortCapBig : cap;
     return KMC_OK;
 }
+
+// Test hook (diagnostic library only, not in kmc.h): the windows per list that
+// canon_plan aims at, 16 .. kListTarget (0 restores kListTarget), so that records of
+// a few hundred kilobytes have the lists per coarse bucket -- K3b's ring geometry --
+// of records of up to 128 M windows.  Host geometry only: no kernel reads it, and
+// the size query follows it.
+extern "C" KMC_DIAG_API int kmc_diag_canon_list_target(unsigned t) {
+    if (t != 0 && (t < 16 || t > (unsigned)kListTarget)) return KMC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h_mu);
+    h_list_target = t ? (int64_t)t : kListTarget;
+    return KMC_OK;
+}
 #endif
 
 namespace {
@@ -1727,11 +1740,20 @@ void canon_plan(const int64_t *hidx, int64_t n, int k, int cus, CanonPlan &P) {
     P.lbase.assign(n + 1, 0);
     P.fsplit.clear();
     int64_t M = 0, Mc = 0, L = 0, windows = 0;
+#ifdef KMC_DIAG_HOOKS
+    int64_t target;
+    {
+        std::lock_guard<std::mutex> lk(h_mu);
+        target = h_list_target;
+    }
+#else
+    constexpr int64_t target = kListTarget;
+#endif
     for (int64_t r = 0; r < n; ++r) {
         const int64_t a = hidx[r], nw = std::max<int64_t>(0, hidx[r + 1] - a - k);
         windows += nw;
         int g = 0;
-        while (g < kMaxLg && ((int64_t)kListTarget << g) < nw) ++g;
+        while (g < kMaxLg && (target << g) < nw) ++g;
         const int gc = g < kCoarseLg ? g : kCoarseLg;
         P.lg[r] = (uint8_t)g;
         if (nw > 0) {

@@ -105,6 +105,7 @@ class diag:
                                                                  ctypes.POINTER(ctypes.c_ulonglong)]
             _diag_lib.kmc_diag_dense_spill_cap.argtypes = [ctypes.c_uint]
             _diag_lib.kmc_diag_canon_stale_queue.argtypes = [ctypes.c_longlong]
+            _diag_lib.kmc_diag_canon_list_target.argtypes = [ctypes.c_uint]
         self._prev = _active
         _active = _diag_lib
         return _diag_lib
@@ -119,6 +120,7 @@ class diag:
         L.kmc_diag_canon_direct(1)
         L.kmc_diag_dense_spill_cap(0)
         L.kmc_diag_canon_stale_queue(-1)
+        L.kmc_diag_canon_list_target(0)
         _active = self._prev
         return False
 

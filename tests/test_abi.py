@@ -37,7 +37,7 @@ def test_diag_library_adds_only_the_test_hooks(kmc):
     got = _dynamic_symbols(kmc.DIAG_LIB_PATH)
     hooks = [n for n in got if n.startswith("kmc_diag_")]
     assert hooks == ["kmc_diag_canon_claim_cap", "kmc_diag_canon_direct", "kmc_diag_canon_fallback",
-                     "kmc_diag_canon_fallback_detail",
+                     "kmc_diag_canon_fallback_detail", "kmc_diag_canon_list_target",
                      "kmc_diag_canon_sort_cap",
                      "kmc_diag_canon_sort_cap_big", "kmc_diag_canon_stale_queue", "kmc_diag_dense_spill_cap",
                      "kmc_diag_radix_mode"]
