@@ -26,6 +26,8 @@
 // screen_results.tsv).  Inputs may be FASTQ (--format, or a .fq / .fastq name):
 // kmc_fastq_load_device, and a --screen FILE in FASTQ is streamed batch by batch
 // (kmc_fastq_open / _next / _close), so its size is not bounded by device memory.
+// --per-file --min-abundance M: every file is one pass of the abundance accumulator
+// (kmc_sketch_accum_*), a FASTQ file streamed the same way.
 // GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
@@ -76,6 +78,10 @@ struct Options {
     std::vector<std::string> more_inputs;  // the input files after the first
     int format = 0;             // --format: 0 auto (by file name), 1 fasta, 2 fastq
     uint64_t screen_batch = 0;  // --screen-batch BYTES (0: the reader's default, 256 MiB)
+    long min_abundance = 0;     // --min-abundance M: --per-file sketches of the k-mers seen M times (0: not given)
+    long accum_slots = 0;       // --accum-slots LOG2 (0: the library's default)
+    uint64_t batch = 0;         // --batch BYTES: the reader's batches of a --min-abundance FASTQ file
+    bool accum_slots_set = false, batch_set = false;
 };
 
 // auto: FASTQ exactly when the name ends in .fq or .fastq, whatever the case
@@ -95,6 +101,7 @@ void usage(FILE *f) {
             "       kmc --canonical --sketch S --sketch-direct --query q.fasta [--top T] [options] <refs.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --screen reads.fasta [--screen ...] [options] <refs.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --screen reads.fastq [--screen-batch BYTES] [options] <refs.fasta>\n"
+            "       kmc --canonical --sketch S --sketch-direct --per-file --min-abundance M [--batch BYTES] [options] <a.fastq> ...\n"
             "       kmc synth OUT.fa RECORDS LENGTH [SEED]   (benchmark input, SURVEY.md 8(d))\n"
             "  -k K              k-mer length (default %d, the reference's K); dense path 1..%d,\n"
             "                    --canonical 1..%d\n"
@@ -166,13 +173,28 @@ void usage(FILE *f) {
             "                    (kmc_fastq_open / _next / _close, one kmc_sketch_screen_count per batch), so it\n"
             "                    is never resident as a whole and may be a pipe (--format fastq --screen\n"
             "                    /dev/stdin); default 0: 256 MiB.  FASTA FILEs are read whole as before\n"
+            "  --min-abundance M with --canonical --sketch S --sketch-direct --per-file only (the inputs, a --query\n"
+            "                    FILE, the references of --screen): a file's sketch holds only the k-mers seen at\n"
+            "                    least M times in the whole file, M >= 1 (Mash's -m; for read sets, whose k-mers\n"
+            "                    seen once are mostly sequencing errors).  Every file is one pass of one\n"
+            "                    accumulator (kmc_sketch_accum_*): a FASTQ file is streamed batch by batch\n"
+            "                    (kmc_fastq_open / _next, one kmc_sketch_accum_add per batch), so it is never\n"
+            "                    resident as a whole and may be a pipe (--format fastq /dev/stdin); a FASTA file\n"
+            "                    is read whole and added in one call.  One line per file gives its records,\n"
+            "                    batches, sketch size, threshold level j and whether the sketch is complete; a\n"
+            "                    file whose sketch is not complete ends the run: raise --accum-slots\n"
+            "  --accum-slots L   with --min-abundance: the accumulator's table has 2^L slots, L in %d..%d\n"
+            "                    (default 0: the power of two at or above %d S)\n"
+            "  --batch B         with --min-abundance: raw bytes per batch of a streamed FASTQ file\n"
+            "                    (default 0: 256 MiB)\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
             "  -q                quiet (no progress lines)\n",
             KMC_DROPIN_K, KMC_DENSE_MAX_K, KMC_CANON_MAX_K, KMC_MAX_SEQS_REFERENCE, KMC_MAX_SEQS_REFERENCE + 1,
             KMC_DROPIN_K, KMC_CANON_MAX_K, (unsigned long long)KMC_SKETCH_DEFAULT_SEED, KMC_SKETCH_MAX_SIZE,
-            KMC_NEAREST_MAX_TOP);
+            KMC_NEAREST_MAX_TOP, KMC_SKETCH_ACCUM_MIN_LOG2_SLOTS, KMC_SKETCH_ACCUM_MAX_LOG2_SLOTS,
+            KMC_SKETCH_ACCUM_DEFAULT_SLOTS_PER_VALUE);
 }
 
 int parse(int argc, char **argv, Options &o) {
@@ -245,6 +267,29 @@ int parse(int argc, char **argv, Options &o) {
             const long long b = atoll(next("--screen-batch"));
             if (b < 0 || b >= (1ll << 32)) return fprintf(stderr, "kmc: --screen-batch must be in 0..2^32-1\n"), 2;
             o.screen_batch = (uint64_t)b;
+        } else if (a == "--min-abundance") {
+            o.min_abundance = atol(next("--min-abundance"));
+            if (o.min_abundance < 1 || o.min_abundance > (long)UINT32_MAX) {
+                fprintf(stderr, "kmc: --min-abundance must be in 1..%u\n", UINT32_MAX);
+                return usage(stderr), 2;
+            }
+        } else if (a == "--accum-slots") {
+            o.accum_slots = atol(next("--accum-slots"));
+            o.accum_slots_set = true;
+            if (o.accum_slots != 0 && (o.accum_slots < KMC_SKETCH_ACCUM_MIN_LOG2_SLOTS ||
+                                       o.accum_slots > KMC_SKETCH_ACCUM_MAX_LOG2_SLOTS)) {
+                fprintf(stderr, "kmc: --accum-slots must be 0 or in %d..%d\n", KMC_SKETCH_ACCUM_MIN_LOG2_SLOTS,
+                        KMC_SKETCH_ACCUM_MAX_LOG2_SLOTS);
+                return usage(stderr), 2;
+            }
+        } else if (a == "--batch") {
+            const long long b = atoll(next("--batch"));
+            o.batch_set = true;
+            if (b < 0 || b >= (1ll << 32)) {
+                fprintf(stderr, "kmc: --batch must be in 0..2^32-1\n");
+                return usage(stderr), 2;
+            }
+            o.batch = (uint64_t)b;
         } else if (a == "--softmask") {
             o.softmask = true;
         } else if (a == "--host-loader") {
@@ -283,6 +328,18 @@ int parse(int argc, char **argv, Options &o) {
     }
     if (o.per_file && !(o.canonical && o.sketch > 0 && o.sketch_direct)) {
         fprintf(stderr, "kmc: --per-file needs --canonical --sketch S --sketch-direct\n");
+        return usage(stderr), 2;
+    }
+    if (o.min_abundance > 0 && !o.per_file) {
+        fprintf(stderr, "kmc: --min-abundance needs --canonical --sketch S --sketch-direct --per-file\n");
+        return usage(stderr), 2;
+    }
+    if (o.min_abundance > 0 && o.max_seqs_set && o.max_seqs > 0) {
+        fprintf(stderr, "kmc: --min-abundance reads every file whole: not with --max-seqs above 0\n");
+        return usage(stderr), 2;
+    }
+    if ((o.accum_slots_set || o.batch_set) && o.min_abundance == 0) {
+        fprintf(stderr, "kmc: --accum-slots and --batch shape the pass of --min-abundance\n");
         return usage(stderr), 2;
     }
     if (o.per_file && !o.max_seqs_set) o.max_seqs = 0;
@@ -396,12 +453,14 @@ struct StreamDestroy { void operator()(hipStream_t s) const { (void)hipStreamDes
 struct EventDestroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
 struct FastaFree { void operator()(kmc_fasta *f) const { kmc_fasta_free(f); } };
 struct FastqClose { void operator()(kmc_fastq_reader *r) const { kmc_fastq_close(r); } };
+struct AccumFree { void operator()(kmc_sketch_accum *a) const { kmc_sketch_accum_free(a); } };
 template <class T>
 using DevBuf = std::unique_ptr<T, DevFree>;
 using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
 using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
 using Fasta = std::unique_ptr<kmc_fasta, FastaFree>;
 using FastqReader = std::unique_ptr<kmc_fastq_reader, FastqClose>;
+using Accum = std::unique_ptr<kmc_sketch_accum, AccumFree>;
 
 // max(count, 1) elements: an empty input still gets a pointer the entry points take
 template <class T>
@@ -532,10 +591,85 @@ int run_sketch_direct(const Options &o, const Records &r, hipStream_t st) {
     }, r.n, st);
 }
 
+// the table of --min-abundance: --accum-slots, or the library's default for sketch size s
+uint32_t accum_log2_slots(const Options &o, uint32_t s) {
+    uint32_t lg = (uint32_t)o.accum_slots;
+    if (lg == 0)
+        for (lg = KMC_SKETCH_ACCUM_MIN_LOG2_SLOTS; (1ull << lg) < (uint64_t)KMC_SKETCH_ACCUM_DEFAULT_SLOTS_PER_VALUE * s;) ++lg;
+    return lg;
+}
+
+// --per-file --min-abundance M: every file is one pass of the accumulator, reset in between;
+// a FASTQ file batch by batch, every add on st behind its batch's parse (the next batch's
+// writes are ordered behind that add), a FASTA file loaded whole and added in one call
+int accum_files(const Options &o, const std::vector<std::string> &files, const char *what, uint32_t s, uint64_t *d_sk,
+                uint32_t *d_sz, hipStream_t st) {
+    const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
+    const uint32_t lg = accum_log2_slots(o, s);
+    kmc_sketch_accum *acc = nullptr;
+    KMCCHK(kmc_sketch_accum_create(s, o.k, flags, KMC_SKETCH_DEFAULT_SEED, lg, &acc));
+    const Accum accum(acc);
+    DevBuf<uint64_t> d_stats;
+    HIPCHK(dev_alloc(d_stats, 4));
+    for (size_t f = 0; f < files.size(); ++f) {
+        const std::string &path = files[f];
+        uint64_t records = 0, bytes = 0, batches = 0;
+        KMCCHK(kmc_sketch_accum_reset(acc, st));
+        FastqReader reader;  // (its buffers, or the loaded file's, live until the file's synchronisation)
+        Records r;
+        if (is_fastq(o, path)) {
+            kmc_fastq_reader *rd = nullptr;
+            const int orc = kmc_fastq_open(path.c_str(), o.batch, &rd);
+            if (orc) return fprintf(stderr, "kmc: %s: %s\n", path.c_str(), kmc_error_string(orc)), 1;
+            reader.reset(rd);
+            for (;;) {
+                const char *d_data = nullptr;
+                const int64_t *d_idx = nullptr;
+                uint64_t nb = 0, ns = 0;
+                const int rc = kmc_fastq_next(rd, &d_data, &nb, &d_idx, &ns, st);
+                if (rc == KMC_ERR_FORMAT) return malformed(path, ns);
+                KMCCHK(rc);
+                if (!d_data) break;
+                KMCCHK(kmc_sketch_accum_add(acc, d_data, d_idx, ns, nb, st));
+                records += ns;
+                bytes += nb;
+                ++batches;
+            }
+        } else {
+            Options of = o;
+            of.input = path;
+            of.quiet = true;
+            if (int e = load(of, st, r)) return e;
+            KMCCHK(kmc_sketch_accum_add(acc, r.data.get(), r.idx.get(), r.n, r.bytes, st));
+            records = r.n;
+            bytes = r.bytes;
+            batches = 1;
+        }
+        KMCCHK(kmc_sketch_accum_finish(acc, (uint32_t)o.min_abundance, d_sk + f * s, d_sz + f, d_stats.get(), st));
+        uint32_t size = 0;
+        uint64_t stats[4] = {0, 0, 0, 0};
+        HIPCHK(hipMemcpyAsync(&size, d_sz + f, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(stats, d_stats.get(), sizeof stats, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));  // before the file's buffers go
+        uint32_t j = 0;  // the library's rule (kmc.h) for the bytes added
+        while (((bytes + ((1ull << j) - 1)) >> j) > (1ull << (lg - 2))) ++j;
+        if (!o.quiet)
+            printf("%s %zu: %s: %" PRIu64 " records, %" PRIu64 " batches, sketch size %u, j %u, complete %d\n", what, f,
+                   path.c_str(), records, batches, size, j, (int)stats[0]);
+        if (!stats[0])
+            return fprintf(stderr,
+                           "kmc: %s: the table of 2^%u slots kept only %u of %u sketch values with abundance >= %ld "
+                           "(%" PRIu64 " k-mers tracked below hash %" PRIu64 "): raise --accum-slots\n",
+                           path.c_str(), lg, size, s, o.min_abundance, stats[2], stats[1]), 1;
+    }
+    return 0;
+}
+
 // --per-file: every file is one group of all its records; file f's call writes row f
 // (rows of separate calls concatenate), so one file at a time is resident
 int sketch_files(const Options &o, const std::vector<std::string> &files, const char *what, uint32_t s, uint64_t *d_sk,
                  uint32_t *d_sz, hipStream_t st) {
+    if (o.min_abundance > 0) return accum_files(o, files, what, s, d_sk, d_sz, st);
     const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
     DevBuf<int64_t> d_grp;
     HIPCHK(dev_alloc(d_grp, 2));

@@ -1,0 +1,499 @@
+// kmc_sketch_accum.hip — the accumulating abundance sketcher: the bottom-s MinHash
+// sketch of the k-mers seen at least min_count times over any number of batches (a
+// read set of any size, Mash's -m).  It counts only the k-mers whose hash lies below a
+// threshold, in a device hash table the handle owns; finish hands the counted keys to
+// the select of kmc_sketch_from_counts.  Every device call is asynchronous with no
+// host read-back; the launches depend on the host arguments and the handle's host
+// state only.
+//
+// The handle's device memory (one allocation, each array rounded up to 256 bytes):
+//   header  256 B        lost      the smallest hash of a refused insert (UINT64_MAX: none)
+//                        tracked   entries of table 0 and of table 1
+//                        rec_off   {0, the length of finish's list}: the offsets of the
+//                                  one record kmc_sketch_from_counts selects from
+//                        qual      list entries with count >= min_count
+//   keys    uint64[C] x 2   open addressing, linear probing, the slot of a key is the
+//   counts  uint32[C] x 2   low log2_slots bits of its HASH; UINT64_MAX: empty (a
+//                           canonical key has at most 62 bits)
+//   select  the workspace of kmc_sketch_from_counts for one record
+// One table is active (host state); the other is the purge's target and, between
+// purges, the place of finish's list.
+//
+// The threshold is the host's: N = the bytes added so far, j the smallest integer with
+// ceil(N / 2^j) <= C / 4, and a window takes part iff its hash is below 2^(64 - j) (one
+// compare against a kernel argument; j = 0: every window).  N bounds the windows, so
+// with a fixed hash the expected number of tracked keys stays at or below C / 4.
+//
+//   add     the screen's walk (kmc_canon_walk.h: for_each_piece, chunk_raw, chunk_keys
+//           with the identity functor, so a window keeps its key; kmc_sketch_walk.h:
+//           the launch shape and walk_of).  A window whose hash passes the threshold
+//           probes from its slot: its key found, the count takes a vector atomic add
+//           (no return value), once per run of equal keys among a thread's 16
+//           windows; an empty slot found, the thread reserves an entry (the one
+//           returning atomic, on `tracked`, that only a new key pays) and inserts the
+//           key with a 64-bit compare-and-swap; a slot that went to another thread
+//           gives the reservation back.  A new key is refused when C / 2 entries are
+//           reserved or the chain is kChain slots long: the refusal is one 64-bit
+//           atomic minimum of its hash into `lost`, no retry, no spin.  So a table
+//           never holds more than C / 2 keys, and more distinct keys than that below
+//           the bound always leave a mark in `lost`; two threads that bring the same
+//           new key when one entry is left may cost the second its window, which
+//           `lost` then records like any other refusal.
+//   purge   when an add raises j: the other table is cleared (memsets), every entry of
+//           the active one whose hash is still below the bound is inserted there with
+//           its count under the same chain bound (a failure goes to `lost` like any
+//           other), and the tables swap roles.
+//   compact finish: limit = min(2^(64 - j), lost); every entry with hash < limit (all
+//           of them when j = 0 and nothing was lost) is appended to one (key, count)
+//           list in the inactive table's arrays through a cursor; every key below
+//           `limit` was tracked from its first window on, so its count is exact.
+//   select  kmc_sketch_from_counts over that list as one record: num_entries is C (a
+//           host number), the list's length is rec_off[1] on the device, and entries
+//           no record claims are skipped by the walk (kmc_walk.h).  So the row is
+//           bit for bit the count -> sketch path's, and the radix select, its sort
+//           and the row format stay in kmc_sketch.hip.
+//   stats   one thread writes the four words.
+// finish writes the header's rec_off and qual, the inactive table and the select
+// workspace only: the accumulator is as it was.
+//
+// The device code trusts the host arguments only: every slot index is masked, every
+// chain is bounded by kChain <= C, the list's cursor is checked against C.
+//
+// Constants (the same in libkmc_diag.so, whose walk has 64-thread workgroups and
+// 256-byte ranges through kmc_sketch_walk.h; the tests force the table's paths with
+// log2_slots = 4 .. 8):
+//   kChain         probes of one key at most           256 (C when smaller)
+//   kDefaultPer    slots per sketch value, at least    4096 (log2_slots = 0)
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <new>
+
+#include "kmc.h"
+#include "kmc_canon_walk.h"
+#include "kmc_internal.h"
+#include "kmc_sketch_pair.h"
+#include "kmc_sketch_walk.h"
+#include "kmc_workspace.h"
+
+namespace kmc {
+namespace {
+
+constexpr uint32_t kChain = 256;
+constexpr uint64_t kDefaultPer = KMC_SKETCH_ACCUM_DEFAULT_SLOTS_PER_VALUE;
+constexpr size_t kHeaderBytes = 256;
+constexpr int kSlotBlock = 256;  // threads of the kernels that walk the slots
+
+struct Header {
+    unsigned long long lost;
+    uint32_t tracked[2];
+    unsigned long long rec_off[2];
+    unsigned long long qual;
+};
+static_assert(sizeof(Header) <= kHeaderBytes, "the header has its 256 bytes");
+
+struct ALayout {
+    Header *hd;
+    unsigned long long *keys[2];
+    uint32_t *counts[2];
+    void *select;
+    size_t select_bytes, bytes;
+};
+
+inline bool log2_slots_ok(uint32_t lg) {
+    return lg == 0 || (lg >= KMC_SKETCH_ACCUM_MIN_LOG2_SLOTS && lg <= KMC_SKETCH_ACCUM_MAX_LOG2_SLOTS);
+}
+
+// log2_slots = 0: the power of two at or above kDefaultPer * sketch_size
+inline uint32_t resolve_log2(uint32_t sketch_size, uint32_t lg) {
+    if (lg) return lg;
+    lg = KMC_SKETCH_ACCUM_MIN_LOG2_SLOTS;
+    while ((1ull << lg) < kDefaultPer * sketch_size) ++lg;
+    return lg;  // <= 26 for KMC_SKETCH_MAX_SIZE
+}
+
+// the one layout behind the size query (base = null) and create
+inline ALayout layout(void *base, uint32_t sketch_size, uint32_t lg) {
+    const uint64_t C = 1ull << lg;
+    Carver c(base);
+    ALayout L;
+    L.hd = reinterpret_cast<Header *>(c.take<char>(kHeaderBytes));
+    for (int t = 0; t < 2; ++t) {
+        L.keys[t] = c.take<unsigned long long>((size_t)C);
+        L.counts[t] = c.take<uint32_t>((size_t)C);
+    }
+    L.select_bytes = kmc_sketch_workspace_size(1, C, sketch_size, 0);  // (host numbers only)
+    L.select = c.take<char>(L.select_bytes);
+    L.bytes = c.total();
+    return L;
+}
+
+// The smallest j >= 0 with ceil(N / 2^j) <= C / 4.
+inline uint32_t level_of(uint64_t N, uint32_t lg) {
+    const uint64_t quarter = 1ull << (lg - 2);
+    uint32_t j = 0;
+    while (((N + ((1ull << j) - 1)) >> j) > quarter) ++j;
+    return j;  // N < 2^62, quarter >= 4: j <= 60
+}
+
+// the largest hash that takes part at level j: 2^(64 - j) - 1
+inline uint64_t max_hash(uint32_t j) { return j == 0 ? ~0ull : (1ull << (64 - j)) - 1ull; }
+
+// One table as a kernel sees it, all from the host.
+struct Table {
+    unsigned long long *keys;
+    uint32_t *counts;
+    uint32_t *tracked;
+    unsigned long long *lost;
+    uint32_t mask, chain, half;
+};
+
+// Where the count of `key` (hash h) is kept, inserting the key when it is new; null:
+// refused, and h has gone to `lost`.  CAP: new keys are refused at T.half tracked.
+template <bool CAP>
+__device__ __forceinline__ uint32_t *find_or_insert(const Table &T, unsigned long long key, unsigned long long h) {
+    uint32_t i = (uint32_t)h & T.mask;
+    for (uint32_t step = 0; step < T.chain; ++step) {
+        // (a stale empty reading only costs the compare-and-swap; a key never changes)
+        const unsigned long long x = __hip_atomic_load(T.keys + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (x == key) return T.counts + i;
+        if (x == kFill) {
+            // the entry is reserved before the slot is taken (the purge only counts)
+            const uint32_t had = __hip_atomic_fetch_add(T.tracked, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (CAP && had >= T.half) {
+                __hip_atomic_fetch_sub(T.tracked, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                break;
+            }
+            const unsigned long long was = atomicCAS(T.keys + i, (unsigned long long)kFill, key);
+            if (was == kFill) return T.counts + i;
+            __hip_atomic_fetch_sub(T.tracked, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // another thread's slot
+            if (was == key) return T.counts + i;
+        }
+        i = (i + 1) & T.mask;
+    }
+    __hip_atomic_fetch_min(T.lost, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return nullptr;
+}
+
+// ---------------------------------------------------------------------------
+// add
+// ---------------------------------------------------------------------------
+using Walk = WalkOf<Offsets>;
+
+struct KeyOf {  // a window keeps its key: the slot needs the hash, the table the key
+    __device__ __forceinline__ unsigned long long operator()(uint64_t key) const { return key; }
+};
+
+struct AArgs {
+    const char *data;  // rounded down to 16 bytes
+    Offsets idx;
+    int64_t n;
+    int k;
+    uint32_t flags;
+    int G;
+    uint64_t seed;
+    uint64_t maxh;  // hashes above it leave
+    Table T;
+};
+
+template <bool FWD, bool BIGK>
+__device__ __forceinline__ void add_piece(const AArgs &a, const Walk &W, int64_t ps, int64_t pe, int64_t rend) {
+    const int tid = threadIdx.x;
+    const int64_t c0 = ps >> 4, c1 = ((pe - 1) >> 4) + 1;
+    ChunkRaw nx = chunk_raw(W, (c0 + tid) << 4);
+    for (int64_t cb = c0; cb < c1; cb += kBlock) {
+        const int64_t c = cb + tid;
+        unsigned long long key[16];
+        const ChunkRaw cr = nx;
+        nx = chunk_raw(W, (c + kBlock) << 4);  // next round's chunk
+        uint32_t pend = chunk_keys<FWD, BIGK>(W, cr, c << 4, ps, pe, rend, KeyOf{}, key);  // (past the piece: 0)
+        uint32_t cm = 0u;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) cm |= (uint32_t)(sketch_hash(key[j], a.seed) <= a.maxh) << j;
+        pend &= cm;
+        if (pend == 0u) continue;
+        unsigned long long last = 0;
+        uint32_t *at = nullptr;
+        uint32_t run = 0u;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            if (!((pend >> j) & 1u)) continue;
+            if (run && key[j] == last) {
+                ++run;
+                continue;
+            }
+            if (run && at) __hip_atomic_fetch_add(at, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            last = key[j];
+            at = find_or_insert<true>(a.T, last, sketch_hash(last, a.seed));
+            run = 1u;
+        }
+        if (run && at) __hip_atomic_fetch_add(at, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+template <bool FWD, bool BIGK>
+__global__ __launch_bounds__(kBlock) void accum_add_kernel(AArgs a) {
+    __shared__ int64_t s_first;
+    const Walk W = walk_of(a.data, a.idx, a.n, a.k, a.flags, a.G);
+    for_each_piece(W, &s_first, [&](int64_t, int64_t ps, int64_t pe, int64_t rend) {
+        add_piece<FWD, BIGK>(a, W, ps, pe, rend);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// purge, compact, stats
+// ---------------------------------------------------------------------------
+struct PArgs {
+    const unsigned long long *keys;  // the table that is left, C slots
+    const uint32_t *counts;
+    uint64_t C, seed, maxh;
+    Table T;  // the cleared table
+};
+
+__global__ __launch_bounds__(kSlotBlock) void accum_purge_kernel(PArgs a) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kSlotBlock + threadIdx.x; i < a.C; i += (uint64_t)gridDim.x * kSlotBlock) {
+        const unsigned long long key = a.keys[i];
+        if (key == kFill) continue;
+        const unsigned long long h = sketch_hash(key, a.seed);
+        if (h > a.maxh) continue;
+        uint32_t *at = find_or_insert<false>(a.T, key, h);
+        if (at) __hip_atomic_fetch_add(at, a.counts[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+struct FArgs {
+    const unsigned long long *keys;  // the active table, C slots
+    const uint32_t *counts;
+    uint64_t C, seed, maxh;
+    uint32_t j, min_count, s;
+    Header *hd;
+    unsigned long long *list_keys;  // [C]
+    uint32_t *list_counts;
+    const uint32_t *size_out;
+    uint64_t *stats;
+};
+
+// the exclusive bound of the hashes whose counts are exact; *all: nothing bounds them
+__device__ __forceinline__ unsigned long long limit_of(const FArgs &a, bool *all) {
+    const unsigned long long lost = a.hd->lost;
+    *all = a.j == 0 && lost == kFill;
+    if (a.j == 0) return lost;
+    const unsigned long long bound = a.maxh + 1ull;
+    return lost < bound ? lost : bound;
+}
+
+__global__ __launch_bounds__(kSlotBlock) void accum_compact_kernel(FArgs a) {
+    bool all;
+    const unsigned long long limit = limit_of(a, &all);
+    const uint32_t m = a.min_count > 1 ? a.min_count : 1u;
+    for (uint64_t i = (uint64_t)blockIdx.x * kSlotBlock + threadIdx.x; i < a.C; i += (uint64_t)gridDim.x * kSlotBlock) {
+        const unsigned long long key = a.keys[i];
+        if (key == kFill) continue;
+        if (!all && sketch_hash(key, a.seed) >= limit) continue;
+        const uint32_t cnt = a.counts[i];
+        const unsigned long long at = atomicAdd(&a.hd->rec_off[1], 1ull);
+        if (at < a.C) {  // (guard: at most C slots hold a key)
+            a.list_keys[at] = key;
+            a.list_counts[at] = cnt;
+        }
+        if (cnt >= m) atomicAdd(&a.hd->qual, 1ull);
+    }
+}
+
+__global__ void accum_stats_kernel(FArgs a) {
+    bool all;
+    const unsigned long long limit = limit_of(a, &all);
+    a.stats[0] = (all || *a.size_out == a.s) ? 1u : 0u;
+    a.stats[1] = limit;
+    a.stats[2] = a.hd->rec_off[1];
+    a.stats[3] = a.hd->qual;
+}
+
+inline unsigned slot_grid(uint64_t C) {
+    const uint64_t b = (C + kSlotBlock - 1) / kSlotBlock;
+    return (unsigned)(b < 4096 ? b : 4096);
+}
+
+}  // namespace
+}  // namespace kmc
+
+using namespace kmc;
+
+struct kmc_sketch_accum {
+    uint32_t s, lg;
+    int k;
+    unsigned flags;
+    uint64_t seed;
+    void *base;
+    ALayout L;
+    // what the adds so far have made of the table
+    uint64_t N;  // bytes added
+    uint32_t j;  // the threshold's level: it never falls
+    int active;  // the table the adds go to
+};
+
+namespace {
+
+Table table_of(const kmc_sketch_accum *a, int t) {
+    const uint64_t C = 1ull << a->lg;
+    Table T;
+    T.keys = a->L.keys[t];
+    T.counts = a->L.counts[t];
+    T.tracked = &a->L.hd->tracked[t];
+    T.lost = &a->L.hd->lost;
+    T.mask = (uint32_t)(C - 1);
+    T.chain = C < kChain ? (uint32_t)C : kChain;
+    T.half = (uint32_t)(C / 2);
+    return T;
+}
+
+// table t empty, with no tracked entry
+int clear_table(const kmc_sketch_accum *a, int t, hipStream_t st) {
+    const size_t C = (size_t)1 << a->lg;
+    if (hipError_t he = hipMemsetAsync(a->L.keys[t], 0xFF, C * 8, st)) return (int)he;
+    if (hipError_t he = hipMemsetAsync(a->L.counts[t], 0, C * 4, st)) return (int)he;
+    return (int)hipMemsetAsync(&a->L.hd->tracked[t], 0, 4, st);
+}
+
+// the state after create: table 0 empty and active, nothing lost, N = 0, j = 0
+int start_over(kmc_sketch_accum *a, hipStream_t st) {
+    if (hipError_t he = hipMemsetAsync(a->L.hd, 0, kHeaderBytes, st)) return (int)he;
+    if (hipError_t he = hipMemsetAsync(&a->L.hd->lost, 0xFF, 8, st)) return (int)he;
+    if (int e = clear_table(a, 0, st)) return e;
+    a->N = 0;
+    a->j = 0;
+    a->active = 0;
+    return KMC_OK;
+}
+
+}  // namespace
+
+extern "C" size_t kmc_sketch_accum_device_bytes(uint32_t sketch_size, uint32_t log2_slots) {
+    if (!sketch_size_ok(sketch_size) || !log2_slots_ok(log2_slots)) return 0;
+    return layout(nullptr, sketch_size, resolve_log2(sketch_size, log2_slots)).bytes;
+}
+
+extern "C" int kmc_sketch_accum_create(uint32_t sketch_size, int k, unsigned flags, uint64_t seed, uint32_t log2_slots,
+                                       kmc_sketch_accum **out) {
+    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
+    if (!sketch_size_ok(sketch_size) || !log2_slots_ok(log2_slots) || !out) return KMC_ERR_INVALID_ARG;
+    if (flags & ~(KMC_CANON_SOFTMASK | KMC_CANON_FORWARD)) return KMC_ERR_INVALID_ARG;
+    *out = nullptr;
+    kmc_sketch_accum *a = new (std::nothrow) kmc_sketch_accum();
+    if (!a) return KMC_ERR_NOMEM;
+    a->s = sketch_size;
+    a->lg = resolve_log2(sketch_size, log2_slots);
+    a->k = k;
+    a->flags = flags;
+    a->seed = seed;
+    a->base = nullptr;
+    if (hipMalloc(&a->base, layout(nullptr, a->s, a->lg).bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        delete a;
+        return KMC_ERR_NOMEM;
+    }
+    a->L = layout(a->base, a->s, a->lg);
+    int e = start_over(a, nullptr);
+    if (!e) e = (int)hipStreamSynchronize(nullptr);  // the clearing is done before any stream's first add
+    if (e) {
+        kmc_sketch_accum_free(a);
+        return e;
+    }
+    *out = a;
+    return KMC_OK;
+}
+
+extern "C" int kmc_sketch_accum_add(kmc_sketch_accum *a, const char *data, const int64_t *indices, uint64_t num_seqs,
+                                    uint64_t data_bytes, hipStream_t stream) {
+    if (!a || num_seqs > kMaxSeqs) return KMC_ERR_INVALID_ARG;
+    if (num_seqs == 0) return KMC_OK;
+    if (!indices || (data_bytes > 0 && !data)) return KMC_ERR_INVALID_ARG;
+    if (data_bytes >= (1ull << 62) || a->N + data_bytes >= (1ull << 62)) return KMC_ERR_INVALID_ARG;
+    int device = 0, cus = 0;
+    if (int e = current_device_cus(&device, &cus)) return e;
+    const uint64_t C = 1ull << a->lg, N = a->N + data_bytes;
+    const uint32_t j = level_of(N, a->lg);
+    if (j > a->j) {  // purge: what stays below the new bound moves to the other table
+        const int from = a->active, to = from ^ 1;
+        if (int e = clear_table(a, to, stream)) return e;
+        PArgs p;
+        p.keys = a->L.keys[from];
+        p.counts = a->L.counts[from];
+        p.C = C;
+        p.seed = a->seed;
+        p.maxh = max_hash(j);
+        p.T = table_of(a, to);
+        hipLaunchKernelGGL(accum_purge_kernel, dim3(slot_grid(C)), dim3(kSlotBlock), 0, stream, p);
+        if (hipError_t he = hipGetLastError()) return (int)he;
+        a->j = j;
+        a->active = to;
+    }
+    // any `data` pointer: rounded down to 16 bytes, every offset moved up by the difference
+    const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
+    AArgs g;
+    g.data = data - mis;
+    g.idx = Offsets{indices, (int64_t)data_bytes, (int64_t)mis};
+    g.n = (int64_t)num_seqs;
+    g.k = a->k;
+    g.flags = a->flags;
+    g.G = walk_groups(data_bytes, cus);
+    g.seed = a->seed;
+    g.maxh = max_hash(a->j);
+    g.T = table_of(a, a->active);
+    const bool fwd = a->flags & KMC_CANON_FORWARD, big = a->k >= 16;
+    const dim3 grid((unsigned)g.G), block(kBlock);
+    if (fwd) {
+        if (big) hipLaunchKernelGGL((accum_add_kernel<true, true>), grid, block, 0, stream, g);
+        else hipLaunchKernelGGL((accum_add_kernel<true, false>), grid, block, 0, stream, g);
+    } else {
+        if (big) hipLaunchKernelGGL((accum_add_kernel<false, true>), grid, block, 0, stream, g);
+        else hipLaunchKernelGGL((accum_add_kernel<false, false>), grid, block, 0, stream, g);
+    }
+    if (hipError_t he = hipGetLastError()) return (int)he;
+    a->N = N;
+    return KMC_OK;
+}
+
+extern "C" int kmc_sketch_accum_finish(kmc_sketch_accum *a, uint32_t min_count, uint64_t *sketch_row,
+                                       uint32_t *sketch_size_out, uint64_t *stats, hipStream_t stream) {
+    if (!a || !sketch_row || !sketch_size_out) return KMC_ERR_INVALID_ARG;
+    const uint64_t C = 1ull << a->lg;
+    const int list = a->active ^ 1;  // cleared by the next purge before it is a table again
+    FArgs f;
+    f.keys = a->L.keys[a->active];
+    f.counts = a->L.counts[a->active];
+    f.C = C;
+    f.seed = a->seed;
+    f.maxh = max_hash(a->j);
+    f.j = a->j;
+    f.min_count = min_count;
+    f.s = a->s;
+    f.hd = a->L.hd;
+    f.list_keys = a->L.keys[list];
+    f.list_counts = a->L.counts[list];
+    f.size_out = sketch_size_out;
+    f.stats = stats;
+    if (hipError_t he = hipMemsetAsync(a->L.hd->rec_off, 0, sizeof(a->L.hd->rec_off) + sizeof(a->L.hd->qual), stream))
+        return (int)he;
+    hipLaunchKernelGGL(accum_compact_kernel, dim3(slot_grid(C)), dim3(kSlotBlock), 0, stream, f);
+    if (hipError_t he = hipGetLastError()) return (int)he;
+    // the list as the one record of the count -> sketch path: C entries to walk, of
+    // which the device's rec_off claims the first rec_off[1]
+    if (int e = kmc_sketch_from_counts(reinterpret_cast<const uint64_t *>(f.list_keys), f.list_counts,
+                                       reinterpret_cast<const uint64_t *>(a->L.hd->rec_off), C, 1, a->s, a->seed,
+                                       min_count, sketch_row, sketch_size_out, a->L.select, a->L.select_bytes, stream))
+        return e;
+    if (stats) hipLaunchKernelGGL(accum_stats_kernel, dim3(1), dim3(1), 0, stream, f);
+    return (int)hipGetLastError();
+}
+
+extern "C" int kmc_sketch_accum_reset(kmc_sketch_accum *a, hipStream_t stream) {
+    if (!a) return KMC_ERR_INVALID_ARG;
+    return start_over(a, stream);
+}
+
+extern "C" void kmc_sketch_accum_free(kmc_sketch_accum *a) {
+    if (!a) return;
+    if (a->base) (void)hipFree(a->base);
+    delete a;
+}

@@ -187,16 +187,7 @@ __global__ __launch_bounds__(kBuildBlock) void screen_build_kernel(BArgs a) {
 // ---------------------------------------------------------------------------
 // count
 // ---------------------------------------------------------------------------
-// record offsets as kmc_sketch_from_sequences' prep writes them, computed as they are
-// read: clamp(indices[r], 0, data_bytes) + (data & 15)
-struct Offsets {
-    const int64_t *p;
-    int64_t bytes, mis;
-    __device__ __forceinline__ int64_t operator[](int64_t r) const {
-        const int64_t x = p[r];
-        return (x < 0 ? 0 : (x > bytes ? bytes : x)) + mis;
-    }
-};
+// (Offsets, the record offsets computed as they are read, and walk_of: kmc_sketch_walk.h)
 using Walk = WalkOf<Offsets>;
 
 struct CArgs {
@@ -210,23 +201,6 @@ struct CArgs {
     void *index;
     uint64_t index_bytes;
 };
-
-__device__ __forceinline__ Walk make_walk(const CArgs &a) {
-    Walk W;
-    W.data = a.data;
-    W.idx = a.idx;
-    W.n = a.n;
-    W.lo = a.idx[0];
-    W.hi = a.idx[a.n];
-    if (W.hi < W.lo) W.hi = W.lo;
-    W.k = a.k;
-    W.flags = a.flags;
-    W.c_lo = W.lo >> 4;
-    const int64_t chunks = W.hi > W.lo ? ((W.hi + 15) >> 4) - W.c_lo : 0;
-    const int64_t cpw = (chunks + a.G - 1) / a.G;
-    W.cpw = cpw > 1 ? cpw : 1;
-    return W;
-}
 
 // The windows of record piece [ps, pe): every hash at or below maxv (or UINT64_MAX,
 // when that is indexed) is looked up and counted.
@@ -277,7 +251,7 @@ __global__ __launch_bounds__(kBlock) void screen_count_kernel(CArgs a) {
     if (!T.ok) return;
     const uint64_t maxv = T.hd->maxv;
     const bool has_ff = T.hd->has_ff != 0u;
-    const Walk W = make_walk(a);
+    const Walk W = walk_of(a.data, a.idx, a.n, a.k, a.flags, a.G);
     const HashOf hf{a.seed};
     for_each_piece(W, &s_first, [&](int64_t, int64_t ps, int64_t pe, int64_t rend) {
         count_piece<FWD, BIGK>(T, maxv, has_ff, W, hf, ps, pe, rend);

@@ -1,8 +1,9 @@
 // kmc_sketch_walk.h — the geometry of the sketch path's walks over the record buffer,
-// shared by the direct sketcher (kmc_sketch_seq.hip) and the screen
-// (kmc_sketch_screen.hip): the workgroup shape, the number of ranges of a call, the
-// walk's view for kmc_canon_walk.h and the hash a window stores.  One definition
-// each, so that both walk the same bytes with the same launch.
+// shared by the direct sketcher (kmc_sketch_seq.hip), the screen
+// (kmc_sketch_screen.hip) and the abundance accumulator (kmc_sketch_accum.hip): the
+// workgroup shape, the number of ranges of a call, the walk's view for
+// kmc_canon_walk.h, the offsets read as they are clamped and the hash a window
+// stores.  One definition each, so that all walk the same bytes with the same launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,6 +41,37 @@ struct WalkOf {
     uint32_t flags;
     int64_t c_lo, cpw;
 };
+
+// record offsets as kmc_sketch_from_sequences' prep writes them, computed as they are
+// read: clamp(indices[r], 0, data_bytes) + (data & 15); the walks that keep no
+// per-record state (the screen, the abundance accumulator) need no workspace for them
+struct Offsets {
+    const int64_t *p;
+    int64_t bytes, mis;
+    __device__ __forceinline__ int64_t operator[](int64_t r) const {
+        const int64_t x = p[r];
+        return (x < 0 ? 0 : (x > bytes ? bytes : x)) + mis;
+    }
+};
+
+// the view of a call over all n records of `idx`, cut into G ranges
+template <class Idx>
+__device__ __forceinline__ WalkOf<Idx> walk_of(const char *data, const Idx &idx, int64_t n, int k, uint32_t flags, int G) {
+    WalkOf<Idx> W;
+    W.data = data;
+    W.idx = idx;
+    W.n = n;
+    W.lo = idx[0];
+    W.hi = idx[n];
+    if (W.hi < W.lo) W.hi = W.lo;
+    W.k = k;
+    W.flags = flags;
+    W.c_lo = W.lo >> 4;
+    const int64_t chunks = W.hi > W.lo ? ((W.hi + 15) >> 4) - W.c_lo : 0;
+    const int64_t cpw = (chunks + G - 1) / G;
+    W.cpw = cpw > 1 ? cpw : 1;
+    return W;
+}
 
 struct HashOf {
     uint64_t seed;

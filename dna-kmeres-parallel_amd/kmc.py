@@ -229,6 +229,15 @@ def _load(path):
     L.kmc_sketch_screen_count.argtypes = [_P, ctypes.c_size_t, _P, _P, _U64, _U64, ctypes.c_int, ctypes.c_uint, _U64, _P]
     L.kmc_sketch_screen_results.argtypes = [_P, ctypes.c_size_t, _P, _P, _U64, ctypes.c_uint32, ctypes.c_int, _P, _P,
                                             _P, _P]
+    L.kmc_sketch_accum_device_bytes.restype = ctypes.c_size_t
+    L.kmc_sketch_accum_device_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+    L.kmc_sketch_accum_create.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint, _U64, ctypes.c_uint32,
+                                          ctypes.POINTER(_P)]
+    L.kmc_sketch_accum_add.argtypes = [_P, _P, _P, _U64, _U64, _P]
+    L.kmc_sketch_accum_finish.argtypes = [_P, ctypes.c_uint32, _P, _P, _P, _P]
+    L.kmc_sketch_accum_reset.argtypes = [_P, _P]
+    L.kmc_sketch_accum_free.argtypes = [_P]
+    L.kmc_sketch_accum_free.restype = None
     L.minKmeres2_hip.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.kmc_count_canonical_hash.argtypes = [_P, _P, _U64, ctypes.c_int, ctypes.c_uint, _P, _P, _U64, _P,
                                            ctypes.POINTER(_U64), _P]
@@ -684,6 +693,86 @@ def sketch_screen_results(index, r, rs, k, median=True, identity=True, out=None,
                                          _dptr(ident), _stream(stream))
     _check(rc, "kmc_sketch_screen_results")
     return sh, med, ident
+
+
+SKETCH_ACCUM_MIN_LOG2_SLOTS = 4
+SKETCH_ACCUM_MAX_LOG2_SLOTS = 30
+
+
+def sketch_accum_device_bytes(sketch_size, log2_slots=0):
+    """Device bytes a SketchAccum of these two numbers holds (0 on bad arguments)."""
+    return int(lib().kmc_sketch_accum_device_bytes(int(sketch_size), int(log2_slots)))
+
+
+class SketchAccum:
+    """kmc_sketch_accum_*: the bottom-s sketch of the k-mers seen at least min_count
+    times over any number of batches (a read set of any size).  add() takes a batch
+    of records (data, indices: as sketch_from_sequences); finish(min_count) returns
+    (row int64 [s]: uint64 hashes ascending, then all-ones fill; size int32 [1];
+    stats int64 [4]: complete, limit, tracked, qualifying, or None) and leaves the
+    accumulator as it is; reset() empties it.  `log2_slots`: the table's size, 0 for
+    the default (kmc.h).  The handle belongs to the library it was created in.
+
+        with kmc.SketchAccum(1000, 21) as acc:
+            with kmc.FastqReader(path, 1 << 28, copy=False) as rd:
+                for data, indices in rd:
+                    acc.add(data, indices)
+            row, size, stats = acc.finish(min_count=2)"""
+
+    def __init__(self, sketch_size, k, flags=0, seed=SKETCH_DEFAULT_SEED, log2_slots=0):
+        self._h = _P()
+        self._lib = lib()
+        self.sketch_size = int(sketch_size)
+        _check(self._lib.kmc_sketch_accum_create(self.sketch_size, int(k), int(flags), int(seed) & _M64,
+                                                 int(log2_slots), ctypes.byref(self._h)), "kmc_sketch_accum_create")
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the accumulator is closed")
+        return self._h
+
+    def add(self, data, indices, data_bytes=None, stream=None):
+        h = self._handle()
+        n = int(indices.numel() - 1)
+        if data_bytes is None:
+            data_bytes = data.numel()
+        _check(self._lib.kmc_sketch_accum_add(h, _dptr(data), _dptr(indices), n, int(data_bytes),
+                                              _stream(stream)), "kmc_sketch_accum_add")
+
+    def finish(self, min_count=1, stats=True, out=None, stream=None):
+        """`stats`: True for a new tensor, or the caller's own int64 tensor [4]; `out`:
+        the caller's own (row, size)."""
+        import torch
+        h = self._handle()
+        with _on(stream):
+            dv = torch.device("cuda", torch.cuda.current_device())
+            row, size = out if out is not None else (torch.empty(self.sketch_size, dtype=torch.int64, device=dv),
+                                                     torch.empty(1, dtype=torch.int32, device=dv))
+            if isinstance(stats, torch.Tensor):
+                st = stats
+            else:
+                st = torch.empty(4, dtype=torch.int64, device=dv) if stats else None
+        _check(self._lib.kmc_sketch_accum_finish(h, int(min_count), _dptr(row), _dptr(size), _dptr(st),
+                                                 _stream(stream)), "kmc_sketch_accum_finish")
+        return row, size, st
+
+    def reset(self, stream=None):
+        _check(self._lib.kmc_sketch_accum_reset(self._handle(), _stream(stream)), "kmc_sketch_accum_reset")
+
+    def close(self):
+        if self._h:
+            self._lib.kmc_sketch_accum_free(self._h)
+            self._h = _P()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        self.close()
 
 
 def min_kmeres2(sums, mins, num_seqs, current_seq, indexes, stream=None):

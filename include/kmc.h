@@ -389,7 +389,7 @@ KMC_API int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *coun
  * smallest distinct hashes of the record it is in as a sorted set in LDS.  Exact
  * for any content (repeats, low complexity, fewer distinct k-mers than
  * sketch_size, records of no window): no capacity and no retry.  There is no
- * min_count: that filter needs the counts.
+ * min_count: that filter needs the counts (kmc_sketch_accum_* below keeps them).
  *   data, indices, num_seqs, data_bytes  as kmc_count_dense: data a device pointer of
  *                 any alignment readable for [0, data_bytes), indices device
  *                 int64[num_seqs + 1] (offsets are clamped to [0, data_bytes])
@@ -629,6 +629,83 @@ KMC_API int kmc_sketch_screen_count(void *index, size_t index_bytes, const char 
 KMC_API int kmc_sketch_screen_results(const void *index, size_t index_bytes, const uint64_t *r_sketches,
                                       const uint32_t *r_sizes, uint64_t num_refs, uint32_t sketch_size, int k,
                                       uint32_t *shared, uint32_t *median_mult, float *identity, hipStream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* Sketching a sequence set of any size with a minimum k-mer abundance (Mash's -m).
+ * In reads a large share of the distinct k-mers are sequencing errors seen once; they
+ * fill the bottom of the hash range, so a bottom-s sketch of raw reads compares badly
+ * with the assembly of the same organism.  kmc_sketch_from_sequences[_grouped] has no
+ * counts, and kmc_count_canonical_hash counts per record, where every record is one
+ * read.  The accumulator counts over ALL records of ALL batches, but only the k-mers
+ * whose hash lies below a threshold, in a device hash table the handle owns:
+ *
+ * kmc_sketch_accum_create: a handle for sketches of sketch_size values with the
+ * windows, validity, keys, flags, k, seed and hash of kmc_sketch_from_sequences.
+ *   log2_slots  the table has C = 2^log2_slots slots of a key and a uint32 count,
+ *               KMC_SKETCH_ACCUM_MIN_LOG2_SLOTS .. KMC_SKETCH_ACCUM_MAX_LOG2_SLOTS
+ *               (16 slots .. 2^30); 0: the power of two at or above
+ *               KMC_SKETCH_ACCUM_DEFAULT_SLOTS_PER_VALUE * sketch_size
+ *   memory      kmc_sketch_accum_device_bytes(): 256 + 2 (8 C + 4 C) bytes and the
+ *               workspace of kmc_sketch_from_counts for one record (each array rounded
+ *               up to 256 bytes); host numbers only, 0 on bad arguments
+ * The allocation is made and cleared on the current device before the call returns.
+ *
+ * kmc_sketch_accum_add: the valid windows of the records (data, indices, num_seqs,
+ * data_bytes as kmc_sketch_from_sequences: any alignment, offsets clamped) join the
+ * one multiset of canonical keys of all adds since create or reset.  With N the sum of
+ * data_bytes so far, this call included (an upper bound of the windows), and j the
+ * smallest integer with ceil(N / 2^j) <= C / 4, a window takes part iff its hash is
+ * below 2^(64 - j); j never falls.  When a call raises j, the entries still below the
+ * new bound first move, with their counts, to a second table of the same size.  A new
+ * key is refused, and the smallest refused hash kept (`lost`), once C / 2 keys are
+ * tracked or its probe chain is 256 slots long; nothing else happens then.  Counts
+ * are exact while fewer than 2^32 windows have been added; beyond that they are
+ * modulo 2^32, with no stray access.  num_seqs == 0: KMC_OK, N is unchanged.
+ *
+ * kmc_sketch_accum_finish: with limit = min(2^(64 - j), lost), unbounded when j = 0
+ * and nothing was lost, every key with a hash below limit was tracked from its first
+ * window on.  Among those, the keys with multiplicity >= min_count (0 and 1: every
+ * key) are selected by kmc_sketch_from_counts itself, so the row is bit for bit what
+ * the count -> sketch path gives for them.
+ *   sketch_row       device uint64[sketch_size]: the smallest distinct hashes,
+ *                    ascending, then UINT64_MAX
+ *   sketch_size_out  device uint32: the number kept
+ *   stats            device uint64[4], may be NULL:
+ *                    [0] complete    1 iff *sketch_size_out == sketch_size or limit is
+ *                                    unbounded: the row is the true bottom-s.  Else
+ *                                    the row holds every qualifying hash below limit:
+ *                                    an exact prefix of it, shorter than sketch_size
+ *                                    (create the handle with more slots)
+ *                    [1] limit       the exclusive bound; UINT64_MAX when unbounded
+ *                    [2] tracked     keys tracked below limit
+ *                    [3] qualifying  those of them with multiplicity >= min_count
+ * It does not modify the accumulator: add, finish(1), finish(2), add, finish is a
+ * valid sequence.  kmc_sketch_accum_reset: as after create, N = 0 and j = 0.
+ * kmc_sketch_accum_free: releases everything (NULL: nothing).
+ *
+ * add, finish and reset are asynchronous on `stream`, with no host read-back; the
+ * work launched depends on the host arguments and the handle's N and j only.  Calls
+ * on one accumulator are ordered by the caller, on the device it was created on;
+ * different accumulators may overlap (no library-owned buffer is used).  Errors,
+ * judged before any device is touched: k outside 1..KMC_CANON_MAX_K:
+ * KMC_ERR_UNSUPPORTED_K; KMC_ERR_INVALID_ARG for a sketch_size outside
+ * 1..KMC_SKETCH_MAX_SIZE, unknown flag bits, log2_slots out of range, a null handle
+ * or `out`, null sketch_row or sketch_size_out, num_seqs above 2^40, null indices,
+ * null data with data_bytes > 0, an N that would reach 2^62.  KMC_ERR_NOMEM when
+ * create cannot allocate. */
+#define KMC_SKETCH_ACCUM_MIN_LOG2_SLOTS 4
+#define KMC_SKETCH_ACCUM_MAX_LOG2_SLOTS 30
+#define KMC_SKETCH_ACCUM_DEFAULT_SLOTS_PER_VALUE 4096
+typedef struct kmc_sketch_accum kmc_sketch_accum;
+KMC_API size_t kmc_sketch_accum_device_bytes(uint32_t sketch_size, uint32_t log2_slots);
+KMC_API int kmc_sketch_accum_create(uint32_t sketch_size, int k, unsigned flags, uint64_t seed, uint32_t log2_slots,
+                                    kmc_sketch_accum **out);
+KMC_API int kmc_sketch_accum_add(kmc_sketch_accum *a, const char *data, const int64_t *indices, uint64_t num_seqs,
+                                 uint64_t data_bytes, hipStream_t stream);
+KMC_API int kmc_sketch_accum_finish(kmc_sketch_accum *a, uint32_t min_count, uint64_t *sketch_row,
+                                    uint32_t *sketch_size_out, uint64_t *stats, hipStream_t stream);
+KMC_API int kmc_sketch_accum_reset(kmc_sketch_accum *a, hipStream_t stream);
+KMC_API void kmc_sketch_accum_free(kmc_sketch_accum *a);
 
 /* ------------------------------------------------------------------------ */
 /* Tracing (the reference times step 1 with cudaEvents, main.cu:262-300): when set,

@@ -15,6 +15,10 @@ With --screen: kmc_sketch_screen_build, _count and _results of 1000 references o
 1 Mbase (and of 100 of 5 kbase) in a mixture of 1000 x 1 Mbase, beside
 kmc_sketch_from_sequences_grouped over the same mixture as one group, the same walk
 plus the set upkeep (profiles/pr_sketch_screen.jsonl).
+With --accum: kmc_sketch_accum_add over the same mixture, as one call and as 16 calls
+(j rises and purges happen), and kmc_sketch_accum_finish, beside kmc_sketch_screen_count
+against the 1000-reference index and kmc_sketch_from_sequences_grouped with one group:
+the parent commit's code on the same walk (profiles/pr_sketch_accum.jsonl).
 
 Inputs (synthetic, generated on the device):
   iid          8 x 50 Mbase independent records, k = 31
@@ -313,6 +317,78 @@ def screen_main(args, dev):
             torch.cuda.empty_cache()
 
 
+def accum_main(args, dev):
+    """--accum: the abundance accumulator on the --screen mode's mixture, in this process.
+    The yardsticks are the screen count (walk, hash and prefilter only) and the grouped
+    sketch of one group (walk plus LDS set upkeep) on the same buffer.  Every timed add
+    starts from a reset accumulator (reset is timed alone too); the row of the one-call
+    and of the 16-call pass are asserted equal to the grouped sketch before anything is
+    timed (m = 1; what m = 2 keeps, the chance repeats among 10^9 random windows that lie
+    below the threshold, is recorded)."""
+    k, s, records, calls = 21, 1000, 1000, 16
+    record_len = max(int(1_000_000 * args.scale), 5000)
+    mix = torch.empty(records * (record_len + 1), dtype=torch.uint8, device=dev)
+    kmc.synth_fill(mix, records, record_len, 0x5EED0008)
+    midx = torch.from_numpy(kmc.synth_indices(records, record_len)).to(dev)
+    one_group = torch.tensor([0, records], dtype=torch.int64, device=dev)
+    # the screen mode's "genomes" index
+    refs = torch.empty(records * (record_len + 1), dtype=torch.uint8, device=dev)
+    kmc.synth_fill(refs, records, record_len, 0x5EED0009)
+    refs.view(records, record_len + 1)[::2] = mix.view(records, record_len + 1)[::2]
+    sk, sz = kmc.sketch_from_sequences(refs, midx, k, s)
+    del refs
+    index = kmc.sketch_screen_build(sk, sz)
+    # the 16 calls: consecutive records, offsets from each piece's first byte
+    cuts = [records * c // calls for c in range(calls + 1)]
+    pieces = []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        lo, hi = a * (record_len + 1), b * (record_len + 1)
+        pieces.append((mix[lo:hi], (midx[a:b + 1] - lo).contiguous()))
+    lg = max((4096 * s - 1).bit_length(), kmc.SKETCH_ACCUM_MIN_LOG2_SLOTS)  # the default table (kmc.h)
+    levels, n = [], 0
+    for d, _ in pieces:
+        n += int(d.numel())
+        levels.append(next(j for j in range(64) if -(-n // (1 << j)) <= (1 << lg) // 4))
+    acc = kmc.SketchAccum(s, k)
+
+    def whole():
+        acc.reset()
+        acc.add(mix, midx)
+
+    def in_calls():
+        acc.reset()
+        for d, i in pieces:
+            acc.add(d, i)
+
+    grp = kmc.sketch_from_sequences_grouped(mix, midx, one_group, k, s)
+    stats = {}
+    for name, fn in (("one_call", whole), ("16_calls", in_calls)):
+        fn()
+        row, size, st = acc.finish(1)
+        none = acc.finish(2, stats=False)
+        torch.cuda.synchronize()
+        assert torch.equal(row, grp[0][0]) and int(size[0]) == int(grp[1][0]) == s and int(st[0]) == 1, name
+        stats[name] = [int(x) for x in st.cpu().numpy().view(np.uint64)] + [int(none[1][0])]
+    rec = {
+        "mixture_records": records, "mixture_record_len": record_len, "k": k, "sketch_size": s,
+        "log2_slots": lg, "device_bytes": kmc.sketch_accum_device_bytes(s), "calls": calls,
+        "levels_of_the_16_calls": levels, "final_j": levels[-1], "rows_equal_grouped": True,
+        # complete, limit, tracked, qualifying at m = 1; then the size of the m = 2 row
+        "stats_one_call": stats["one_call"], "stats_16_calls": stats["16_calls"],
+        "kmc_sketch_accum_reset": timed(lambda: acc.reset(), args.runs),
+        "reset_and_add_one_call": timed(whole, args.runs),
+        "reset_and_add_16_calls": timed(in_calls, args.runs),
+        "kmc_sketch_accum_finish": timed(lambda: acc.finish(2), args.runs),
+        "kmc_sketch_screen_count": timed(lambda: kmc.sketch_screen_count(index, mix, midx, k), args.runs),
+        "kmc_sketch_from_sequences_grouped": timed(
+            lambda: kmc.sketch_from_sequences_grouped(mix, midx, one_group, k, s), args.runs),
+    }
+    acc.close()
+    with open(args.out, "a") as out:
+        out.write(json.dumps(rec) + "\n")
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(HERE), "profiles", "pr_sketch.jsonl"))
@@ -339,8 +415,16 @@ def main():
                          "whole) in a synthetic mixture of 1000 x 1 Mbase, beside kmc_sketch_from_sequences_grouped "
                          "over the mixture as one group (2 warm-ups, median of --runs); appends to "
                          "--out profiles/pr_sketch_screen.jsonl")
+    ap.add_argument("--accum", action="store_true",
+                    help="time kmc_sketch_accum_add of the --screen mixture (1000 x 1 Mbase, s = 1000, k = 21) as one "
+                         "call and as 16 calls, and kmc_sketch_accum_finish, beside kmc_sketch_screen_count against "
+                         "the 1000-reference index and kmc_sketch_from_sequences_grouped with one group (rows "
+                         "asserted equal; 2 warm-ups, median of --runs); appends to --out "
+                         "profiles/pr_sketch_accum.jsonl")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.accum:
+        return accum_main(args, dev)
     if args.screen:
         return screen_main(args, dev)
     if args.query:
