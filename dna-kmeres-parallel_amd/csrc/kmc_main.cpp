@@ -27,7 +27,8 @@
 // kmc_fastq_load_device, and a --screen FILE in FASTQ is streamed batch by batch
 // (kmc_fastq_open / _next / _close), so its size is not bounded by device memory.
 // --per-file --min-abundance M: every file is one pass of the abundance accumulator
-// (kmc_sketch_accum_*), a FASTQ file streamed the same way.
+// (kmc_sketch_accum_*), a FASTQ file streamed the same way.  --cluster D: the sketches, however
+// made, are grouped at Mash distance D (kmc_sketch_cluster -> clusters.tsv) instead of compared.
 // GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
@@ -82,6 +83,8 @@ struct Options {
     long accum_slots = 0;       // --accum-slots LOG2 (0: the library's default)
     uint64_t batch = 0;         // --batch BYTES: the reader's batches of a --min-abundance FASTQ file
     bool accum_slots_set = false, batch_set = false;
+    double cluster = 0.0;  // --cluster D: clusters of the sketches at Mash distance D instead of their distances
+    bool cluster_set = false;
 };
 
 // auto: FASTQ exactly when the name ends in .fq or .fastq, whatever the case
@@ -102,6 +105,7 @@ void usage(FILE *f) {
             "       kmc --canonical --sketch S --sketch-direct --screen reads.fasta [--screen ...] [options] <refs.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --screen reads.fastq [--screen-batch BYTES] [options] <refs.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --per-file --min-abundance M [--batch BYTES] [options] <a.fastq> ...\n"
+            "       kmc --canonical --sketch S [--sketch-direct] [--per-file] --cluster D [options] <input.fasta> ...\n"
             "       kmc synth OUT.fa RECORDS LENGTH [SEED]   (benchmark input, SURVEY.md 8(d))\n"
             "  -k K              k-mer length (default %d, the reference's K); dense path 1..%d,\n"
             "                    --canonical 1..%d\n"
@@ -187,6 +191,15 @@ void usage(FILE *f) {
             "                    (default 0: the power of two at or above %d S)\n"
             "  --batch B         with --min-abundance: raw bytes per batch of a streamed FASTQ file\n"
             "                    (default 0: 256 MiB)\n"
+            "  --cluster D       with --canonical --sketch S (with or without --sketch-direct, --per-file,\n"
+            "                    --min-count, --min-abundance), not with --query or --screen: the sketches,\n"
+            "                    made as without it, are grouped at Mash distance D in 0..1 instead of\n"
+            "                    compared (kmc_sketch_cluster at kmc_mash_jaccard_of_distance(D, k), single\n"
+            "                    linkage: records whose distance is at most D, and everything such pairs\n"
+            "                    connect, form a cluster).  <out>/clusters.tsv gets one line per record (per\n"
+            "                    file with --per-file): index<TAB>representative<TAB>cluster<TAB>size, the\n"
+            "                    representative being the cluster's smallest index and clusters numbered by\n"
+            "                    it; sketch_results.csv is not written (no distance is kept)\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
@@ -290,6 +303,15 @@ int parse(int argc, char **argv, Options &o) {
                 return usage(stderr), 2;
             }
             o.batch = (uint64_t)b;
+        } else if (a == "--cluster") {
+            char *end = nullptr;
+            const char *v = next("--cluster");
+            o.cluster = strtod(v, &end);
+            o.cluster_set = true;
+            if (end == v || *end != '\0' || !(o.cluster >= 0.0 && o.cluster <= 1.0)) {
+                fprintf(stderr, "kmc: --cluster takes a Mash distance in 0..1\n");
+                return usage(stderr), 2;
+            }
         } else if (a == "--softmask") {
             o.softmask = true;
         } else if (a == "--host-loader") {
@@ -361,6 +383,10 @@ int parse(int argc, char **argv, Options &o) {
     }
     if (o.top < 0 || o.top > KMC_NEAREST_MAX_TOP || o.min_shared < 0 || o.min_shared > (long)UINT32_MAX) {
         fprintf(stderr, "kmc: --top must be in 0..%d, --min-shared in 0..%u\n", KMC_NEAREST_MAX_TOP, UINT32_MAX);
+        return usage(stderr), 2;
+    }
+    if (o.cluster_set && (o.sketch == 0 || !o.query.empty() || !o.screen.empty())) {
+        fprintf(stderr, "kmc: --cluster groups the sketches of --canonical --sketch S: not with --query or --screen\n");
         return usage(stderr), 2;
     }
     if (o.screen_batch && o.screen.empty()) {
@@ -557,6 +583,41 @@ int step2(const Options &o, uint64_t n, hipStream_t st, bool even_empty, std::ve
     return 0;
 }
 
+// --cluster D: the rows' clusters at Mash distance D, clusters.tsv; no distance leaves the device
+int cluster_step(const Options &o, const uint64_t *d_sk, const uint32_t *d_sz, uint64_t n, hipStream_t st,
+                 hipEvent_t r0, hipEvent_t r1) {
+    const uint32_t s = (uint32_t)o.sketch;
+    DevBuf<uint32_t> d_lab, d_idx;
+    Event t0 = make_event(), t1 = make_event();
+    HIPCHK(dev_alloc(d_lab, n));
+    HIPCHK(dev_alloc(d_idx, n));
+    HIPCHK(hipEventRecord(t0.get(), st));
+    KMCCHK(kmc_sketch_cluster(d_sk, d_sz, n, s, kmc_mash_jaccard_of_distance(o.cluster, o.k), d_lab.get(), d_idx.get(),
+                              nullptr, nullptr, 0, st));
+    HIPCHK(hipEventRecord(t1.get(), st));
+    HIPCHK(hipEventSynchronize(t1.get()));
+    std::vector<uint32_t> lab(n), idx(n), size(n, 0);
+    if (n > 0) {
+        HIPCHK(hipMemcpy(lab.data(), d_lab.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(idx.data(), d_idx.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    uint64_t clusters = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (lab[i] >= n) return fprintf(stderr, "kmc: kmc_sketch_cluster: label out of range\n"), 1;
+        clusters += size[lab[i]]++ == 0;
+    }
+    if (!o.quiet) {
+        printf("Sketch (s=%u): %.3f ms\n", s, ms_between(r0, r1));
+        printf("Sketch clusters (distance <= %g): %.3f ms, %" PRIu64 " clusters of %" PRIu64 " records\n", o.cluster,
+               ms_between(t0.get(), t1.get()), clusters, n);
+    }
+    const std::string path = o.out_dir + "/clusters.tsv";
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return fprintf(stderr, "kmc: cannot write %s\n", path.c_str()), 1;
+    for (uint64_t i = 0; i < n; ++i) fprintf(f, "%" PRIu64 "\t%u\t%u\t%u\n", i, lab[i], idx[i], size[lab[i]]);
+    return fclose(f) == 0 ? 0 : 1;
+}
+
 // --sketch: the rows of every record (make_rows: from the canonical lists or, with
 // --sketch-direct, from the record buffer), their Mash distances, sketch_results.csv
 template <class MakeRows>
@@ -570,6 +631,7 @@ int sketch_step(const Options &o, MakeRows make_rows, uint64_t n, hipStream_t st
     HIPCHK(hipEventRecord(r0.get(), st));
     KMCCHK(make_rows(s, d_sk.get(), d_sz.get()));
     HIPCHK(hipEventRecord(r1.get(), st));
+    if (o.cluster_set) return cluster_step(o, d_sk.get(), d_sz.get(), n, st, r0.get(), r1.get());
     const auto distances = [&](float *d_out) {
         return kmc_sketch_distances(d_sk.get(), d_sz.get(), n, s, o.k, d_out, nullptr, nullptr, st);
     };

@@ -41,8 +41,8 @@
 // pairs; a workgroup stages the 2T rows of a tile in LDS and its 16 wavefronts
 // take the tile's pairs.  The kernel, its tile loop and the pair's counts are
 // kmc_sketch_pair.h's, shared with the rectangle and the search of
-// kmc_sketch_query.hip; this file gives the shape Triangle (which tile, which pairs,
-// where a result goes).  For a pair (A, B) the lanes take 64 consecutive
+// kmc_sketch_query.hip; the shape is Triangle of kmc_sketch_triangle.h (which tile,
+// which pairs, where a result goes).  For a pair (A, B) the lanes take 64 consecutive
 // elements x of A, lower-bound them in B (pos, match), and with the matches
 // before x (a ballot prefix) get the element's rank in the union,
 //     rank = (x + 1) + (pos + match) - matches(A[0..x]),
@@ -72,6 +72,7 @@
 #include "kmc_dist_common.h"
 #include "kmc_internal.h"
 #include "kmc_sketch_pair.h"
+#include "kmc_sketch_triangle.h"
 #include "kmc_walk.h"
 #include "kmc_workspace.h"
 
@@ -249,21 +250,8 @@ __global__ __launch_bounds__(BLOCK) void sketch_sort_kernel(KParams p) {
 // ---------------------------------------------------------------------------
 // distances
 // ---------------------------------------------------------------------------
-// The packed upper triangle as a shape of sketch_dist_kernel (kmc_sketch_pair.h): both
-// row sets are the one set, the tiles are square, and tile t is the t-th of the nt
-// tile rows' upper triangle, diagonal included.
-struct Triangle {
-    static __device__ __forceinline__ void tile(const DParams &p, int64_t t, uint64_t *buf, TileRows &A, TileRows &B) {
-        // with its diagonal it is the strict triangle of nt + 1: b nt - b (b - 1) / 2 = (nt + 1) b - b (b + 1) / 2
-        const int64_t bi = tri_row(t, p.nrt + 1), bj = bi + (t - tri_row_start(bi, p.nrt + 1));
-        A = TileRows{p.q, p.qs, bi * p.Tq, p.n, buf};
-        B = TileRows{p.q, p.qs, bj * p.Tq, p.n, buf + p.Tq * (int)p.s};
-    }
-    static __device__ __forceinline__ bool counts(int64_t i, int64_t j) { return i < j; }
-    static __device__ __forceinline__ int64_t index(const DParams &p, int64_t i, int64_t j) {
-        return tri_index(i, j, p.n);
-    }
-};
+// The packed upper triangle is the shape Triangle of kmc_sketch_triangle.h, which the
+// clustering (kmc_sketch_cluster.hip) walks as well.
 
 // ---------------------------------------------------------------------------
 // host
@@ -370,19 +358,10 @@ extern "C" int kmc_sketch_distances(const uint64_t *sketches, const uint32_t *sk
     if (!sketch_size_ok(sketch_size)) return KMC_ERR_INVALID_ARG;
     if (num_seqs > KMC_SPARSE_MAX_SEQS) return KMC_ERR_INVALID_ARG;
     DParams p;
-    p.q = p.r = sketches;
-    p.qs = p.rs = sketch_sizes;
-    p.m = p.n = (int64_t)num_seqs;
-    p.s = sketch_size;
     p.k = k;
     p.out = out;
     p.shared = shared;
     p.denom = denom;
-    bool stage = false;
-    int T = tile_edge(kDistElems, sketch_size, &stage);  // square: not the rectangle's Tr
-    if ((int64_t)T > p.n) T = (int)p.n;
-    p.Tq = p.Tr = T;
-    p.nrt = ceil_div(p.n, T);
-    p.ntiles = p.nrt * (p.nrt + 1) / 2;
+    const bool stage = triangle_tiling(p, sketches, sketch_sizes, (int64_t)num_seqs, sketch_size);
     return launch_sketch_dist<Triangle>(p, stage, stream);
 }

@@ -223,6 +223,12 @@ def _load(path):
     L.kmc_sketch_nearest_workspace_size.argtypes = [_U64, _U64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
     L.kmc_sketch_nearest.argtypes = [_P, _P, _U64, _P, _P, _U64, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
                                      ctypes.c_uint32, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
+    L.kmc_mash_jaccard_of_distance.restype = ctypes.c_double
+    L.kmc_mash_jaccard_of_distance.argtypes = [ctypes.c_double, ctypes.c_int]
+    L.kmc_sketch_cluster_workspace_size.restype = ctypes.c_size_t
+    L.kmc_sketch_cluster_workspace_size.argtypes = [_U64, ctypes.c_int]
+    L.kmc_sketch_cluster.argtypes = [_P, _P, _U64, ctypes.c_uint32, ctypes.c_double, _P, _P, _P, _P, ctypes.c_size_t,
+                                     _P]
     L.kmc_sketch_screen_index_size.restype = ctypes.c_size_t
     L.kmc_sketch_screen_index_size.argtypes = [_U64, ctypes.c_uint32]
     L.kmc_sketch_screen_build.argtypes = [_P, _P, _U64, ctypes.c_uint32, _P, ctypes.c_size_t, _P]
@@ -640,6 +646,40 @@ def sketch_nearest(q, qs, r, rs, k, top, min_shared=1, workspace=None, out=None,
                                   _stream(stream))
     _check(rc, "kmc_sketch_nearest")
     return refs, sh, dn, dist, counts
+
+
+def mash_jaccard_of_distance(d, k):
+    """The Jaccard threshold of a Mash distance d at k-mer length k
+    (kmc_mash_jaccard_of_distance): e^(-k d) / (2 - e^(-k d)); NaN for a bad d or k."""
+    return float(lib().kmc_mash_jaccard_of_distance(float(d), int(k)))
+
+
+def sketch_cluster_workspace_size(num_seqs, device=0):
+    return int(lib().kmc_sketch_cluster_workspace_size(num_seqs, device))
+
+
+def sketch_cluster(sketches, sizes, min_jaccard, index=True, workspace=None, out=None, stream=None):
+    """Single-linkage clusters of sketch rows [n, s] with sizes [n] (kmc_sketch_cluster):
+    rows i and j are linked iff denom > 0 and shared >= min_jaccard * denom.  Returns
+    (labels int32 [n], cluster_index int32 [n], num_clusters int32 [1]): the smallest
+    index of each row's cluster, the cluster's rank by that index, and the number of
+    clusters; index=False: (labels, None, None), no ranking.  `out` is the caller's
+    own triple, whose second and third entries may be None."""
+    import torch
+    with _on(stream):
+        sketches = sketches.contiguous()
+        n, s = int(sketches.shape[0]), int(sketches.shape[1])
+        if out is not None:
+            labels, cidx, count = out
+        else:
+            dev = sketches.device
+            labels = torch.empty(max(n, 1), dtype=torch.int32, device=dev)  # (no row: still a pointer to pass)
+            cidx = torch.empty(n, dtype=torch.int32, device=dev) if index else None
+            count = torch.empty(1, dtype=torch.int32, device=dev) if index else None
+    rc = lib().kmc_sketch_cluster(_dptr(sketches), _dptr(sizes), n, s, float(min_jaccard), _dptr(labels), _dptr(cidx),
+                                  _dptr(count), *_ws(workspace), _stream(stream))
+    _check(rc, "kmc_sketch_cluster")
+    return labels[:n], cidx, count
 
 
 SCREEN_MAX_VALUES = 1 << 30

@@ -331,10 +331,11 @@ KMC_API int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *coun
  * every k-mer costs too much.  A record is reduced to its sketch_size smallest
  * distinct key hashes; distances come from those sorted lists alone, and sketches
  * made in separate calls (with one seed and sketch_size) may be concatenated.
- * The rows have two consumers: kmc_sketch_distances, all pairs of one row set, and
+ * The rows have three consumers: kmc_sketch_distances, all pairs of one row set;
  * the search of one row set (the queries) in another (the references):
  * kmc_sketch_distances_rect, every query against every reference, and
- * kmc_sketch_nearest, the best references of every query without that rectangle.
+ * kmc_sketch_nearest, the best references of every query without that rectangle; and
+ * kmc_sketch_cluster, the groups of one row set at a threshold without its pairs.
  *
  * kmc_sketch_from_counts: sketches of the per-record lists of
  * kmc_count_canonical_hash[_ex], with the list conventions of
@@ -508,7 +509,54 @@ KMC_API int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *coun
  * sketch_size outside 1..KMC_SKETCH_MAX_SIZE and, with num_queries > 0, null
  * hit_refs or hit_counts, or null rows or sizes with num_refs > 0.  The size query
  * returns 0 on bad arguments (and needs no device for those), and 0 when either
- * count is 0: no workspace is used then. */
+ * count is 0: no workspace is used then.
+ *
+ * kmc_sketch_cluster: the records of one row set grouped at a similarity threshold
+ * (dereplication), without the triangle of their distances.
+ *   link rule     records i < j are linked iff neither row is empty (so denom(i, j) > 0) and
+ *                     (double)shared >= min_jaccard * (double)denom
+ *                 with shared and denom exactly kmc_sketch_distances' (the same device
+ *                 function; rows assumed ascending, sizes clamped to sketch_size).  One
+ *                 IEEE double product and one compare of integers at most 16384: a host
+ *                 that applies the rule to the triangle's counts gets the same links bit
+ *                 for bit.  Like kmc_sketch_nearest's order the rule is defined on the
+ *                 integers: it depends neither on the device's log nor on the cap at
+ *                 1.0.  Two empty rows (denom 0) are never linked, and an empty row has
+ *                 shared 0 of denom > 0 with a row that is not, which only min_jaccard
+ *                 == 0 would accept: the rule leaves that pair out, so an empty row is
+ *                 always a cluster of its own.  min_jaccard == 0 links every pair of
+ *                 rows that are not empty; min_jaccard == 1 only pairs with shared ==
+ *                 denom.
+ *   clusters      the connected components of the link graph (single linkage)
+ *   labels        device uint32[num_seqs]: the smallest record index of i's component,
+ *                 the cluster's representative.  The input determines it, whatever
+ *                 order the device links in.
+ *   cluster_index device uint32[num_seqs], may be NULL: the rank of i's cluster among
+ *                 all clusters ordered by representative, 0 .. C - 1
+ *   num_clusters  device uint32, may be NULL: C
+ *   workspace     device scratch of kmc_sketch_cluster_workspace_size() bytes, 8-byte
+ *                 aligned (KMC_ERR_ALIGNMENT), or NULL for a library-owned buffer under
+ *                 kmc_pair_distances' rule (NULL-workspace calls on a device must not
+ *                 overlap); KMC_ERR_WORKSPACE when smaller.  The union-find parent of
+ *                 every record, a representative flag per record, their exclusive scan
+ *                 and the scan's partials:
+ *                     4 n  +  4 n  +  8 (n + 1)  +  8 ceil(n / 4096)  bytes, n = num_seqs
+ *                 (each array rounded up to 256).  The same for every call, whichever
+ *                 optional output is asked for; it does not depend on the device.
+ * Asynchronous on `stream`, no host read-back; the work launched depends on the host
+ * arguments only; nothing a former call left in the workspace is read.  Errors, judged
+ * before any device is touched: KMC_ERR_INVALID_ARG for a sketch_size outside
+ * 1..KMC_SKETCH_MAX_SIZE, num_seqs above KMC_SPARSE_MAX_SEQS, a min_jaccard outside
+ * [0, 1] or NaN, null labels, and null sketches or sketch_sizes with num_seqs > 0.
+ * num_seqs == 0: KMC_OK, *num_clusters = 0 when it is given, nothing else is written.
+ * num_seqs == 1: label 0, index 0, one cluster.  The size query returns 0 on bad
+ * arguments and for num_seqs == 0, and needs no device.
+ *
+ * kmc_mash_jaccard_of_distance: the threshold of kmc_sketch_cluster for a Mash distance.
+ * Host only, no device: e^(-k d) / (2 - e^(-k d)) in double, the J at which
+ * -log(2J / (1 + J)) / k equals d, so a pair's distance is at most d exactly when its J
+ * is at least this value.  NaN for d outside [0, 1] (or NaN) and for k outside
+ * 1..KMC_CANON_MAX_K. */
 #define KMC_SKETCH_MAX_SIZE 16384
 #define KMC_NEAREST_MAX_TOP 1024
 #define KMC_SKETCH_DEFAULT_SEED 42ull
@@ -548,6 +596,11 @@ KMC_API int kmc_sketch_nearest(const uint64_t *q_sketches, const uint32_t *q_siz
                                uint32_t sketch_size, int k, uint32_t top, uint32_t min_shared,
                                uint32_t *hit_refs, uint32_t *hit_shared, uint32_t *hit_denom, float *hit_dist,
                                uint32_t *hit_counts, void *workspace, size_t workspace_bytes, hipStream_t stream);
+KMC_API double kmc_mash_jaccard_of_distance(double max_dist, int k);
+KMC_API size_t kmc_sketch_cluster_workspace_size(uint64_t num_seqs, int device);
+KMC_API int kmc_sketch_cluster(const uint64_t *sketches, const uint32_t *sketch_sizes, uint64_t num_seqs,
+                               uint32_t sketch_size, double min_jaccard, uint32_t *labels, uint32_t *cluster_index,
+                               uint32_t *num_clusters, void *workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Screening a sequence set for the references it contains (containment; what Mash

@@ -19,6 +19,8 @@ With --accum: kmc_sketch_accum_add over the same mixture, as one call and as 16 
 (j rises and purges happen), and kmc_sketch_accum_finish, beside kmc_sketch_screen_count
 against the 1000-reference index and kmc_sketch_from_sequences_grouped with one group:
 the parent commit's code on the same walk (profiles/pr_sketch_accum.jsonl).
+With --cluster: kmc_sketch_cluster beside kmc_sketch_distances on the same rows, unrelated
+rows and 64-member clusters of near-identical rows (profiles/pr_sketch_cluster.jsonl).
 
 Inputs (synthetic, generated on the device):
   iid          8 x 50 Mbase independent records, k = 31
@@ -267,6 +269,69 @@ def query_main(args, dev):
             torch.cuda.empty_cache()
 
 
+def clustered_rows(n, s, dev, seed, members=64, changed=0.02):
+    """n full rows in groups of `members`: every row of a group is the group's base row
+    (synthetic_rows) with about `changed` of its values replaced by values of its own."""
+    base, _ = synthetic_rows((n + members - 1) // members, s, dev, seed)
+    rows = base.repeat_interleave(members, dim=0)[:n].clone()
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed + 1)
+    hit = torch.rand((n, s), device=dev, generator=g) < changed
+    rows[hit] = torch.randint(0, 1 << 62, (int(hit.sum()),), dtype=torch.int64, device=dev, generator=g)
+    rows = torch.sort(rows, dim=1).values
+    dup = torch.zeros_like(rows, dtype=torch.bool)
+    dup[:, 1:] = rows[:, 1:] == rows[:, :-1]
+    rows = torch.sort(rows + dup * torch.arange(1, s + 1, device=dev), dim=1).values
+    return rows.contiguous(), torch.full((n,), s, dtype=torch.int32, device=dev)
+
+
+def cluster_main(args, dev):
+    """--cluster: kmc_sketch_cluster at the Jaccard threshold of Mash distance 0.05 beside
+    kmc_sketch_distances, the existing code that reads the same rows through the same
+    tiles, in one process.  unrelated: no pair is linked; clustered: groups of 64 rows
+    that differ in 2 % of their values.  The labels are asserted before anything is
+    timed.  The margin is DESIGN.md 4.3c's: the clustering may be slower than the
+    triangle by at most twice the spread (max - min) of the triangle's own runs."""
+    k, s, members = 21, 1000, 64
+    mj = kmc.mash_jaccard_of_distance(0.05, k)
+    with open(args.out, "w") as out:
+        for n in (4096, 65536):
+            n = max(int(n * args.scale), 2 * members)
+            runs = args.runs if n <= 8192 else max(5, args.runs // 2)
+            for name, make in (("unrelated", synthetic_rows), ("clustered", clustered_rows)):
+                rows, sizes = make(n, s, dev, 3)
+                labels, index, count = kmc.sketch_cluster(rows, sizes, mj)
+                torch.cuda.synchronize()
+                ids = torch.arange(n, device=dev, dtype=torch.int32)
+                exp = ids if name == "unrelated" else ids // members * members
+                assert torch.equal(labels, exp), name
+                assert torch.equal(index, ids if name == "unrelated" else ids // members)
+                assert int(count) == (n if name == "unrelated" else (n + members - 1) // members)
+                tri_out = torch.empty(n * (n - 1) // 2, dtype=torch.float32, device=dev)
+                ws = torch.empty(kmc.sketch_cluster_workspace_size(n), dtype=torch.uint8, device=dev)
+                outs = (labels, index, count)
+                tri = timed(lambda: kmc.sketch_distances(rows, sizes, k, out=(tri_out, None, None)), runs, warmup=1)
+                clu = timed(lambda: kmc.sketch_cluster(rows, sizes, mj, workspace=ws, out=outs), runs, warmup=1)
+                only = timed(lambda: kmc.sketch_cluster(rows, sizes, mj, workspace=ws, out=(labels, None, None)), runs,
+                             warmup=1)
+                spread = tri["ms_max"] - tri["ms_min"]
+                rec = {
+                    "collection": name, "rows": n, "sketch_size": s, "k": k, "max_dist": 0.05, "min_jaccard": mj,
+                    "members": members if name == "clustered" else 1, "clusters": int(count),
+                    "pairs": n * (n - 1) // 2, "triangle_bytes": 4 * (n * (n - 1) // 2),
+                    "workspace_bytes_cluster": kmc.sketch_cluster_workspace_size(n), "same_root_skip": False,
+                    "kmc_sketch_distances": tri, "kmc_sketch_cluster": clu, "kmc_sketch_cluster_labels_only": only,
+                    "triangle_spread_ms": spread,
+                    "cluster_minus_triangle_ms": clu["ms_median"] - tri["ms_median"],
+                    "within_margin": clu["ms_median"] <= tri["ms_median"] + 2 * spread,
+                }
+                out.write(json.dumps(rec) + "\n")
+                out.flush()
+                print(json.dumps(rec), flush=True)
+                del rows, sizes, tri_out, ws, labels, index, count
+                torch.cuda.empty_cache()
+
+
 def screen_main(args, dev):
     """--screen: references in a mixture.  Half of the references are cut from the
     mixture (reference r, r even, is the head of mixture record r); shared == size is
@@ -421,8 +486,15 @@ def main():
                          "the 1000-reference index and kmc_sketch_from_sequences_grouped with one group (rows "
                          "asserted equal; 2 warm-ups, median of --runs); appends to --out "
                          "profiles/pr_sketch_accum.jsonl")
+    ap.add_argument("--cluster", action="store_true",
+                    help="time kmc_sketch_cluster beside kmc_sketch_distances on the same rows: 4096 and 65536 rows "
+                         "of s = 1000, unrelated and in 64-member clusters of near-identical rows (labels asserted; "
+                         "1 warm-up, median of --runs, of at least 5 at 65536 rows); --out "
+                         "profiles/pr_sketch_cluster.jsonl")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.cluster:
+        return cluster_main(args, dev)
     if args.accum:
         return accum_main(args, dev)
     if args.screen:
