@@ -27,7 +27,9 @@
 // kmc_fastq_load_device, and a --screen FILE in FASTQ is streamed batch by batch
 // (kmc_fastq_open / _next / _close), so its size is not bounded by device memory.
 // --per-file --min-abundance M: every file is one pass of the abundance accumulator
-// (kmc_sketch_accum_*), a FASTQ file streamed the same way.  --cluster D: the sketches, however
+// (kmc_sketch_accum_*), a FASTQ file streamed the same way; --spectrum B: that pass's abundance
+// spectrum (kmc_spectrum_from_accum, kmc_spectrum_summarize -> spectrum.tsv, spectrum_summary.tsv),
+// from which --min-abundance auto takes every file's M.  --cluster D: the sketches, however
 // made, are grouped at Mash distance D (kmc_sketch_cluster -> clusters.tsv) instead of compared.
 // GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
@@ -83,6 +85,8 @@ struct Options {
     long accum_slots = 0;       // --accum-slots LOG2 (0: the library's default)
     uint64_t batch = 0;         // --batch BYTES: the reader's batches of a --min-abundance FASTQ file
     bool accum_slots_set = false, batch_set = false;
+    bool min_abundance_auto = false;  // --min-abundance auto: every file's M is its spectrum's valley
+    long spectrum = 0;                // --spectrum B: the abundance spectrum of every input file, B bins (0: not given)
     double cluster = 0.0;  // --cluster D: clusters of the sketches at Mash distance D instead of their distances
     bool cluster_set = false;
 };
@@ -105,6 +109,7 @@ void usage(FILE *f) {
             "       kmc --canonical --sketch S --sketch-direct --screen reads.fasta [--screen ...] [options] <refs.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --screen reads.fastq [--screen-batch BYTES] [options] <refs.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --per-file --min-abundance M [--batch BYTES] [options] <a.fastq> ...\n"
+            "       kmc --canonical --sketch S --sketch-direct --per-file --spectrum B [--min-abundance auto] [options] <a.fastq> ...\n"
             "       kmc --canonical --sketch S [--sketch-direct] [--per-file] --cluster D [options] <input.fasta> ...\n"
             "       kmc synth OUT.fa RECORDS LENGTH [SEED]   (benchmark input, SURVEY.md 8(d))\n"
             "  -k K              k-mer length (default %d, the reference's K); dense path 1..%d,\n"
@@ -187,9 +192,25 @@ void usage(FILE *f) {
             "                    is read whole and added in one call.  One line per file gives its records,\n"
             "                    batches, sketch size, threshold level j and whether the sketch is complete; a\n"
             "                    file whose sketch is not complete ends the run: raise --accum-slots\n"
-            "  --accum-slots L   with --min-abundance: the accumulator's table has 2^L slots, L in %d..%d\n"
-            "                    (default 0: the power of two at or above %d S)\n"
-            "  --batch B         with --min-abundance: raw bytes per batch of a streamed FASTQ file\n"
+            "                    M may be `auto`: every file then gets the min_abundance of its own abundance\n"
+            "                    spectrum (kmc_spectrum_summarize: the valley between the k-mers of sequencing\n"
+            "                    errors and the coverage peak; 1 for a file without one, such as an assembly),\n"
+            "                    taken with the bins of --spectrum, or 256; its line then ends `min-abundance M`\n"
+            "  --spectrum B      with --canonical --sketch S --sketch-direct --per-file only: the abundance spectrum\n"
+            "                    of every input file (not of a --query FILE or the references of --screen), B bins\n"
+            "                    in 2..%d: how many distinct k-mers the file holds once, twice, ... (the last bin:\n"
+            "                    B - 1 times or more), taken from the accumulator's pass before its sketch\n"
+            "                    (kmc_spectrum_from_accum); without --min-abundance that pass runs with M = 1, so\n"
+            "                    the sketches are those of the run without --spectrum.  When the table holds only\n"
+            "                    the k-mers whose hash is below a limit, the numbers are those of that uniform\n"
+            "                    sample and scale = 2^64 / limit estimates the file's.  <out>/spectrum.tsv gets\n"
+            "                    file<TAB>c<TAB>hist[c]<TAB>scale*hist[c] for every c >= 1 with hist[c] > 0;\n"
+            "                    <out>/spectrum_summary.tsv one line per file: file, path, limit, scale, k-mers\n"
+            "                    sampled, windows sampled, distinct, total, valley, peak, the M used, saturated,\n"
+            "                    genome_size (kmc_spectrum_summarize)\n"
+            "  --accum-slots L   with --min-abundance or --spectrum: the accumulator's table has 2^L slots, L in\n"
+            "                    %d..%d (default 0: the power of two at or above %d S)\n"
+            "  --batch B         with --min-abundance or --spectrum: raw bytes per batch of a streamed FASTQ file\n"
             "                    (default 0: 256 MiB)\n"
             "  --cluster D       with --canonical --sketch S (with or without --sketch-direct, --per-file,\n"
             "                    --min-count, --min-abundance), not with --query or --screen: the sketches,\n"
@@ -206,7 +227,7 @@ void usage(FILE *f) {
             "  -q                quiet (no progress lines)\n",
             KMC_DROPIN_K, KMC_DENSE_MAX_K, KMC_CANON_MAX_K, KMC_MAX_SEQS_REFERENCE, KMC_MAX_SEQS_REFERENCE + 1,
             KMC_DROPIN_K, KMC_CANON_MAX_K, (unsigned long long)KMC_SKETCH_DEFAULT_SEED, KMC_SKETCH_MAX_SIZE,
-            KMC_NEAREST_MAX_TOP, KMC_SKETCH_ACCUM_MIN_LOG2_SLOTS, KMC_SKETCH_ACCUM_MAX_LOG2_SLOTS,
+            KMC_NEAREST_MAX_TOP, KMC_SPECTRUM_MAX_BINS, KMC_SKETCH_ACCUM_MIN_LOG2_SLOTS, KMC_SKETCH_ACCUM_MAX_LOG2_SLOTS,
             KMC_SKETCH_ACCUM_DEFAULT_SLOTS_PER_VALUE);
 }
 
@@ -281,9 +302,17 @@ int parse(int argc, char **argv, Options &o) {
             if (b < 0 || b >= (1ll << 32)) return fprintf(stderr, "kmc: --screen-batch must be in 0..2^32-1\n"), 2;
             o.screen_batch = (uint64_t)b;
         } else if (a == "--min-abundance") {
-            o.min_abundance = atol(next("--min-abundance"));
+            const char *v = next("--min-abundance");
+            o.min_abundance_auto = strcmp(v, "auto") == 0;
+            o.min_abundance = o.min_abundance_auto ? 1 : atol(v);
             if (o.min_abundance < 1 || o.min_abundance > (long)UINT32_MAX) {
-                fprintf(stderr, "kmc: --min-abundance must be in 1..%u\n", UINT32_MAX);
+                fprintf(stderr, "kmc: --min-abundance must be in 1..%u, or auto\n", UINT32_MAX);
+                return usage(stderr), 2;
+            }
+        } else if (a == "--spectrum") {
+            o.spectrum = atol(next("--spectrum"));
+            if (o.spectrum < 2 || o.spectrum > KMC_SPECTRUM_MAX_BINS) {
+                fprintf(stderr, "kmc: --spectrum must be in 2..%d\n", KMC_SPECTRUM_MAX_BINS);
                 return usage(stderr), 2;
             }
         } else if (a == "--accum-slots") {
@@ -360,10 +389,19 @@ int parse(int argc, char **argv, Options &o) {
         fprintf(stderr, "kmc: --min-abundance reads every file whole: not with --max-seqs above 0\n");
         return usage(stderr), 2;
     }
-    if ((o.accum_slots_set || o.batch_set) && o.min_abundance == 0) {
-        fprintf(stderr, "kmc: --accum-slots and --batch shape the pass of --min-abundance\n");
+    if (o.spectrum > 0 && !o.per_file) {
+        fprintf(stderr, "kmc: --spectrum needs --canonical --sketch S --sketch-direct --per-file\n");
         return usage(stderr), 2;
     }
+    if (o.spectrum > 0 && o.max_seqs_set && o.max_seqs > 0) {
+        fprintf(stderr, "kmc: --spectrum reads every file whole: not with --max-seqs above 0\n");
+        return usage(stderr), 2;
+    }
+    if ((o.accum_slots_set || o.batch_set) && o.min_abundance == 0 && o.spectrum == 0) {
+        fprintf(stderr, "kmc: --accum-slots and --batch shape the pass of --min-abundance or --spectrum\n");
+        return usage(stderr), 2;
+    }
+    if (o.spectrum > 0 && o.min_abundance == 0) o.min_abundance = 1;  // the accumulator's pass, every k-mer
     if (o.per_file && !o.max_seqs_set) o.max_seqs = 0;
     if (!o.query.empty() && !(o.canonical && o.sketch > 0 && o.sketch_direct)) {
         fprintf(stderr, "kmc: --query needs --canonical --sketch S --sketch-direct\n");
@@ -480,6 +518,7 @@ struct EventDestroy { void operator()(hipEvent_t e) const { (void)hipEventDestro
 struct FastaFree { void operator()(kmc_fasta *f) const { kmc_fasta_free(f); } };
 struct FastqClose { void operator()(kmc_fastq_reader *r) const { kmc_fastq_close(r); } };
 struct AccumFree { void operator()(kmc_sketch_accum *a) const { kmc_sketch_accum_free(a); } };
+struct FileClose { void operator()(FILE *f) const { (void)fclose(f); } };
 template <class T>
 using DevBuf = std::unique_ptr<T, DevFree>;
 using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
@@ -487,6 +526,7 @@ using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
 using Fasta = std::unique_ptr<kmc_fasta, FastaFree>;
 using FastqReader = std::unique_ptr<kmc_fastq_reader, FastqClose>;
 using Accum = std::unique_ptr<kmc_sketch_accum, AccumFree>;
+using File = std::unique_ptr<FILE, FileClose>;
 
 // max(count, 1) elements: an empty input still gets a pointer the entry points take
 template <class T>
@@ -664,15 +704,30 @@ uint32_t accum_log2_slots(const Options &o, uint32_t s) {
 // --per-file --min-abundance M: every file is one pass of the accumulator, reset in between;
 // a FASTQ file batch by batch, every add on st behind its batch's parse (the next batch's
 // writes are ordered behind that add), a FASTA file loaded whole and added in one call
-int accum_files(const Options &o, const std::vector<std::string> &files, const char *what, uint32_t s, uint64_t *d_sk,
-                uint32_t *d_sz, hipStream_t st) {
+// `inputs`: the files are the command's main inputs, whose spectra --spectrum writes.  With
+// --min-abundance auto every file's spectrum is read back before its finish, whose M it gives.
+int accum_files(const Options &o, const std::vector<std::string> &files, const char *what, bool inputs, uint32_t s,
+                uint64_t *d_sk, uint32_t *d_sz, hipStream_t st) {
     const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
     const uint32_t lg = accum_log2_slots(o, s);
     kmc_sketch_accum *acc = nullptr;
     KMCCHK(kmc_sketch_accum_create(s, o.k, flags, KMC_SKETCH_DEFAULT_SEED, lg, &acc));
     const Accum accum(acc);
-    DevBuf<uint64_t> d_stats;
+    DevBuf<uint64_t> d_stats, d_hist, d_sstats;
     HIPCHK(dev_alloc(d_stats, 4));
+    const bool written = inputs && o.spectrum > 0, taken = written || o.min_abundance_auto;
+    const uint32_t B = o.spectrum > 0 ? (uint32_t)o.spectrum : 256u;
+    std::vector<uint64_t> hist(B, 0);
+    File f_hist, f_sum;
+    if (taken) {
+        HIPCHK(dev_alloc(d_hist, B));
+        HIPCHK(dev_alloc(d_sstats, 4));
+    }
+    if (written) {
+        f_hist.reset(fopen((o.out_dir + "/spectrum.tsv").c_str(), "w"));
+        f_sum.reset(fopen((o.out_dir + "/spectrum_summary.tsv").c_str(), "w"));
+        if (!f_hist || !f_sum) return fprintf(stderr, "kmc: cannot write %s/spectrum.tsv\n", o.out_dir.c_str()), 1;
+    }
     for (size_t f = 0; f < files.size(); ++f) {
         const std::string &path = files[f];
         uint64_t records = 0, bytes = 0, batches = 0;
@@ -707,7 +762,18 @@ int accum_files(const Options &o, const std::vector<std::string> &files, const c
             bytes = r.bytes;
             batches = 1;
         }
-        KMCCHK(kmc_sketch_accum_finish(acc, (uint32_t)o.min_abundance, d_sk + f * s, d_sz + f, d_stats.get(), st));
+        uint32_t M = (uint32_t)o.min_abundance;
+        uint64_t sstats[4] = {0, 0, 0, 0};
+        kmc_spectrum_summary sum;
+        if (taken) {
+            KMCCHK(kmc_spectrum_from_accum(acc, B, d_hist.get(), d_sstats.get(), st));
+            HIPCHK(hipMemcpyAsync(hist.data(), d_hist.get(), (size_t)B * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(sstats, d_sstats.get(), sizeof sstats, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            KMCCHK(kmc_spectrum_summarize(hist.data(), B, sstats[1], &sum));
+            if (o.min_abundance_auto) M = sum.min_abundance;
+        }
+        KMCCHK(kmc_sketch_accum_finish(acc, M, d_sk + f * s, d_sz + f, d_stats.get(), st));
         uint32_t size = 0;
         uint64_t stats[4] = {0, 0, 0, 0};
         HIPCHK(hipMemcpyAsync(&size, d_sz + f, 4, hipMemcpyDeviceToHost, st));
@@ -715,23 +781,37 @@ int accum_files(const Options &o, const std::vector<std::string> &files, const c
         HIPCHK(hipStreamSynchronize(st));  // before the file's buffers go
         uint32_t j = 0;  // the library's rule (kmc.h) for the bytes added
         while (((bytes + ((1ull << j) - 1)) >> j) > (1ull << (lg - 2))) ++j;
-        if (!o.quiet)
-            printf("%s %zu: %s: %" PRIu64 " records, %" PRIu64 " batches, sketch size %u, j %u, complete %d\n", what, f,
+        if (!o.quiet) {
+            printf("%s %zu: %s: %" PRIu64 " records, %" PRIu64 " batches, sketch size %u, j %u, complete %d", what, f,
                    path.c_str(), records, batches, size, j, (int)stats[0]);
+            if (o.min_abundance_auto) printf(", min-abundance %u", M);
+            printf("\n");
+        }
+        if (written) {
+            for (uint32_t c = 1; c < B; ++c)
+                if (hist[c] > 0)
+                    fprintf(f_hist.get(), "%zu\t%u\t%" PRIu64 "\t%.6g\n", f, c, hist[c], sum.scale * (double)hist[c]);
+            fprintf(f_sum.get(),
+                    "%zu\t%s\t%" PRIu64 "\t%.6g\t%" PRIu64 "\t%" PRIu64 "\t%.6g\t%.6g\t%u\t%u\t%u\t%u\t%.6g\n", f,
+                    path.c_str(), sstats[1], sum.scale, sstats[2], sstats[3], sum.distinct, sum.total, sum.valley,
+                    sum.peak, M, sum.saturated, sum.genome_size);
+        }
         if (!stats[0])
             return fprintf(stderr,
-                           "kmc: %s: the table of 2^%u slots kept only %u of %u sketch values with abundance >= %ld "
+                           "kmc: %s: the table of 2^%u slots kept only %u of %u sketch values with abundance >= %u "
                            "(%" PRIu64 " k-mers tracked below hash %" PRIu64 "): raise --accum-slots\n",
-                           path.c_str(), lg, size, s, o.min_abundance, stats[2], stats[1]), 1;
+                           path.c_str(), lg, size, s, M, stats[2], stats[1]), 1;
     }
+    if (written && ((fclose(f_hist.release()) != 0) | (fclose(f_sum.release()) != 0)))
+        return fprintf(stderr, "kmc: cannot write %s/spectrum.tsv\n", o.out_dir.c_str()), 1;
     return 0;
 }
 
 // --per-file: every file is one group of all its records; file f's call writes row f
 // (rows of separate calls concatenate), so one file at a time is resident
-int sketch_files(const Options &o, const std::vector<std::string> &files, const char *what, uint32_t s, uint64_t *d_sk,
-                 uint32_t *d_sz, hipStream_t st) {
-    if (o.min_abundance > 0) return accum_files(o, files, what, s, d_sk, d_sz, st);
+int sketch_files(const Options &o, const std::vector<std::string> &files, const char *what, bool inputs, uint32_t s,
+                 uint64_t *d_sk, uint32_t *d_sz, hipStream_t st) {
+    if (o.min_abundance > 0) return accum_files(o, files, what, inputs, s, d_sk, d_sz, st);
     const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
     DevBuf<int64_t> d_grp;
     HIPCHK(dev_alloc(d_grp, 2));
@@ -764,7 +844,7 @@ int run_per_file(const Options &o, hipStream_t st) {
     std::vector<std::string> files{o.input};
     files.insert(files.end(), o.more_inputs.begin(), o.more_inputs.end());
     return sketch_step(o, [&](uint32_t s, uint64_t *d_sk, uint32_t *d_sz) {
-        return sketch_files(o, files, "File", s, d_sk, d_sz, st);
+        return sketch_files(o, files, "File", true, s, d_sk, d_sz, st);
     }, files.size(), st);
 }
 
@@ -783,7 +863,8 @@ int make_rows(const Options &o, const std::vector<std::string> &files, const cha
         rows.n = files.size();
         HIPCHK(dev_alloc(rows.sk, rows.n * s));
         HIPCHK(dev_alloc(rows.sz, rows.n));
-        return sketch_files(o, files, what, s, rows.sk.get(), rows.sz.get(), st);
+        // (announce: the command's inputs; the references of --screen get no spectrum)
+        return sketch_files(o, files, what, announce && o.screen.empty(), s, rows.sk.get(), rows.sz.get(), st);
     }
     Options of = o;
     of.input = files[0];

@@ -12,6 +12,7 @@
 //                        rec_off   {0, the length of finish's list}: the offsets of the
 //                                  one record kmc_sketch_from_counts selects from
 //                        qual      list entries with count >= min_count
+//                        spec      the spectrum's scratch: {entries, sum of counts}
 //   keys    uint64[C] x 2   open addressing, linear probing, the slot of a key is the
 //   counts  uint32[C] x 2   low log2_slots bits of its HASH; UINT64_MAX: empty (a
 //                           canonical key has at most 62 bits)
@@ -56,6 +57,14 @@
 // finish writes the header's rec_off and qual, the inactive table and the select
 // workspace only: the accumulator is as it was.
 //
+//   spectrum  kmc_spectrum_from_accum: the histogram of the counts of the entries
+//           below the same `limit`, a uniform sample of the set's distinct k-mers with
+//           exact multiplicities.  One pass over the active table: a workgroup bins
+//           its slots in a private uint32 histogram in LDS (it sees C / 4096 <= 2^18
+//           slots at most), then adds its non-zero bins to `hist` with 64-bit atomics
+//           and its entry count and count sum to the header's `spec` words, once.  It
+//           writes hist, stats and `spec` only.
+//
 // The device code trusts the host arguments only: every slot index is masked, every
 // chain is bounded by kChain <= C, the list's cursor is checked against C.
 //
@@ -89,6 +98,7 @@ struct Header {
     uint32_t tracked[2];
     unsigned long long rec_off[2];
     unsigned long long qual;
+    unsigned long long spec[2];
 };
 static_assert(sizeof(Header) <= kHeaderBytes, "the header has its 256 bytes");
 
@@ -274,7 +284,8 @@ struct FArgs {
 };
 
 // the exclusive bound of the hashes whose counts are exact; *all: nothing bounds them
-__device__ __forceinline__ unsigned long long limit_of(const FArgs &a, bool *all) {
+template <class Args>
+__device__ __forceinline__ unsigned long long limit_of(const Args &a, bool *all) {
     const unsigned long long lost = a.hd->lost;
     *all = a.j == 0 && lost == kFill;
     if (a.j == 0) return lost;
@@ -307,6 +318,66 @@ __global__ void accum_stats_kernel(FArgs a) {
     a.stats[1] = limit;
     a.stats[2] = a.hd->rec_off[1];
     a.stats[3] = a.hd->qual;
+}
+
+// ---------------------------------------------------------------------------
+// spectrum
+// ---------------------------------------------------------------------------
+struct SArgs {
+    const unsigned long long *keys;  // the active table, C slots
+    const uint32_t *counts;
+    uint64_t C, seed, maxh;
+    uint32_t j, bins;  // bins in 2 .. KMC_SPECTRUM_MAX_BINS
+    Header *hd;
+    unsigned long long *hist;  // [bins], cleared
+    uint64_t *stats;
+};
+
+__global__ __launch_bounds__(kSlotBlock) void accum_spectrum_kernel(SArgs a) {
+    extern __shared__ uint32_t s_hist[];  // [bins]
+    __shared__ unsigned long long s_sum[2];
+    const uint32_t tid = threadIdx.x, top = a.bins - 1u;
+    for (uint32_t b = tid; b < a.bins; b += kSlotBlock) s_hist[b] = 0u;
+    if (tid < 2) s_sum[tid] = 0ull;
+    __syncthreads();
+    bool all;
+    const unsigned long long limit = limit_of(a, &all);
+    unsigned long long n = 0ull, sum = 0ull;
+    for (uint64_t i = (uint64_t)blockIdx.x * kSlotBlock + tid; i < a.C; i += (uint64_t)gridDim.x * kSlotBlock) {
+        const unsigned long long key = a.keys[i];
+        if (key == kFill) continue;
+        if (!all && sketch_hash(key, a.seed) >= limit) continue;
+        const uint32_t cnt = a.counts[i];
+        atomicAdd(&s_hist[cnt < top ? cnt : top], 1u);
+        ++n;
+        sum += cnt;
+    }
+    for (int off = warpSize / 2; off > 0; off >>= 1) {
+        n += __shfl_down(n, off);
+        sum += __shfl_down(sum, off);
+    }
+    if ((tid & (warpSize - 1)) == 0 && n) {
+        atomicAdd(&s_sum[0], n);
+        atomicAdd(&s_sum[1], sum);
+    }
+    __syncthreads();
+    for (uint32_t b = tid; b < a.bins; b += kSlotBlock) {
+        const uint32_t v = s_hist[b];
+        if (v) atomicAdd(a.hist + b, (unsigned long long)v);
+    }
+    if (tid == 0 && s_sum[0]) {
+        atomicAdd(&a.hd->spec[0], s_sum[0]);
+        atomicAdd(&a.hd->spec[1], s_sum[1]);
+    }
+}
+
+__global__ void accum_spectrum_stats_kernel(SArgs a) {
+    bool all;
+    const unsigned long long limit = limit_of(a, &all);
+    a.stats[0] = all ? 1u : 0u;
+    a.stats[1] = limit;
+    a.stats[2] = a.hd->spec[0];
+    a.stats[3] = a.hd->spec[1];
 }
 
 inline unsigned slot_grid(uint64_t C) {
@@ -484,6 +555,29 @@ extern "C" int kmc_sketch_accum_finish(kmc_sketch_accum *a, uint32_t min_count, 
                                        min_count, sketch_row, sketch_size_out, a->L.select, a->L.select_bytes, stream))
         return e;
     if (stats) hipLaunchKernelGGL(accum_stats_kernel, dim3(1), dim3(1), 0, stream, f);
+    return (int)hipGetLastError();
+}
+
+extern "C" int kmc_spectrum_from_accum(kmc_sketch_accum *a, uint32_t num_bins, uint64_t *hist, uint64_t *stats,
+                                       hipStream_t stream) {
+    if (!a || !hist || num_bins < 2 || num_bins > KMC_SPECTRUM_MAX_BINS) return KMC_ERR_INVALID_ARG;
+    const uint64_t C = 1ull << a->lg;
+    SArgs g;
+    g.keys = a->L.keys[a->active];
+    g.counts = a->L.counts[a->active];
+    g.C = C;
+    g.seed = a->seed;
+    g.maxh = max_hash(a->j);
+    g.j = a->j;
+    g.bins = num_bins;
+    g.hd = a->L.hd;
+    g.hist = reinterpret_cast<unsigned long long *>(hist);
+    g.stats = stats;
+    if (hipError_t he = hipMemsetAsync(hist, 0, (size_t)num_bins * 8, stream)) return (int)he;
+    if (hipError_t he = hipMemsetAsync(a->L.hd->spec, 0, sizeof(a->L.hd->spec), stream)) return (int)he;
+    hipLaunchKernelGGL(accum_spectrum_kernel, dim3(slot_grid(C)), dim3(kSlotBlock), (size_t)num_bins * 4, stream, g);
+    if (hipError_t he = hipGetLastError()) return (int)he;
+    if (stats) hipLaunchKernelGGL(accum_spectrum_stats_kernel, dim3(1), dim3(1), 0, stream, g);
     return (int)hipGetLastError();
 }
 

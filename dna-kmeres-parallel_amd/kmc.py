@@ -22,6 +22,7 @@ caller orders its own use of the inputs and results against `s`.  The wrappers
 that return tensors also take `out=`: the caller's own output tensors, in the
 order they are returned.
 """
+import collections
 import ctypes
 import os
 import re
@@ -66,6 +67,15 @@ class DenseArgs(ctypes.Structure):
         ("sum", _P), ("sum_ld", _U64), ("invalid", _P),
         ("read_lo", _U64), ("read_hi", _U64), ("win_lo", _U64), ("win_hi", _U64),
         ("workspace", _P), ("workspace_bytes", ctypes.c_size_t), ("status", _P),
+    ]
+
+
+class SpectrumSummary(ctypes.Structure):
+    _fields_ = [
+        ("scale", ctypes.c_double), ("sampled_distinct", _U64), ("sampled_total", _U64),
+        ("distinct", ctypes.c_double), ("total", ctypes.c_double),
+        ("valley", ctypes.c_uint32), ("peak", ctypes.c_uint32), ("min_abundance", ctypes.c_uint32),
+        ("saturated", ctypes.c_uint32), ("genome_size", ctypes.c_double),
     ]
 
 
@@ -244,6 +254,8 @@ def _load(path):
     L.kmc_sketch_accum_reset.argtypes = [_P, _P]
     L.kmc_sketch_accum_free.argtypes = [_P]
     L.kmc_sketch_accum_free.restype = None
+    L.kmc_spectrum_from_accum.argtypes = [_P, ctypes.c_uint32, _P, _P, _P]
+    L.kmc_spectrum_summarize.argtypes = [_P, ctypes.c_uint32, _U64, ctypes.POINTER(SpectrumSummary)]
     L.minKmeres2_hip.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.kmc_count_canonical_hash.argtypes = [_P, _P, _U64, ctypes.c_int, ctypes.c_uint, _P, _P, _U64, _P,
                                            ctypes.POINTER(_U64), _P]
@@ -750,7 +762,8 @@ class SketchAccum:
     of records (data, indices: as sketch_from_sequences); finish(min_count) returns
     (row int64 [s]: uint64 hashes ascending, then all-ones fill; size int32 [1];
     stats int64 [4]: complete, limit, tracked, qualifying, or None) and leaves the
-    accumulator as it is; reset() empties it.  `log2_slots`: the table's size, 0 for
+    accumulator as it is; spectrum(num_bins) gives the abundance spectrum of what was
+    added (kmc_spectrum_from_accum), and leaves it as it is too; reset() empties it.  `log2_slots`: the table's size, 0 for
     the default (kmc.h).  The handle belongs to the library it was created in.
 
         with kmc.SketchAccum(1000, 21) as acc:
@@ -796,6 +809,25 @@ class SketchAccum:
                                                  _stream(stream)), "kmc_sketch_accum_finish")
         return row, size, st
 
+    def spectrum(self, num_bins, stats=True, out=None, stream=None):
+        """kmc_spectrum_from_accum: (hist int64 [num_bins]: uint64 numbers of tracked
+        k-mers seen c times, the last bin saturating; stats int64 [4]: exact, limit,
+        entries, windows, or None) of everything added so far, for the k-mers below the
+        limit finish() reports.  It leaves the accumulator as it is.  `stats`: True for
+        a new tensor, or the caller's own int64 tensor [4]; `out`: the caller's own hist."""
+        import torch
+        h = self._handle()
+        with _on(stream):
+            dv = torch.device("cuda", torch.cuda.current_device())
+            hist = out if out is not None else torch.empty(max(int(num_bins), 0), dtype=torch.int64, device=dv)
+            if isinstance(stats, torch.Tensor):
+                st = stats
+            else:
+                st = torch.empty(4, dtype=torch.int64, device=dv) if stats else None
+        _check(self._lib.kmc_spectrum_from_accum(h, int(num_bins), _dptr(hist), _dptr(st), _stream(stream)),
+               "kmc_spectrum_from_accum")
+        return hist, st
+
     def reset(self, stream=None):
         _check(self._lib.kmc_sketch_accum_reset(self._handle(), _stream(stream)), "kmc_sketch_accum_reset")
 
@@ -813,6 +845,24 @@ class SketchAccum:
 
     def __del__(self):
         self.close()
+
+
+SPECTRUM_MAX_BINS = 8192
+SpectrumResult = collections.namedtuple("SpectrumResult", [f[0] for f in SpectrumSummary._fields_])
+
+
+def spectrum_summarize(hist, limit):
+    """kmc_spectrum_summarize of a spectrum (SketchAccum.spectrum's hist, a tensor or a
+    host array of uint64 bit patterns) and its limit (stats[1]): a namedtuple of the
+    fields of kmc_spectrum_summary (kmc.h).  Host only."""
+    if hasattr(hist, "cpu"):
+        hist = hist.cpu().numpy()
+    h = np.ascontiguousarray(hist)
+    h = h.view(np.uint64) if h.dtype == np.int64 else h.astype(np.uint64)
+    out = SpectrumSummary()
+    _check(lib().kmc_spectrum_summarize(h.ctypes.data_as(_P), int(h.size), int(limit) & _M64, ctypes.byref(out)),
+           "kmc_spectrum_summarize")
+    return SpectrumResult(*[getattr(out, f[0]) for f in SpectrumSummary._fields_])
 
 
 def min_kmeres2(sums, mins, num_seqs, current_seq, indexes, stream=None):

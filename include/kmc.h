@@ -761,6 +761,63 @@ KMC_API int kmc_sketch_accum_reset(kmc_sketch_accum *a, hipStream_t stream);
 KMC_API void kmc_sketch_accum_free(kmc_sketch_accum *a);
 
 /* ------------------------------------------------------------------------ */
+/* The abundance spectrum of everything added to an accumulator: how many distinct
+ * k-mers were seen once, twice, ..., c times (jellyfish histo, kmc_tools histogram,
+ * ntCard).  With limit and `all` exactly those of kmc_sketch_accum_finish (limit =
+ * min(2^(64 - j), lost); all: j = 0 and nothing lost), every key with a hash below limit
+ * was tracked from its first window on, so its count is exact; the hash is a bijection
+ * of the key, so those keys are a uniform sample of the set's distinct k-mers at rate
+ * limit / 2^64.  Their histogram times 2^64 / limit is an unbiased estimate of every bin
+ * of the true spectrum, and with `all` it is the exact spectrum.
+ *
+ * kmc_spectrum_from_accum: an entry of the active table takes part iff it holds a key
+ * and (all or its hash < limit).
+ *   num_bins  2 .. KMC_SPECTRUM_MAX_BINS
+ *   hist      device uint64[num_bins], overwritten: a participating entry with count c
+ *             adds 1 to hist[min(c, num_bins - 1)]; the last bin saturates, and hist[0]
+ *             is 0 unless a count wrapped at 2^32
+ *   stats     device uint64[4], may be NULL:
+ *             [0] exact    1 iff all
+ *             [1] limit    the exclusive bound; UINT64_MAX when unbounded
+ *             [2] entries  participating entries: finish's stats[2], the sum of hist
+ *             [3] windows  the sum of their counts in 64 bits (the windows below limit),
+ *                          not truncated by the last bin
+ * It writes hist, stats and two scratch words of the handle only, neither the tables
+ * nor what finish writes: add, spectrum, add, spectrum, finish, spectrum is a valid
+ * sequence, and a spectrum after a finish equals the one before it.  Asynchronous on
+ * `stream`, no host read-back; the launches depend on the table's size, num_bins and j
+ * only; calls on one accumulator are ordered by the caller.  KMC_ERR_INVALID_ARG, judged
+ * before any device is touched, for a null handle, a null hist, num_bins out of range.
+ *
+ * kmc_spectrum_summarize: host only, no device.  hist is a host copy of the histogram,
+ * limit its stats[1]; B = num_bins.  Every double is one IEEE operation on the operands
+ * stated beside its field.  The last bin is a tail and not a count: it is no rise and no
+ * peak.  The valley is where the k-mers of sequencing errors end: the first bin that is
+ * not above a NON-EMPTY next bin (the empty bins past the last count of an assembly's
+ * spectrum are no valley: such a file gets min_abundance 1).  KMC_ERR_INVALID_ARG for a
+ * null pointer, num_bins outside 2..KMC_SPECTRUM_MAX_BINS, limit == 0. */
+#define KMC_SPECTRUM_MAX_BINS 8192
+typedef struct kmc_spectrum_summary {
+    double   scale;            /* limit == UINT64_MAX ? 1.0 : ldexp(1.0, 64) / (double)limit */
+    uint64_t sampled_distinct; /* sum over c >= 1 of hist[c] */
+    uint64_t sampled_total;    /* sum over c >= 1 of c * hist[c] (mod 2^64; the last bin at c = B - 1) */
+    double   distinct;         /* scale * (double)sampled_distinct */
+    double   total;            /* scale * (double)sampled_total */
+    uint32_t valley;           /* smallest c in 1 .. B - 3 with hist[c] <= hist[c + 1] and hist[c + 1] > 0;
+                                  0: none */
+    uint32_t peak;             /* valley > 0: the c in valley + 1 .. B - 2 with the largest hist[c], the
+                                  smallest such c on ties; else 0 */
+    uint32_t min_abundance;    /* valley > 0 ? valley : 1 */
+    uint32_t saturated;        /* hist[B - 1] > 0 */
+    double   genome_size;      /* peak > 0 ? (scale * (double)(sum over c >= valley of c * hist[c], mod 2^64))
+                                  / (double)peak : 0.0 */
+} kmc_spectrum_summary;
+KMC_API int kmc_spectrum_from_accum(kmc_sketch_accum *a, uint32_t num_bins, uint64_t *hist, uint64_t *stats,
+                                    hipStream_t stream);
+KMC_API int kmc_spectrum_summarize(const uint64_t *hist, uint32_t num_bins, uint64_t limit,
+                                   kmc_spectrum_summary *out);
+
+/* ------------------------------------------------------------------------ */
 /* Tracing (the reference times step 1 with cudaEvents, main.cu:262-300): when set,
  * every following dense count call on this host thread records `before` right
  * before its histogram kernel and `after` right after it, on the call's stream,

@@ -18,7 +18,9 @@ plus the set upkeep (profiles/pr_sketch_screen.jsonl).
 With --accum: kmc_sketch_accum_add over the same mixture, as one call and as 16 calls
 (j rises and purges happen), and kmc_sketch_accum_finish, beside kmc_sketch_screen_count
 against the 1000-reference index and kmc_sketch_from_sequences_grouped with one group:
-the parent commit's code on the same walk (profiles/pr_sketch_accum.jsonl).
+the parent commit's code on the same walk (profiles/pr_sketch_accum.jsonl); and
+kmc_spectrum_from_accum of the same table with 256 and 8192 bins, beside _finish
+(--out profiles/pr_spectrum.jsonl).
 With --cluster: kmc_sketch_cluster beside kmc_sketch_distances on the same rows, unrelated
 rows and 64-member clusters of near-identical rows (profiles/pr_sketch_cluster.jsonl).
 
@@ -444,6 +446,9 @@ def accum_main(args, dev):
         "reset_and_add_one_call": timed(whole, args.runs),
         "reset_and_add_16_calls": timed(in_calls, args.runs),
         "kmc_sketch_accum_finish": timed(lambda: acc.finish(2), args.runs),
+        # the spectrum of the same table (the state the 16 calls left), 256 and 8192 bins
+        "kmc_spectrum_from_accum_256": timed(lambda: acc.spectrum(256), args.runs),
+        "kmc_spectrum_from_accum_8192": timed(lambda: acc.spectrum(8192), args.runs),
         "kmc_sketch_screen_count": timed(lambda: kmc.sketch_screen_count(index, mix, midx, k), args.runs),
         "kmc_sketch_from_sequences_grouped": timed(
             lambda: kmc.sketch_from_sequences_grouped(mix, midx, one_group, k, s), args.runs),
