@@ -23,7 +23,7 @@
 // sketches are searched in, kmc_sketch_nearest -> query_results.tsv, or with --top 0
 // kmc_sketch_distances_rect -> query_distances.csv; --screen FILE: the input files are references
 // looked for among all k-mers of FILE, a read set or metagenome, kmc_sketch_screen_* ->
-// screen_results.tsv).  Inputs may be FASTQ (--format, or a .fq / .fastq name):
+// screen_results.tsv; --winner-takes-all: kmc_sketch_screen_winners' lines instead of _results').  Inputs may be FASTQ (--format, or a .fq / .fastq name):
 // kmc_fastq_load_device, and a --screen FILE in FASTQ is streamed batch by batch
 // (kmc_fastq_open / _next / _close), so its size is not bounded by device memory.
 // --per-file --min-abundance M: every file is one pass of the abundance accumulator
@@ -81,6 +81,7 @@ struct Options {
     std::vector<std::string> more_inputs;  // the input files after the first
     int format = 0;             // --format: 0 auto (by file name), 1 fasta, 2 fastq
     uint64_t screen_batch = 0;  // --screen-batch BYTES (0: the reader's default, 256 MiB)
+    bool winner_takes_all = false;  // --winner-takes-all: with --screen, kmc_sketch_screen_winners' lines
     long min_abundance = 0;     // --min-abundance M: --per-file sketches of the k-mers seen M times (0: not given)
     long accum_slots = 0;       // --accum-slots LOG2 (0: the library's default)
     uint64_t batch = 0;         // --batch BYTES: the reader's batches of a --min-abundance FASTQ file
@@ -108,6 +109,7 @@ void usage(FILE *f) {
             "       kmc --canonical --sketch S --sketch-direct --query q.fasta [--top T] [options] <refs.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --screen reads.fasta [--screen ...] [options] <refs.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --screen reads.fastq [--screen-batch BYTES] [options] <refs.fasta>\n"
+            "       kmc --canonical --sketch S --sketch-direct --screen reads.fasta --winner-takes-all [options] <refs.fasta>\n"
             "       kmc --canonical --sketch S --sketch-direct --per-file --min-abundance M [--batch BYTES] [options] <a.fastq> ...\n"
             "       kmc --canonical --sketch S --sketch-direct --per-file --spectrum B [--min-abundance auto] [options] <a.fastq> ...\n"
             "       kmc --canonical --sketch S [--sketch-direct] [--per-file] --cluster D [options] <input.fasta> ...\n"
@@ -172,6 +174,13 @@ void usage(FILE *f) {
             "                    (shared: sketch values found; median: their median multiplicity; identity:\n"
             "                    (shared/size)^(1/k)), and <TAB>path with --per-file; sketch_results.csv is\n"
             "                    not written\n"
+            "  --winner-takes-all with --screen only, for a redundant reference collection (Mash's screen -w):\n"
+            "                    every found sketch value is credited to one reference only, the one with the\n"
+            "                    largest shared/size that holds it, the earlier one on a tie\n"
+            "                    (kmc_sketch_screen_winners).  The lines of screen_results.tsv are then\n"
+            "                    index<TAB>won<TAB>size<TAB>median_won<TAB>identity_won<TAB>shared_all: the values\n"
+            "                    won, their median multiplicity, (won/size)^(1/k), and in the extra column\n"
+            "                    shared_all the `shared` of the plain screen; <TAB>path last with --per-file\n"
             "  --format F        auto (default), fasta or fastq, for every file of the command.  auto: a file\n"
             "                    whose name ends in .fq or .fastq (any case) is FASTQ, every other FASTA.\n"
             "                    FASTQ is strict four-line FASTQ (kmc_fastq_load_device: records are the\n"
@@ -285,6 +294,8 @@ int parse(int argc, char **argv, Options &o) {
             o.query = next("--query");
         } else if (a == "--screen") {
             o.screen.push_back(next("--screen"));
+        } else if (a == "--winner-takes-all") {
+            o.winner_takes_all = true;
         } else if (a == "--top") {
             o.top = atol(next("--top"));
             o.top_set = true;
@@ -413,6 +424,10 @@ int parse(int argc, char **argv, Options &o) {
     }
     if (!o.screen.empty() && !o.query.empty()) {
         fprintf(stderr, "kmc: --screen and --query exclude each other\n");
+        return usage(stderr), 2;
+    }
+    if (o.winner_takes_all && o.screen.empty()) {
+        fprintf(stderr, "kmc: --winner-takes-all credits the values of --screen\n");
         return usage(stderr), 2;
     }
     if ((o.top_set || o.min_shared_set) && o.query.empty()) {
@@ -954,9 +969,11 @@ int run_screen(const Options &o, hipStream_t st) {
     const size_t index_bytes = kmc_sketch_screen_index_size(n, s);
     if (index_bytes == 0) return fprintf(stderr, "kmc: too many reference sketch values for one screen index\n"), 1;
     DevBuf<char> d_index;
-    DevBuf<uint32_t> d_sh, d_med;
+    DevBuf<uint32_t> d_sh, d_med, d_all;
     DevBuf<float> d_id;
     Event b0 = make_event(), b1 = make_event(), c0 = make_event(), c1 = make_event(), r1 = make_event();
+    const bool wta = o.winner_takes_all;
+    if (wta) HIPCHK(dev_alloc(d_all, n));
     HIPCHK(dev_alloc(d_index, index_bytes));
     HIPCHK(dev_alloc(d_sh, n));
     HIPCHK(dev_alloc(d_med, n));
@@ -1016,24 +1033,30 @@ int run_screen(const Options &o, hipStream_t st) {
                    ms_between(c0.get(), c1.get()));
     }
     HIPCHK(hipEventRecord(c1.get(), st));
-    KMCCHK(kmc_sketch_screen_results(d_index.get(), index_bytes, R.sk.get(), R.sz.get(), n, s, o.k, d_sh.get(),
-                                     d_med.get(), d_id.get(), st));
+    if (wta)  // (the library's own workspace)
+        KMCCHK(kmc_sketch_screen_winners(d_index.get(), index_bytes, R.sk.get(), R.sz.get(), n, s, o.k, d_sh.get(),
+                                         d_med.get(), d_id.get(), d_all.get(), nullptr, 0, st));
+    else
+        KMCCHK(kmc_sketch_screen_results(d_index.get(), index_bytes, R.sk.get(), R.sz.get(), n, s, o.k, d_sh.get(),
+                                         d_med.get(), d_id.get(), st));
     HIPCHK(hipEventRecord(r1.get(), st));
     HIPCHK(hipEventSynchronize(r1.get()));
-    if (!o.quiet) printf("Screen results: %.3f ms\n", ms_between(c1.get(), r1.get()));
-    std::vector<uint32_t> sh(n), med(n), sz(n);
+    if (!o.quiet) printf(wta ? "Screen winners: %.3f ms\n" : "Screen results: %.3f ms\n", ms_between(c1.get(), r1.get()));
+    std::vector<uint32_t> sh(n), med(n), sz(n), all(wta ? n : 0);
     std::vector<float> ident(n);
     if (n > 0) {
         HIPCHK(hipMemcpy(sh.data(), d_sh.get(), n * 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(med.data(), d_med.get(), n * 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(sz.data(), R.sz.get(), n * 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(ident.data(), d_id.get(), n * 4, hipMemcpyDeviceToHost));
+        if (wta) HIPCHK(hipMemcpy(all.data(), d_all.get(), n * 4, hipMemcpyDeviceToHost));
     }
     const std::string path = o.out_dir + "/screen_results.tsv";
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return fprintf(stderr, "kmc: cannot write %s\n", path.c_str()), 1;
     for (uint64_t r = 0; r < n; ++r) {
         fprintf(f, "%" PRIu64 "\t%u\t%u\t%u\t%f", r, sh[r], std::min(sz[r], s), med[r], ident[r]);
+        if (wta) fprintf(f, "\t%u", all[r]);
         if (o.per_file) fprintf(f, "\t%s", files[r].c_str());
         fputc('\n', f);
     }

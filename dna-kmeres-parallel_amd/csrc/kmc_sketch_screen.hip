@@ -36,10 +36,20 @@
 //           multiplicities (as 64-bit words, absent values as UINT64_MAX) are sorted
 //           in LDS (bitonic_sort of kmc_sketch_pair.h) and the lower median is taken.
 //
+//   winners the results with every found value credited to one row only, the best
+//           that holds it (include/kmc.h has the rule): the first pass is results
+//           itself (all[r], no median), claim raises the owner word of every found
+//           value's slot to its best holder with a 64-bit atomic maximum, recount is
+//           results again, taking a value only where the row owns it.  The owner
+//           words are the call's workspace (one per slot the blob can hold, one more
+//           for UINT64_MAX, and all[]); the index is only read.
+//
 // The device code trusts nothing in the blob: count and results read log2cap, check
 // that the layout of that many slots fits index_bytes and return otherwise; every
 // slot index is masked to the table and a probe chain is left after C steps, so a
 // blob that was never built gives an unspecified result and no stray access or hang.
+// claim and recount also check the slot count against the owner words they were given
+// and return without touching anything when it does not fit.
 //
 // Constants, shipped / under -DKMC_DIAG_HOOKS (no new symbol):
 //   kBlock, kMinChunks, kWgPerCu   the sketcher's (kmc_sketch_walk.h): 64-thread
@@ -271,6 +281,10 @@ struct RArgs {
     int k;
     uint32_t *shared, *median;
     float *identity;
+    // winners only (claim and the recount): the owner word of every slot, then UINT64_MAX's
+    unsigned long long *owner;
+    uint64_t owner_slots;
+    const uint32_t *all;
 };
 
 __device__ __forceinline__ float containment_identity(uint32_t shared, uint32_t size, int k) {
@@ -280,11 +294,70 @@ __device__ __forceinline__ float containment_identity(uint32_t shared, uint32_t 
     return (float)pow((double)shared / (double)size, 1.0 / (double)k);
 }
 
-template <int CAP>
+// The owner word of a found value: the best row that holds it, as one number a 64-bit
+// atomic maximum can raise.  Row r with all of its size values found (all >= 1) offers
+//   q = floor(all * 2^32 / size)   above   2^30 - 1 - r   (30 bits; r < 2^30)
+// and the largest offer is the rule's first row (include/kmc.h):
+//   - all <= size <= 2^14, so 2^18 <= q <= 2^32: 33 bits, 63 with the low field, and
+//     never 0, which is the cleared word: nobody claimed the value
+//   - two fractions all/size that differ have denominators of at most 2^14 each, so they
+//     differ by at least 2^-28, times 2^32 by at least 16: their floors differ and keep
+//     the order of all[a] * size[b] against all[b] * size[a]
+//   - equal fractions are the same rational and give the same q; the low field then
+//     prefers the smaller r
+// so the word depends on the row alone and the maximum on the set of holders, not on
+// the order the device meets them in.
+constexpr uint32_t kRowBits = 30;
+constexpr unsigned long long kRowMask = (1ull << kRowBits) - 1;
+static_assert(KMC_SCREEN_MAX_VALUES <= (1ull << kRowBits), "a row index fits the owner word's low field");
+static_assert(KMC_SKETCH_MAX_SIZE <= (1 << 14), "the fractions of two rows differ by 2^-28 at least");
+
+__device__ __forceinline__ unsigned long long owner_word(uint32_t all, uint32_t size, int64_t r) {
+    return ((((unsigned long long)all << 32) / size) << kRowBits) | (kRowMask - (unsigned long long)r);
+}
+
+__device__ __forceinline__ bool owned_by(unsigned long long word, int64_t r) {
+    return word != 0ull && (word & kRowMask) == kRowMask - (unsigned long long)r;
+}
+
+// The owner word of the value whose multiplicity is kept at `at` (find): its slot's, or
+// the one after the last slot's for UINT64_MAX.
+__device__ __forceinline__ unsigned long long *owner_of(const Table &T, const RArgs &a, const uint32_t *at) {
+    return a.owner + (at == &T.hd->ff_mult ? a.owner_slots : (uint64_t)(at - T.mult));
+}
+
+// claim: one workgroup per row, a thread per value (coalesced over the row); every found
+// value's owner word is raised to the row's offer with a vector atomic of agent scope
+// (no return value).  a.all is the first pass's shared[]; a row with none found offers
+// nothing.
+__global__ __launch_bounds__(kBlock) void screen_claim_kernel(RArgs a) {
+    const Table T = open_table(a.index, a.index_bytes);
+    if (!T.ok || T.cap > a.owner_slots) return;
+    const bool has_ff = T.hd->has_ff != 0u;
+    const int tid = threadIdx.x, s = (int)a.s;
+    for (int64_t r = blockIdx.x; r < a.n; r += gridDim.x) {
+        const int n = row_size(a.sizes, r, s);
+        const uint32_t all = a.all[r];
+        if (all == 0u || all > (uint32_t)n) continue;  // (uniform; all <= n unless the blob changed under the call)
+        const unsigned long long word = owner_word(all, (uint32_t)n, r);
+        const uint64_t *row = a.rows + r * (int64_t)s;
+        for (int i = tid; i < n; i += kBlock) {
+            const uint32_t *at = find(T, row[i], has_ff);
+            if (at && *at) __hip_atomic_fetch_max(owner_of(T, a, at), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// results, and with WON the recount of winners: a found value counts only where its
+// owner word names the row.
+template <int CAP, bool WON>
 __global__ __launch_bounds__(kBlock) void screen_results_kernel(RArgs a) {
     __shared__ uint64_t buf[CAP];  // the multiplicities of the row's values, UINT64_MAX: absent
     __shared__ uint32_t s_shared;
     const Table T = open_table(a.index, a.index_bytes);
+    if constexpr (WON) {
+        if (!T.ok || T.cap > a.owner_slots) return;
+    }
     const bool has_ff = T.ok && T.hd->has_ff != 0u;
     const int tid = threadIdx.x, s = (int)a.s;
     for (int64_t r = blockIdx.x; r < a.n; r += gridDim.x) {
@@ -298,7 +371,10 @@ __global__ __launch_bounds__(kBlock) void screen_results_kernel(RArgs a) {
             uint64_t m = kFill;
             if (i < n && T.ok) {
                 const uint32_t *at = find(T, row[i], has_ff);
-                const uint32_t c = at ? *at : 0u;
+                uint32_t c = at ? *at : 0u;
+                if constexpr (WON) {
+                    if (c && !owned_by(*owner_of(T, a, at), r)) c = 0u;
+                }
                 if (c) {
                     m = c;
                     ++found;
@@ -332,6 +408,50 @@ inline int index_check(const void *index, size_t index_bytes, size_t need) {
     if (reinterpret_cast<uintptr_t>(index) & 255u) return KMC_ERR_ALIGNMENT;
     return KMC_OK;
 }
+
+// what results and winners ask of their arguments, in this order
+inline int results_check(const void *index, size_t index_bytes, const uint64_t *r_sketches, const uint32_t *r_sizes,
+                         uint64_t num_refs, uint32_t sketch_size, int k, const uint32_t *counts, bool *nothing) {
+    *nothing = false;
+    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
+    if (!screen_rows_ok(num_refs, sketch_size)) return KMC_ERR_INVALID_ARG;
+    if (num_refs == 0) return *nothing = true, KMC_OK;
+    if (!r_sketches || !r_sizes || !counts) return KMC_ERR_INVALID_ARG;
+    return index_check(index, index_bytes, layout_bytes(kMinSlots));
+}
+
+inline void launch_results(const RArgs &a, bool won, hipStream_t stream) {
+    const dim3 g((unsigned)(a.n < kMaxGridX ? a.n : kMaxGridX)), b(kBlock);
+    for_cap(a.s, [&](auto cap) {
+        if (won) hipLaunchKernelGGL((screen_results_kernel<decltype(cap)::value, true>), g, b, 0, stream, a);
+        else hipLaunchKernelGGL((screen_results_kernel<decltype(cap)::value, false>), g, b, 0, stream, a);
+    });
+}
+
+// the slots of the largest table whose layout fits index_bytes (>= the smallest layout)
+inline uint64_t slots_within(size_t index_bytes) {
+    uint32_t lg = 3;
+    while (lg < kMaxLog2Cap && layout_bytes(1ull << (lg + 1)) <= index_bytes) ++lg;
+    return 1ull << lg;
+}
+
+// the workspace of winners: the one layout behind the size query (base = null) and the bind
+struct WLayout {
+    unsigned long long *owner;  // [slots + 1]: the last is UINT64_MAX's
+    uint32_t *all;
+    size_t bytes;
+};
+
+inline WLayout winners_layout(void *base, uint64_t slots, uint64_t num_refs) {
+    Carver c(base);
+    WLayout L;
+    L.owner = c.take<unsigned long long>((size_t)slots + 1);
+    L.all = c.take<uint32_t>((size_t)num_refs);
+    L.bytes = c.total();
+    return L;
+}
+
+DeviceCache w_ws;  // library-owned workspace of winners
 
 }  // namespace
 }  // namespace kmc
@@ -406,12 +526,10 @@ extern "C" int kmc_sketch_screen_results(const void *index, size_t index_bytes, 
                                          const uint32_t *r_sizes, uint64_t num_refs, uint32_t sketch_size, int k,
                                          uint32_t *shared, uint32_t *median_mult, float *identity,
                                          hipStream_t stream) {
-    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
-    if (!screen_rows_ok(num_refs, sketch_size)) return KMC_ERR_INVALID_ARG;
-    if (num_refs == 0) return KMC_OK;
-    if (!r_sketches || !r_sizes || !shared) return KMC_ERR_INVALID_ARG;
-    if (int e = index_check(index, index_bytes, layout_bytes(kMinSlots))) return e;
-    RArgs a;
+    bool nothing;
+    if (int e = results_check(index, index_bytes, r_sketches, r_sizes, num_refs, sketch_size, k, shared, &nothing)) return e;
+    if (nothing) return KMC_OK;
+    RArgs a{};
     a.index = const_cast<void *>(index);
     a.index_bytes = index_bytes;
     a.rows = r_sketches;
@@ -422,9 +540,49 @@ extern "C" int kmc_sketch_screen_results(const void *index, size_t index_bytes, 
     a.shared = shared;
     a.median = median_mult;
     a.identity = identity;
-    const dim3 g((unsigned)(a.n < kMaxGridX ? a.n : kMaxGridX)), b(kBlock);
-    for_cap(sketch_size, [&](auto cap) {
-        hipLaunchKernelGGL((screen_results_kernel<decltype(cap)::value>), g, b, 0, stream, a);
-    });
+    launch_results(a, false, stream);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t kmc_sketch_screen_winners_workspace_size(size_t index_bytes, uint64_t num_refs) {
+    if (num_refs == 0 || num_refs > KMC_SCREEN_MAX_VALUES || index_bytes < layout_bytes(kMinSlots)) return 0;
+    return winners_layout(nullptr, slots_within(index_bytes), num_refs).bytes;
+}
+
+extern "C" int kmc_sketch_screen_winners(const void *index, size_t index_bytes, const uint64_t *r_sketches,
+                                         const uint32_t *r_sizes, uint64_t num_refs, uint32_t sketch_size, int k,
+                                         uint32_t *won, uint32_t *median_won, float *identity_won,
+                                         uint32_t *shared_all, void *workspace, size_t workspace_bytes,
+                                         hipStream_t stream) {
+    bool nothing;
+    if (int e = results_check(index, index_bytes, r_sketches, r_sizes, num_refs, sketch_size, k, won, &nothing)) return e;
+    if (nothing) return KMC_OK;
+    const uint64_t slots = slots_within(index_bytes);
+    int device = 0;  // (a caller's workspace is judged, and bound, without one)
+    if (!workspace)
+        if (hipError_t he = hipGetDevice(&device)) return (int)he;
+    WLayout L;
+    if (int e = bind_layout(w_ws, device, workspace, workspace_bytes, 8,
+                            [&](void *b) { return winners_layout(b, slots, num_refs); }, &L))
+        return e;
+    if (hipError_t he = hipMemsetAsync(L.owner, 0, ((size_t)slots + 1) * 8, stream)) return (int)he;
+    RArgs a{};
+    a.index = const_cast<void *>(index);
+    a.index_bytes = index_bytes;
+    a.rows = r_sketches;
+    a.sizes = r_sizes;
+    a.n = (int64_t)num_refs;
+    a.s = sketch_size;
+    a.k = k;
+    a.shared = shared_all ? shared_all : L.all;  // the first pass: results' shared, nothing else
+    launch_results(a, false, stream);
+    a.all = a.shared;
+    a.owner = L.owner;
+    a.owner_slots = slots;
+    hipLaunchKernelGGL(screen_claim_kernel, dim3((unsigned)(a.n < kMaxGridX ? a.n : kMaxGridX)), dim3(kBlock), 0, stream, a);
+    a.shared = won;
+    a.median = median_won;
+    a.identity = identity_won;
+    launch_results(a, true, stream);
     return (int)hipGetLastError();
 }

@@ -245,6 +245,10 @@ def _load(path):
     L.kmc_sketch_screen_count.argtypes = [_P, ctypes.c_size_t, _P, _P, _U64, _U64, ctypes.c_int, ctypes.c_uint, _U64, _P]
     L.kmc_sketch_screen_results.argtypes = [_P, ctypes.c_size_t, _P, _P, _U64, ctypes.c_uint32, ctypes.c_int, _P, _P,
                                             _P, _P]
+    L.kmc_sketch_screen_winners_workspace_size.restype = ctypes.c_size_t
+    L.kmc_sketch_screen_winners_workspace_size.argtypes = [ctypes.c_size_t, _U64]
+    L.kmc_sketch_screen_winners.argtypes = [_P, ctypes.c_size_t, _P, _P, _U64, ctypes.c_uint32, ctypes.c_int, _P, _P,
+                                            _P, _P, _P, ctypes.c_size_t, _P]
     L.kmc_sketch_accum_device_bytes.restype = ctypes.c_size_t
     L.kmc_sketch_accum_device_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     L.kmc_sketch_accum_create.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint, _U64, ctypes.c_uint32,
@@ -745,6 +749,36 @@ def sketch_screen_results(index, r, rs, k, median=True, identity=True, out=None,
                                          _dptr(ident), _stream(stream))
     _check(rc, "kmc_sketch_screen_results")
     return sh, med, ident
+
+
+def sketch_screen_winners_workspace_size(index, num_refs):
+    """Bytes of sketch_screen_winners' workspace for `index` (the tensor, or its size in
+    bytes) and num_refs rows; 0 on bad arguments and for no row."""
+    nbytes = index if isinstance(index, int) else index.numel() * index.element_size()
+    return int(lib().kmc_sketch_screen_winners_workspace_size(nbytes, num_refs))
+
+
+def sketch_screen_winners(index, r, rs, k, median=True, identity=True, shared_all=True, workspace=None, out=None,
+                          stream=None):
+    """The results with every found value credited to the best row that holds it only
+    (kmc_sketch_screen_winners; Mash's screen -w): (won int32 [n], median multiplicity of
+    the won values int32 [n] or None, identity of won / size float32 [n] or None,
+    sketch_screen_results' shared int32 [n] or None); `out`: the caller's own four."""
+    import torch
+    with _on(stream):
+        r = r.contiguous()
+        n, s = int(r.shape[0]), int(r.shape[1])
+        if out is not None:
+            won, med, ident, sh = out
+        else:
+            won = torch.empty(n, dtype=torch.int32, device=r.device)
+            med = torch.empty(n, dtype=torch.int32, device=r.device) if median else None
+            ident = torch.empty(n, dtype=torch.float32, device=r.device) if identity else None
+            sh = torch.empty(n, dtype=torch.int32, device=r.device) if shared_all else None
+    rc = lib().kmc_sketch_screen_winners(*_ws(index), _dptr(r), _dptr(rs), n, s, k, _dptr(won), _dptr(med),
+                                         _dptr(ident), _dptr(sh), *_ws(workspace), _stream(stream))
+    _check(rc, "kmc_sketch_screen_winners")
+    return won, med, ident, sh
 
 
 SKETCH_ACCUM_MIN_LOG2_SLOTS = 4

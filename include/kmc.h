@@ -683,6 +683,70 @@ KMC_API int kmc_sketch_screen_results(const void *index, size_t index_bytes, con
                                       const uint32_t *r_sizes, uint64_t num_refs, uint32_t sketch_size, int k,
                                       uint32_t *shared, uint32_t *median_mult, float *identity, hipStream_t stream);
 
+/* Winner-takes-all results (Mash's screen -w), for a redundant reference collection.
+ * In kmc_sketch_screen_results every row that holds a found value counts it as its own:
+ * twenty strains of one species all report an identity near 1 when one is present.
+ * Here every found value is credited to one row only, the best that holds it.
+ *
+ * kmc_sketch_screen_winners: the inputs of kmc_sketch_screen_results: a built and
+ * counted index and a row set (the one given to build, or any other: values not in the
+ * index are absent; values are assumed distinct within a row, a repeated value gives an
+ * unspecified result and no stray access).  The rule is defined on integers only, like
+ * kmc_sketch_nearest's order and kmc_sketch_cluster's links: it depends on no float and
+ * no device pow.
+ *   size[r]        min(r_sizes[r], sketch_size)
+ *   all[r]         the number of the row's values with multiplicity > 0: exactly
+ *                  kmc_sketch_screen_results' shared[r]
+ *   ranking        row a ranks before row b iff all[a] * size[b] > all[b] * size[a], or
+ *                  the products are equal and a < b (exact in 64 bits: both factors are
+ *                  at most 16384).  A row with all == 0 holds no found value and never
+ *                  competes.
+ *   winner(v)      for every indexed value v with multiplicity > 0: the first row in
+ *                  that ranking among the rows that hold v within their size.  One
+ *                  round, from the first-pass counts, as Mash does it; not iterated.
+ *   won[r]         the number of the row's values v with multiplicity > 0 and
+ *                  winner(v) == r
+ *   median_won[r]  the lower median of the multiplicities of those won values
+ *                  (ascending, element (won - 1) / 2); 0 when won == 0.  May be NULL.
+ *   identity_won[r] kmc_sketch_screen_results' formula on (won[r], size[r], k), by the
+ *                  same device function: NaN for size 0, +0.0f for won == 0, 1.0f for
+ *                  won == size, otherwise pow((double)won / size, 1.0 / k) rounded to
+ *                  float.  May be NULL.
+ *   shared_all[r]  all[r].  May be NULL.
+ * UINT64_MAX within a row's size is a real value and takes part like any other.
+ * Consequences: the sum of won over the rows is the number of distinct found values
+ * that at least one row holds; won[r] <= all[r]; a row set with no value shared
+ * between rows has won == all, and identity and median are then bit for bit those of
+ * kmc_sketch_screen_results; the result does not depend on the order in which the
+ * device processes rows.
+ *   workspace      device scratch of kmc_sketch_screen_winners_workspace_size() bytes,
+ *                  8-byte aligned (KMC_ERR_ALIGNMENT), or NULL for a library-owned buffer
+ *                  under kmc_pair_distances' rule (NULL-workspace calls on a device must
+ *                  not overlap); KMC_ERR_WORKSPACE when smaller.  One 64-bit owner word
+ *                  for every slot an index of index_bytes can hold, one for UINT64_MAX,
+ *                  and all[]:
+ *                      8 (C' + 1)  +  4 num_refs  bytes (each array rounded up to 256),
+ *                  C' the largest power of two in 8..2^32 with 256 + round256(4 C') +
+ *                  8 C' <= index_bytes.  Host numbers only, no device; 0 on bad arguments
+ *                  (index_bytes below the smallest index, num_refs above
+ *                  KMC_SCREEN_MAX_VALUES) and for num_refs == 0; monotone in both.
+ * It does not modify the index: count, winners, results, count, winners is a valid
+ * sequence.  Asynchronous on `stream`, no host read-back; the work launched (one memset
+ * of the owner words, the first pass, a claim and a recount) depends on the host
+ * arguments only; nothing a former call left in the workspace is read.  The device
+ * checks the slot count in the index's header against index_bytes and against the
+ * owner words: on a blob that was never built the outputs are unspecified (they may
+ * be left unwritten), with no stray access.  Errors, judged before any device is
+ * touched, are those of kmc_sketch_screen_results in its order (null won for null
+ * shared), then KMC_ERR_WORKSPACE and KMC_ERR_ALIGNMENT for the workspace.
+ * num_refs == 0: KMC_OK, nothing written. */
+KMC_API size_t kmc_sketch_screen_winners_workspace_size(size_t index_bytes, uint64_t num_refs);
+KMC_API int kmc_sketch_screen_winners(const void *index, size_t index_bytes, const uint64_t *r_sketches,
+                                      const uint32_t *r_sizes, uint64_t num_refs, uint32_t sketch_size, int k,
+                                      uint32_t *won, uint32_t *median_won, float *identity_won,
+                                      uint32_t *shared_all, void *workspace, size_t workspace_bytes,
+                                      hipStream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* Sketching a sequence set of any size with a minimum k-mer abundance (Mash's -m).
  * In reads a large share of the distinct k-mers are sequencing errors seen once; they

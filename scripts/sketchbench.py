@@ -14,7 +14,10 @@ references, on synthetic rows (profiles/pr_sketch_query.jsonl).
 With --screen: kmc_sketch_screen_build, _count and _results of 1000 references of
 1 Mbase (and of 100 of 5 kbase) in a mixture of 1000 x 1 Mbase, beside
 kmc_sketch_from_sequences_grouped over the same mixture as one group, the same walk
-plus the set upkeep (profiles/pr_sketch_screen.jsonl).
+plus the set upkeep (profiles/pr_sketch_screen.jsonl); kmc_sketch_screen_winners on the
+same counted index beside _results, and once more on a redundant collection: the same
+rows as 50 groups of 20 that share 90 % of their values (--out
+profiles/pr_screen_winners.jsonl).
 With --accum: kmc_sketch_accum_add over the same mixture, as one call and as 16 calls
 (j rises and purges happen), and kmc_sketch_accum_finish, beside kmc_sketch_screen_count
 against the 1000-reference index and kmc_sketch_from_sequences_grouped with one group:
@@ -339,7 +342,9 @@ def screen_main(args, dev):
     mixture (reference r, r even, is the head of mixture record r); shared == size is
     asserted for them, and no more than chance hits for the others, before anything is
     timed.  The
-    yardstick for count is the grouped sketch of the whole mixture, on the same buffer."""
+    yardstick for count is the grouped sketch of the whole mixture, on the same buffer.
+    winners runs on the same counted index as results, with a caller's workspace; with
+    nothing shared between rows its numbers are asserted to be results' own."""
     k, s, records = 21, 1000, 1000
     record_len = max(int(1_000_000 * args.scale), 5000)
     mix = torch.empty(records * (record_len + 1), dtype=torch.uint8, device=dev)
@@ -364,24 +369,81 @@ def screen_main(args, dev):
             # (chance hits: 10^9 windows against 2.2 x 10^12 canonical 21-mers, 0.45 expected per reference)
             assert int(sh[1::2].max()) <= 10, (name, "a reference that is not in the mixture shares", int(sh[1::2].max()))
             assert int(med[::2].min()) == 1 and float(ident[::2].min()) == 1.0, (name, int(med[::2].min()))
+            ws = torch.empty(kmc.sketch_screen_winners_workspace_size(index, nrefs), dtype=torch.uint8, device=dev)
+            won, wmed, wident, wall = kmc.sketch_screen_winners(index, sk, sz, k, workspace=ws)
+            torch.cuda.synchronize()
+            # (a chance hit is a value of the mixture record it hits, mostly one of that record's smallest: when
+            # the record is a reference too, the two contest it and the contained one wins)
+            assert torch.equal(wall, sh) and bool((won <= wall).all()) and int(won.sum()) == distinct_found(index, sk, k), name
+            assert int((sh[::2] - won[::2]).max()) <= 10 and torch.equal(wmed[::2], med[::2]), name
             # the share of the mixture's windows at or below the largest indexed value: what the prefilter passes
             top = int(sk.max()) if int(sk.min()) >= 0 else None  # (as int64: every value below 2^63)
             rec = {
                 "input": name, "refs": nrefs, "ref_len": ref_len, "mixture_records": records,
                 "mixture_record_len": record_len, "k": k, "sketch_size": s, "contained_found_whole": True,
                 "chance_hits_max": int(sh[1::2].max()),
-                "index_bytes": int(index.numel()),
+                "index_bytes": int(index.numel()), "winners_workspace_bytes": int(ws.numel()),
                 "prefilter_pass_fraction": None if top is None else top / 2.0 ** 64,
                 "kmc_sketch_screen_build": timed(lambda: kmc.sketch_screen_build(sk, sz, index=index), args.runs),
                 "kmc_sketch_screen_count": timed(lambda: kmc.sketch_screen_count(index, mix, midx, k), args.runs),
                 "kmc_sketch_screen_results": timed(lambda: kmc.sketch_screen_results(index, sk, sz, k), args.runs),
+                "kmc_sketch_screen_winners": timed(lambda: kmc.sketch_screen_winners(index, sk, sz, k, workspace=ws),
+                                                   args.runs),
                 "kmc_sketch_from_sequences_grouped": grouped,
             }
             out.write(json.dumps(rec) + "\n")
             out.flush()
             print(json.dumps(rec), flush=True)
-            del sk, sz, index
+            if name == "genomes":
+                rec = screen_redundant(args, dev, sk, mix, midx, k, s)
+                out.write(json.dumps(rec) + "\n")
+                out.flush()
+                print(json.dumps(rec), flush=True)
+            del sk, sz, index, ws
             torch.cuda.empty_cache()
+
+
+def distinct_found(index, rows, k):
+    """How many distinct values of the rows the index holds with a multiplicity above 0:
+    the results of one-value rows.  The sum of winners' won must be this number."""
+    values = torch.unique(rows.reshape(-1)).reshape(-1, 1)
+    ones = torch.ones(values.shape[0], dtype=torch.int32, device=rows.device)
+    found, _, _ = kmc.sketch_screen_results(index, values, ones, k, median=False, identity=False)
+    return int(found.sum())
+
+
+def screen_redundant(args, dev, sk, mix, midx, k, s):
+    """The "genomes" rows as a redundant collection: 50 groups of 20 rows; row j of a group
+    keeps its own first s / 10 values and takes the other 9 s / 10 from the group's row 0.
+    Every second row is in the mixture, so in each group row 0 (all found, the smallest
+    index) wins the shared values, the other rows that are in the mixture win their own
+    s / 10, and the rows that are not win nothing but chance hits: asserted before timing,
+    with the sum of won against the number of distinct found values."""
+    n, group, own = int(sk.shape[0]), 20, s // 10
+    assert n % group == 0
+    rows = sk.view(n // group, group, s).clone()
+    rows[:, :, own:] = rows[:, :1, own:]
+    rows = rows.view(n, s).contiguous()
+    sz = torch.full((n,), s, dtype=torch.int32, device=dev)
+    index = kmc.sketch_screen_build(rows, sz)
+    kmc.sketch_screen_count(index, mix, midx, k)
+    ws = torch.empty(kmc.sketch_screen_winners_workspace_size(index, n), dtype=torch.uint8, device=dev)
+    sh, _, _ = kmc.sketch_screen_results(index, rows, sz, k)
+    won, _, _, wall = kmc.sketch_screen_winners(index, rows, sz, k, workspace=ws)
+    torch.cuda.synchronize()
+    won_g, sh_g = won.view(-1, group), sh.view(-1, group)
+    assert torch.equal(wall, sh) and int(sh_g[:, ::2].min()) == s and int(sh_g[:, 1::2].min()) >= s - own
+    assert bool((won <= wall).all()) and int(won.sum()) == distinct_found(index, rows, k)
+    # (but for the few values that two groups hold by chance)
+    assert int(won_g[:, 0].min()) >= s - 10 and int(won_g[:, 2::2].min()) >= own - 10 and int(won_g[:, 2::2].max()) == own
+    assert int(won_g[:, 1::2].max()) <= 10, int(won_g[:, 1::2].max())
+    return {
+        "input": "genomes_redundant", "refs": n, "groups": n // group, "rows_per_group": group, "shared_fraction": 0.9,
+        "k": k, "sketch_size": s, "index_bytes": int(index.numel()), "winners_workspace_bytes": int(ws.numel()),
+        "won_sum": int(won.sum()), "shared_sum": int(sh.sum()),
+        "kmc_sketch_screen_results": timed(lambda: kmc.sketch_screen_results(index, rows, sz, k), args.runs),
+        "kmc_sketch_screen_winners": timed(lambda: kmc.sketch_screen_winners(index, rows, sz, k, workspace=ws), args.runs),
+    }
 
 
 def accum_main(args, dev):
@@ -484,7 +546,8 @@ def main():
                          "100 of 5 kbase (s = 1000, k = 21, half of them cut from the mixture: asserted found "
                          "whole) in a synthetic mixture of 1000 x 1 Mbase, beside kmc_sketch_from_sequences_grouped "
                          "over the mixture as one group (2 warm-ups, median of --runs); appends to "
-                         "--out profiles/pr_sketch_screen.jsonl")
+                         "--out profiles/pr_sketch_screen.jsonl; kmc_sketch_screen_winners beside _results, also on a "
+                         "redundant collection: --out profiles/pr_screen_winners.jsonl")
     ap.add_argument("--accum", action="store_true",
                     help="time kmc_sketch_accum_add of the --screen mixture (1000 x 1 Mbase, s = 1000, k = 21) as one "
                          "call and as 16 calls, and kmc_sketch_accum_finish, beside kmc_sketch_screen_count against "
