@@ -31,6 +31,9 @@
 // spectrum (kmc_spectrum_from_accum, kmc_spectrum_summarize -> spectrum.tsv, spectrum_summary.tsv),
 // from which --min-abundance auto takes every file's M.  --cluster D: the sketches, however
 // made, are grouped at Mash distance D (kmc_sketch_cluster -> clusters.tsv) instead of compared.
+// --pairs D: the pairs of sketches within Mash distance D with their counts and distances
+// (kmc_sketch_links -> pairs.tsv; with --query FILE kmc_sketch_links_rect -> query_pairs.tsv)
+// instead of every distance.
 // GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
@@ -90,6 +93,8 @@ struct Options {
     long spectrum = 0;                // --spectrum B: the abundance spectrum of every input file, B bins (0: not given)
     double cluster = 0.0;  // --cluster D: clusters of the sketches at Mash distance D instead of their distances
     bool cluster_set = false;
+    double pairs = 0.0;  // --pairs D: the list of the pairs within Mash distance D instead of every distance
+    bool pairs_set = false;
 };
 
 // auto: FASTQ exactly when the name ends in .fq or .fastq, whatever the case
@@ -113,6 +118,7 @@ void usage(FILE *f) {
             "       kmc --canonical --sketch S --sketch-direct --per-file --min-abundance M [--batch BYTES] [options] <a.fastq> ...\n"
             "       kmc --canonical --sketch S --sketch-direct --per-file --spectrum B [--min-abundance auto] [options] <a.fastq> ...\n"
             "       kmc --canonical --sketch S [--sketch-direct] [--per-file] --cluster D [options] <input.fasta> ...\n"
+            "       kmc --canonical --sketch S [--sketch-direct] [--per-file] --pairs D [--query q.fasta] [options] <input.fasta> ...\n"
             "       kmc synth OUT.fa RECORDS LENGTH [SEED]   (benchmark input, SURVEY.md 8(d))\n"
             "  -k K              k-mer length (default %d, the reference's K); dense path 1..%d,\n"
             "                    --canonical 1..%d\n"
@@ -230,6 +236,15 @@ void usage(FILE *f) {
             "                    file with --per-file): index<TAB>representative<TAB>cluster<TAB>size, the\n"
             "                    representative being the cluster's smallest index and clusters numbered by\n"
             "                    it; sketch_results.csv is not written (no distance is kept)\n"
+            "  --pairs D         with --canonical --sketch S (with or without --sketch-direct, --per-file,\n"
+            "                    --min-count, --min-abundance), not with --cluster or --screen: only the pairs of\n"
+            "                    sketches whose Mash distance is at most D in 0..1 are written, not every distance\n"
+            "                    (kmc_sketch_links at kmc_mash_jaccard_of_distance(D, k): the pairs --cluster D\n"
+            "                    links; Mash's dist -d).  <out>/pairs.tsv gets one line per pair i < j, sorted by\n"
+            "                    (i, j): i<TAB>j<TAB>shared<TAB>denom<TAB>distance; sketch_results.csv is not\n"
+            "                    written.  With --query FILE (and no --top): every query sketch against every\n"
+            "                    reference sketch (kmc_sketch_links_rect), <out>/query_pairs.tsv with lines\n"
+            "                    query<TAB>ref<TAB>shared<TAB>denom<TAB>distance sorted by (query, ref)\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
@@ -352,6 +367,15 @@ int parse(int argc, char **argv, Options &o) {
                 fprintf(stderr, "kmc: --cluster takes a Mash distance in 0..1\n");
                 return usage(stderr), 2;
             }
+        } else if (a == "--pairs") {
+            char *end = nullptr;
+            const char *v = next("--pairs");
+            o.pairs = strtod(v, &end);
+            o.pairs_set = true;
+            if (end == v || *end != '\0' || !(o.pairs >= 0.0 && o.pairs <= 1.0)) {
+                fprintf(stderr, "kmc: --pairs takes a Mash distance in 0..1\n");
+                return usage(stderr), 2;
+            }
         } else if (a == "--softmask") {
             o.softmask = true;
         } else if (a == "--host-loader") {
@@ -440,6 +464,22 @@ int parse(int argc, char **argv, Options &o) {
     }
     if (o.cluster_set && (o.sketch == 0 || !o.query.empty() || !o.screen.empty())) {
         fprintf(stderr, "kmc: --cluster groups the sketches of --canonical --sketch S: not with --query or --screen\n");
+        return usage(stderr), 2;
+    }
+    if (o.pairs_set && o.sketch == 0) {
+        fprintf(stderr, "kmc: --pairs lists the pairs of the sketches of --canonical --sketch S\n");
+        return usage(stderr), 2;
+    }
+    if (o.pairs_set && o.cluster_set) {
+        fprintf(stderr, "kmc: --pairs and --cluster exclude each other\n");
+        return usage(stderr), 2;
+    }
+    if (o.pairs_set && !o.screen.empty()) {
+        fprintf(stderr, "kmc: --pairs and --screen exclude each other\n");
+        return usage(stderr), 2;
+    }
+    if (o.pairs_set && o.top_set) {
+        fprintf(stderr, "kmc: --pairs lists every pair of --query within its distance: not with --top\n");
         return usage(stderr), 2;
     }
     if (o.screen_batch && o.screen.empty()) {
@@ -673,6 +713,65 @@ int cluster_step(const Options &o, const uint64_t *d_sk, const uint32_t *d_sz, u
     return fclose(f) == 0 ? 0 : 1;
 }
 
+// --pairs D: the pairs within Mash distance D with their counts and distances, sorted, as
+// `name` in --out: the pairs i < j of the rows R (Q null: kmc_sketch_links), or every query
+// row of Q against every row of R (kmc_sketch_links_rect).  One call with room for
+// min(all pairs, 2^26) entries; a second one of exactly *num_links when they did not fit.
+int pairs_step(const Options &o, const uint64_t *q_sk, const uint32_t *q_sz, uint64_t m, const uint64_t *r_sk,
+               const uint32_t *r_sz, uint64_t n, hipStream_t st, const char *name) {
+    const uint32_t s = (uint32_t)o.sketch;
+    const double min_jaccard = kmc_mash_jaccard_of_distance(o.pairs, o.k);
+    const uint64_t all = q_sk ? m * n : n * (n > 0 ? n - 1 : 0) / 2;
+    uint64_t capacity = std::min<uint64_t>(all, 1ull << 26), found = 0;
+    DevBuf<kmc_sketch_link> d_links;
+    DevBuf<float> d_dist;
+    DevBuf<uint64_t> d_count;
+    Event t0 = make_event(), t1 = make_event();
+    HIPCHK(dev_alloc(d_count, 1));
+    HIPCHK(hipEventRecord(t0.get(), st));
+    for (int call = 0; call < 2; ++call) {
+        HIPCHK(dev_alloc(d_links, capacity));
+        HIPCHK(dev_alloc(d_dist, capacity));
+        if (q_sk)
+            KMCCHK(kmc_sketch_links_rect(q_sk, q_sz, m, r_sk, r_sz, n, s, o.k, min_jaccard, d_links.get(), d_dist.get(),
+                                         capacity, d_count.get(), st));
+        else
+            KMCCHK(kmc_sketch_links(r_sk, r_sz, n, s, o.k, min_jaccard, d_links.get(), d_dist.get(), capacity,
+                                    d_count.get(), st));
+        HIPCHK(hipMemcpyAsync(&found, d_count.get(), sizeof found, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (found <= capacity) break;
+        if (call == 1) return fprintf(stderr, "kmc: kmc_sketch_links: the list grew between two calls\n"), 1;
+        capacity = found;
+    }
+    HIPCHK(hipEventRecord(t1.get(), st));
+    HIPCHK(hipEventSynchronize(t1.get()));
+    std::vector<kmc_sketch_link> links(found);
+    std::vector<float> dist(found);
+    if (found > 0) {
+        HIPCHK(hipMemcpy(links.data(), d_links.get(), found * sizeof(kmc_sketch_link), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dist.data(), d_dist.get(), found * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    std::vector<uint64_t> order(found);  // the entries by (i, j): the device's order is unspecified
+    for (uint64_t e = 0; e < found; ++e) order[e] = e;
+    std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+        return links[a].i != links[b].i ? links[a].i < links[b].i : links[a].j < links[b].j;
+    });
+    if (!o.quiet) {
+        printf("Sketch pairs (distance <= %g): %.3f ms\n", o.pairs, ms_between(t0.get(), t1.get()));
+        if (q_sk)
+            printf("%" PRIu64 " pairs within %g of %" PRIu64 " queries and %" PRIu64 " records\n", found, o.pairs, m, n);
+        else
+            printf("%" PRIu64 " pairs within %g of %" PRIu64 " records\n", found, o.pairs, n);
+    }
+    const std::string path = o.out_dir + "/" + name;
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return fprintf(stderr, "kmc: cannot write %s\n", path.c_str()), 1;
+    for (uint64_t e : order)
+        fprintf(f, "%u\t%u\t%u\t%u\t%f\n", links[e].i, links[e].j, links[e].shared, links[e].denom, dist[e]);
+    return fclose(f) == 0 ? 0 : 1;
+}
+
 // --sketch: the rows of every record (make_rows: from the canonical lists or, with
 // --sketch-direct, from the record buffer), their Mash distances, sketch_results.csv
 template <class MakeRows>
@@ -687,6 +786,11 @@ int sketch_step(const Options &o, MakeRows make_rows, uint64_t n, hipStream_t st
     KMCCHK(make_rows(s, d_sk.get(), d_sz.get()));
     HIPCHK(hipEventRecord(r1.get(), st));
     if (o.cluster_set) return cluster_step(o, d_sk.get(), d_sz.get(), n, st, r0.get(), r1.get());
+    if (o.pairs_set) {
+        HIPCHK(hipEventSynchronize(r1.get()));
+        if (!o.quiet) printf("Sketch (s=%u): %.3f ms\n", s, ms_between(r0.get(), r1.get()));
+        return pairs_step(o, nullptr, nullptr, 0, d_sk.get(), d_sz.get(), n, st, "pairs.tsv");
+    }
     const auto distances = [&](float *d_out) {
         return kmc_sketch_distances(d_sk.get(), d_sz.get(), n, s, o.k, d_out, nullptr, nullptr, st);
     };
@@ -905,6 +1009,8 @@ int run_query(const Options &o, hipStream_t st) {
     if (int e = make_rows(o, files, "Reference", true, st, R)) return e;
     if (int e = make_rows(o, {o.query}, "Query", false, st, Q)) return e;
     const uint64_t m = Q.n, n = R.n;
+    if (o.pairs_set)  // Mash's dist -d of a query file against a collection
+        return pairs_step(o, Q.sk.get(), Q.sz.get(), m, R.sk.get(), R.sz.get(), n, st, "query_pairs.tsv");
     Event t0 = make_event(), t1 = make_event();
     if (top == 0) {  // the whole rectangle
         DevBuf<float> d_out;

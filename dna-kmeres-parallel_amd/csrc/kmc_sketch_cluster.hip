@@ -59,10 +59,7 @@ namespace {
 
 constexpr int kLabelBlock = 256;
 
-// the link rule: one IEEE double product and one compare, the same on host and device
-__host__ __device__ inline bool linked(uint32_t shared, uint32_t denom, double min_jaccard) {
-    return denom > 0 && (double)shared >= min_jaccard * (double)denom;
-}
+// (the link rule: linked() of kmc_sketch_pair.h, shared with kmc_sketch_links.hip)
 
 __device__ __forceinline__ uint32_t parent_of(const uint32_t *parent, uint32_t x) {
     return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -1,8 +1,8 @@
 // kmc_sketch_pair.h — what the sketch translation units share (device code and host
 // rules, no entry point), one definition each so that a fix reaches every user:
 //   rows and sets   lower_bound and bitonic_sort, for global and LDS pointers
-//   a pair          pair_counts and mash_distance: a pair has the same shared, denom
-//                   and float wherever it is computed
+//   a pair          pair_counts, mash_distance and linked: a pair has the same shared,
+//                   denom, float and link wherever it is computed
 //   a tile          stage_rows, tile_pairs (one wavefront per pair of a Tq x Tr tile)
 //                   and sketch_dist_kernel, the packed triangle (kmc_sketch.hip) and
 //                   the query x reference rectangle (kmc_sketch_query.hip) as shape
@@ -140,6 +140,13 @@ __device__ __forceinline__ float mash_distance(uint32_t shared, uint32_t denom, 
     double d = -log(2.0 * j / (1.0 + j)) / (double)k;
     if (d > 1.0) d = 1.0;
     return (float)d;
+}
+
+// The link rule of kmc_sketch_cluster and kmc_sketch_links[_rect] on a pair's counts: one
+// IEEE double product and one compare, the same on host and device.  (That neither row
+// is empty is the caller's `counts` predicate: the tile loop never hands such a pair on.)
+__host__ __device__ inline bool linked(uint32_t shared, uint32_t denom, double min_jaccard) {
+    return denom > 0 && (double)shared >= min_jaccard * (double)denom;
 }
 
 // the values of row r that count: its size, at most s

@@ -8,7 +8,8 @@
 // kmc_sketch_distances_rect: the m x n rectangle is cut into tiles of Tq query rows
 // by Tr reference rows; a workgroup stages the Tq + Tr rows of a tile in LDS and its
 // 16 wavefronts take the tile's pairs, one wavefront per pair: sketch_dist_kernel of
-// kmc_sketch_pair.h, the triangle's kernel, with the shape Rectangle below.  T is the
+// kmc_sketch_pair.h, the triangle's kernel, with the shape Rectangle of
+// kmc_sketch_rectangle.h (shared with the pair list, kmc_sketch_links.hip).  T is the
 // triangle's edge (tile_edge over kDistElems), Tq = min(T, m), Tr = min(kTileMax,
 // kDistElems / s - Tq, n) (tile_shape): a short query set leaves its room to the
 // references.  Below kStageMinTile (s > 2048 shipped) the rows stay in global memory.
@@ -59,6 +60,7 @@
 #include "kmc.h"
 #include "kmc_internal.h"
 #include "kmc_sketch_pair.h"
+#include "kmc_sketch_rectangle.h"
 #include "kmc_workspace.h"
 
 namespace kmc {
@@ -81,21 +83,7 @@ constexpr uint64_t kMaxRefs = 0xFFFFFFFEull;  // the index is 32 bits and UINT32
 static_assert(2 * KMC_NEAREST_MAX_TOP <= kMergeCap && kMergeElems <= kMergeCap, "merge buffer");
 static_assert(2 * KMC_NEAREST_MAX_TOP <= kCandElems, "one candidate buffer holds top + kTileMax keys");
 
-// ---------------------------------------------------------------------------
-// the rectangle
-// ---------------------------------------------------------------------------
-// The m x n rectangle as a shape of sketch_dist_kernel (kmc_sketch_pair.h): nrt tiles
-// per tile row, every pair of a tile, row-major results.
-struct Rectangle {
-    static __device__ __forceinline__ void tile(const DParams &p, int64_t t, uint64_t *buf, TileRows &A, TileRows &B) {
-        const int64_t bi = t / p.nrt, bj = t - bi * p.nrt;
-        A = TileRows{p.q, p.qs, bi * p.Tq, p.m, buf};
-        B = TileRows{p.r, p.rs, bj * p.Tr, p.n, buf + p.Tq * (int)p.s};
-    }
-    static __device__ __forceinline__ bool counts(int64_t, int64_t) { return true; }
-    static __device__ __forceinline__ int64_t index(const DParams &p, int64_t i, int64_t j) { return i * p.n + j; }
-};
-
+// (the rectangle: the shape Rectangle and rectangle_tiling of kmc_sketch_rectangle.h)
 // ---------------------------------------------------------------------------
 // the nearest references
 // ---------------------------------------------------------------------------
@@ -328,23 +316,13 @@ extern "C" int kmc_sketch_distances_rect(const uint64_t *q_sketches, const uint3
     if (!sketch_size_ok(sketch_size)) return KMC_ERR_INVALID_ARG;
     if (num_queries > KMC_SPARSE_MAX_SEQS || num_refs > KMC_SPARSE_MAX_SEQS) return KMC_ERR_INVALID_ARG;
     DParams p;
-    p.q = q_sketches;
-    p.qs = q_sizes;
-    p.r = r_sketches;
-    p.rs = r_sizes;
-    p.m = (int64_t)num_queries;
-    p.n = (int64_t)num_refs;
-    p.s = sketch_size;
     p.k = k;
     p.out = out;
     p.shared = shared;
     p.denom = denom;
-    const TileShape ts = tile_shape(kDistElems, sketch_size, p.m, p.n);
-    p.Tq = ts.Tq;
-    p.Tr = ts.Tr;
-    p.nrt = ceil_div(p.n, ts.Tr);
-    p.ntiles = ceil_div(p.m, ts.Tq) * p.nrt;
-    return launch_sketch_dist<Rectangle>(p, ts.stage, stream);
+    const bool stage = rectangle_tiling(p, q_sketches, q_sizes, (int64_t)num_queries, r_sketches, r_sizes,
+                                        (int64_t)num_refs, sketch_size);
+    return launch_sketch_dist<Rectangle>(p, stage, stream);
 }
 
 extern "C" size_t kmc_sketch_nearest_workspace_size(uint64_t num_queries, uint64_t num_refs, uint32_t sketch_size,

@@ -1,7 +1,8 @@
 // kmc_sketch_triangle.h — all pairs i < j of one row set as a shape of the tile loop of
-// kmc_sketch_pair.h, and the tiling both of its users launch with: the packed triangle
-// of distances (kmc_sketch.hip) and the links of the clustering (kmc_sketch_cluster.hip).
-// One definition, so that both visit the same pairs in the same tiles.
+// kmc_sketch_pair.h, and the tiling all of its users launch with: the packed triangle
+// of distances (kmc_sketch.hip), the links of the clustering (kmc_sketch_cluster.hip) and
+// the list of those links (kmc_sketch_links.hip).
+// One definition, so that all visit the same pairs in the same tiles.
 #pragma once
 
 #include "kmc_dist_common.h"

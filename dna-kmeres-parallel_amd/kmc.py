@@ -79,6 +79,11 @@ class SpectrumSummary(ctypes.Structure):
     ]
 
 
+class SketchLink(ctypes.Structure):
+    """kmc_sketch_link: one listed pair of kmc_sketch_links[_rect], 16 bytes."""
+    _fields_ = [("i", ctypes.c_uint32), ("j", ctypes.c_uint32), ("shared", ctypes.c_uint32), ("denom", ctypes.c_uint32)]
+
+
 _lib = None
 _diag_lib = None
 _active = None  # the diagnostic library while inside diag()
@@ -239,6 +244,9 @@ def _load(path):
     L.kmc_sketch_cluster_workspace_size.argtypes = [_U64, ctypes.c_int]
     L.kmc_sketch_cluster.argtypes = [_P, _P, _U64, ctypes.c_uint32, ctypes.c_double, _P, _P, _P, _P, ctypes.c_size_t,
                                      _P]
+    L.kmc_sketch_links.argtypes = [_P, _P, _U64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double, _P, _P, _U64, _P, _P]
+    L.kmc_sketch_links_rect.argtypes = [_P, _P, _U64, _P, _P, _U64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double, _P,
+                                        _P, _U64, _P, _P]
     L.kmc_sketch_screen_index_size.restype = ctypes.c_size_t
     L.kmc_sketch_screen_index_size.argtypes = [_U64, ctypes.c_uint32]
     L.kmc_sketch_screen_build.argtypes = [_P, _P, _U64, ctypes.c_uint32, _P, ctypes.c_size_t, _P]
@@ -696,6 +704,79 @@ def sketch_cluster(sketches, sizes, min_jaccard, index=True, workspace=None, out
                                   _dptr(count), *_ws(workspace), _stream(stream))
     _check(rc, "kmc_sketch_cluster")
     return labels[:n], cidx, count
+
+
+def _links(call, what, device, capacity, with_dist, out, stream):
+    """The two forms of sketch_links / sketch_links_rect: call(links, dist, capacity,
+    count) makes the library call on `stream`."""
+    import torch
+
+    def make(cap):
+        return (torch.empty((cap, 4), dtype=torch.int32, device=device),
+                torch.empty(cap, dtype=torch.float32, device=device) if with_dist else None)
+
+    if capacity is not None:
+        capacity = int(capacity)
+        with _on(stream):
+            if out is not None:
+                links, dist, count = out
+            else:
+                links, dist = make(capacity)
+                count = torch.empty(1, dtype=torch.int64, device=device)
+        _check(call(links if capacity > 0 else None, dist if capacity > 0 else None, capacity, count), what)
+        return links, dist, count
+    with _on(stream):
+        count = out[2] if out is not None else torch.empty(1, dtype=torch.int64, device=device)
+        _check(call(None, None, 0, count), what)
+        total = int(count.item())  # (waits for the stream)
+        links, dist = (out[0], out[1]) if out is not None else make(total)
+        if total > 0:
+            if int(links.shape[0]) < total or (dist is not None and int(dist.numel()) < total):
+                raise ValueError("%s: %d pairs, but `out` holds fewer entries" % (what, total))
+            _check(call(links, dist, total, count), what)
+            keys = (links[:total, 0].to(torch.int64) << 32) | links[:total, 1].to(torch.int64)
+            order = torch.argsort(keys)
+            links[:total] = links[:total][order]
+            if dist is not None:
+                dist[:total] = dist[:total][order]
+    return links[:total], None if dist is None else dist[:total], count
+
+
+def sketch_links(sketches, sizes, k, min_jaccard, capacity=None, with_dist=True, out=None, stream=None):
+    """The pairs i < j of sketch rows [n, s] with sizes [n] that kmc_sketch_cluster links at
+    min_jaccard (kmc_sketch_links): neither row empty and shared >= min_jaccard * denom.
+    Returns (links int32 [., 4], dist float32 [.] or None, num_links int64 [1]): a row of
+    links is (i, j, shared, denom), dist its Mash distance at k (with_dist=False: None,
+    not computed), num_links the number of listed pairs whether they fit or not.
+      capacity=N     asynchronous on the stream.  The tensors hold N entries, of which the
+                     first min(num_links, N) are written, in no particular order;
+                     capacity=0 is the count-only call (nothing but num_links is written).
+      capacity=None  the convenience form, SYNCHRONOUS: a count-only call, a wait for the
+                     stream, tensors of exactly num_links entries, a second call, and the
+                     entries sorted by (i, j).
+    `out` is the caller's own triple (links, dist or None, num_links); links and dist may be
+    longer than capacity (nothing is written at or beyond it)."""
+    with _on(stream):
+        sketches = sketches.contiguous()
+    n, s = int(sketches.shape[0]), int(sketches.shape[1])
+
+    def call(links, dist, cap, count):
+        return lib().kmc_sketch_links(_dptr(sketches), _dptr(sizes), n, s, k, float(min_jaccard), _dptr(links),
+                                      _dptr(dist), cap, _dptr(count), _stream(stream))
+    return _links(call, "kmc_sketch_links", sketches.device, capacity, with_dist, out, stream)
+
+
+def sketch_links_rect(q, qs, r, rs, k, min_jaccard, capacity=None, with_dist=True, out=None, stream=None):
+    """The pairs of a query row (q [m, s], sizes qs) and a reference row (r [n, s], sizes
+    rs) that the rule of sketch_links accepts (kmc_sketch_links_rect): a row of links is
+    (query, reference, shared, denom).  Forms, results and `out` as sketch_links; the
+    capacity=None form is synchronous and sorts by (query, reference)."""
+    q, r, m, n, s = _row_sets(q, r, stream)
+
+    def call(links, dist, cap, count):
+        return lib().kmc_sketch_links_rect(_dptr(q), _dptr(qs), m, _dptr(r), _dptr(rs), n, s, k, float(min_jaccard),
+                                           _dptr(links), _dptr(dist), cap, _dptr(count), _stream(stream))
+    return _links(call, "kmc_sketch_links_rect", q.device, capacity, with_dist, out, stream)
 
 
 SCREEN_MAX_VALUES = 1 << 30

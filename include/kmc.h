@@ -336,6 +336,7 @@ KMC_API int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *coun
  * kmc_sketch_distances_rect, every query against every reference, and
  * kmc_sketch_nearest, the best references of every query without that rectangle; and
  * kmc_sketch_cluster, the groups of one row set at a threshold without its pairs.
+ * kmc_sketch_links[_rect] list the pairs of either shape that are within a threshold.
  *
  * kmc_sketch_from_counts: sketches of the per-record lists of
  * kmc_count_canonical_hash[_ex], with the list conventions of
@@ -556,7 +557,45 @@ KMC_API int kmc_pair_distances_sparse(const uint64_t *keys, const uint32_t *coun
  * Host only, no device: e^(-k d) / (2 - e^(-k d)) in double, the J at which
  * -log(2J / (1 + J)) / k equals d, so a pair's distance is at most d exactly when its J
  * is at least this value.  NaN for d outside [0, 1] (or NaN) and for k outside
- * 1..KMC_CANON_MAX_K. */
+ * 1..KMC_CANON_MAX_K.
+ *
+ * kmc_sketch_links, kmc_sketch_links_rect: the pairs of rows within a distance, as a list
+ * with their counts and distances (Mash's dist -d: the edge list of a collection), without
+ * the triangle or the rectangle of all pairs.
+ *   listed pairs  kmc_sketch_links: a pair (i, j) with i < j is listed iff kmc_sketch_cluster
+ *                 links it at the same min_jaccard, exactly: neither row is empty and
+ *                     (double)shared >= min_jaccard * (double)denom
+ *                 with shared and denom kmc_sketch_distances' (the same device functions
+ *                 for the counts and for the rule).  The components of the listed pairs are
+ *                 kmc_sketch_cluster's clusters.  kmc_sketch_links_rect: every pair of a
+ *                 query row q and a reference row r is judged by that rule, and an entry's
+ *                 i is q, its j is r.  With both sets pointing at the same rows a row that
+ *                 is not empty pairs with itself (shared == denom), and (a, b) and (b, a)
+ *                 are both listed.
+ *   links         device kmc_sketch_link[capacity], 16-byte aligned (KMC_ERR_ALIGNMENT):
+ *                 entry e holds {i, j, shared, denom} of one listed pair
+ *   dist          device float[capacity], may be NULL: dist[e] is the distance of entry e,
+ *                 the float of kmc_sketch_distances[_rect] for that pair at this k, bit
+ *                 for bit (the same device function)
+ *   num_links     device uint64, required: after the call the number L of listed pairs,
+ *                 whether or not they fit.  The call zeroes it itself, on `stream`.
+ *   capacity      exactly min(L, capacity) entries are written, at positions 0 ..
+ *                 min(L, capacity) - 1 of links and dist; they are distinct pairs of the
+ *                 listed set; nothing is written at or beyond capacity.  capacity == 0
+ *                 with links == NULL and dist == NULL is the count-only call.
+ *   order         the input determines the set of entries.  Their order is unspecified
+ *                 and may differ from call to call; when L > capacity, which entries are
+ *                 kept is unspecified too.  A caller that needs all of them calls again
+ *                 with capacity >= *num_links.
+ * No workspace and no library-owned buffer: calls with different outputs may overlap.
+ * Asynchronous on `stream`, no host read-back; the work launched depends on the host
+ * arguments only.  Errors, judged before any device is touched and in this order: k outside
+ * 1..KMC_CANON_MAX_K: KMC_ERR_UNSUPPORTED_K; KMC_ERR_INVALID_ARG for a sketch_size outside
+ * 1..KMC_SKETCH_MAX_SIZE, a row count above KMC_SPARSE_MAX_SEQS, a min_jaccard outside
+ * [0, 1] or NaN, a null num_links, null links with capacity > 0, and null rows or sizes
+ * while there is a pair to judge; KMC_ERR_ALIGNMENT for links not 16-byte aligned.
+ * num_seqs < 2, or num_queries == 0 or num_refs == 0: KMC_OK and *num_links = 0, nothing
+ * else is written; the row pointers may then be NULL. */
 #define KMC_SKETCH_MAX_SIZE 16384
 #define KMC_NEAREST_MAX_TOP 1024
 #define KMC_SKETCH_DEFAULT_SEED 42ull
@@ -601,6 +640,14 @@ KMC_API size_t kmc_sketch_cluster_workspace_size(uint64_t num_seqs, int device);
 KMC_API int kmc_sketch_cluster(const uint64_t *sketches, const uint32_t *sketch_sizes, uint64_t num_seqs,
                                uint32_t sketch_size, double min_jaccard, uint32_t *labels, uint32_t *cluster_index,
                                uint32_t *num_clusters, void *workspace, size_t workspace_bytes, hipStream_t stream);
+typedef struct kmc_sketch_link { uint32_t i, j, shared, denom; } kmc_sketch_link; /* 16 bytes */
+KMC_API int kmc_sketch_links(const uint64_t *sketches, const uint32_t *sketch_sizes, uint64_t num_seqs,
+                             uint32_t sketch_size, int k, double min_jaccard, kmc_sketch_link *links, float *dist,
+                             uint64_t capacity, uint64_t *num_links, hipStream_t stream);
+KMC_API int kmc_sketch_links_rect(const uint64_t *q_sketches, const uint32_t *q_sizes, uint64_t num_queries,
+                                  const uint64_t *r_sketches, const uint32_t *r_sizes, uint64_t num_refs,
+                                  uint32_t sketch_size, int k, double min_jaccard, kmc_sketch_link *links,
+                                  float *dist, uint64_t capacity, uint64_t *num_links, hipStream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Screening a sequence set for the references it contains (containment; what Mash

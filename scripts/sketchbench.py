@@ -26,6 +26,9 @@ kmc_spectrum_from_accum of the same table with 256 and 8192 bins, beside _finish
 (--out profiles/pr_spectrum.jsonl).
 With --cluster: kmc_sketch_cluster beside kmc_sketch_distances on the same rows, unrelated
 rows and 64-member clusters of near-identical rows (profiles/pr_sketch_cluster.jsonl).
+With --links: kmc_sketch_links, count-only and with a fitting capacity, beside
+kmc_sketch_distances with counts and kmc_sketch_cluster on those rows
+(profiles/pr_sketch_links.jsonl).
 
 Inputs (synthetic, generated on the device):
   iid          8 x 50 Mbase independent records, k = 31
@@ -337,6 +340,66 @@ def cluster_main(args, dev):
                 torch.cuda.empty_cache()
 
 
+def links_main(args, dev):
+    """--links: kmc_sketch_links at the Jaccard threshold of Mash distance 0.05 on the rows of
+    --cluster, count-only and with a capacity that fits, beside the two yardsticks that read
+    the same rows through the same tiles in the same process: kmc_sketch_distances with its
+    counts (the only route to the list before) and kmc_sketch_cluster.  unrelated: no pair is
+    listed; clustered: 64-member groups, 2016 pairs each.  The list is asserted (its count,
+    every pair inside a group, the components equal to the clustering's labels) before
+    anything is timed."""
+    k, s, members = 21, 1000, 64
+    mj = kmc.mash_jaccard_of_distance(0.05, k)
+    with open(args.out, "w") as out:
+        for n in (4096, 65536):
+            n = max(int(n * args.scale), 2 * members)
+            runs = args.runs if n <= 8192 else max(3, args.runs // 3)
+            pairs = n * (n - 1) // 2
+            for name, make in (("unrelated", synthetic_rows), ("clustered", clustered_rows)):
+                rows, sizes = make(n, s, dev, 3)
+                links, dist, count = kmc.sketch_links(rows, sizes, k, mj)  # (sorted, exact capacity)
+                total = int(count)
+                groups, last = divmod(n, members)
+                exp = 0 if name == "unrelated" else groups * (members * (members - 1) // 2) + last * (last - 1) // 2
+                assert total == exp == links.shape[0], (name, total, exp)
+                labels, _, _ = kmc.sketch_cluster(rows, sizes, mj, index=False)
+                if total:
+                    assert torch.equal(links[:, 0] // members, links[:, 1] // members) and bool((links[:, 0] < links[:, 1]).all())
+                    assert torch.equal(labels[links[:, 0].long()], labels[links[:, 1].long()])
+                    assert torch.unique((links[:, 0].long() << 32) | links[:, 1].long()).numel() == total
+                    assert bool((links[:, 2].double() >= mj * links[:, 3].double()).all()) and float(dist.max()) <= 0.05
+                cap = max(total, 1)
+                outs = (torch.empty((cap, 4), dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.float32, device=dev),
+                        count)
+                ws = torch.empty(kmc.sketch_cluster_workspace_size(n), dtype=torch.uint8, device=dev)
+                only = timed(lambda: kmc.sketch_links(rows, sizes, k, mj, capacity=0, out=(None, None, count)), runs, warmup=1)
+                fit = timed(lambda: kmc.sketch_links(rows, sizes, k, mj, capacity=cap, out=outs), runs, warmup=1)
+                assert int(count) == total
+                clu = timed(lambda: kmc.sketch_cluster(rows, sizes, mj, workspace=ws, out=(labels, None, None)), runs, warmup=1)
+                rec = {
+                    "collection": name, "rows": n, "sketch_size": s, "k": k, "max_dist": 0.05, "min_jaccard": mj,
+                    "members": members if name == "clustered" else 1, "pairs": pairs, "links": total,
+                    "list_bytes": 20 * total, "triangle_with_counts_bytes": 12 * pairs,
+                    "kmc_sketch_links_count_only": only, "kmc_sketch_links": fit, "kmc_sketch_cluster_labels_only": clu,
+                    "links_over_cluster": fit["ms_median"] / clu["ms_median"],
+                    "count_only_over_cluster": only["ms_median"] / clu["ms_median"],
+                }
+                del outs, ws, links, dist
+                torch.cuda.empty_cache()
+                free = torch.cuda.mem_get_info(dev)[0]
+                if 12 * pairs <= free - (4 << 30):  # the triangle with its counts, where it fits
+                    tri_out = tuple(torch.empty(pairs, dtype=t, device=dev) for t in (torch.float32, torch.int32, torch.int32))
+                    tri = timed(lambda: kmc.sketch_distances(rows, sizes, k, with_counts=True, out=tri_out), runs, warmup=1)
+                    rec["kmc_sketch_distances_with_counts"] = tri
+                    rec["links_over_triangle"] = fit["ms_median"] / tri["ms_median"]
+                    del tri_out
+                out.write(json.dumps(rec) + "\n")
+                out.flush()
+                print(json.dumps(rec), flush=True)
+                del rows, sizes, labels, count
+                torch.cuda.empty_cache()
+
+
 def screen_main(args, dev):
     """--screen: references in a mixture.  Half of the references are cut from the
     mixture (reference r, r even, is the head of mixture record r); shared == size is
@@ -559,8 +622,15 @@ def main():
                          "of s = 1000, unrelated and in 64-member clusters of near-identical rows (labels asserted; "
                          "1 warm-up, median of --runs, of at least 5 at 65536 rows); --out "
                          "profiles/pr_sketch_cluster.jsonl")
+    ap.add_argument("--links", action="store_true",
+                    help="time kmc_sketch_links, count-only and with a fitting capacity, beside kmc_sketch_distances "
+                         "with counts (where the triangle fits) and kmc_sketch_cluster on the rows of --cluster (the "
+                         "list asserted; 1 warm-up, median of --runs, of a third of them and at least 3 at 65536 "
+                         "rows); --out profiles/pr_sketch_links.jsonl")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.links:
+        return links_main(args, dev)
     if args.cluster:
         return cluster_main(args, dev)
     if args.accum:
