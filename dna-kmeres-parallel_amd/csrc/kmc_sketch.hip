@@ -357,11 +357,8 @@ extern "C" int kmc_sketch_distances(const uint64_t *sketches, const uint32_t *sk
     if (!sketches || !sketch_sizes || !out) return KMC_ERR_INVALID_ARG;
     if (!sketch_size_ok(sketch_size)) return KMC_ERR_INVALID_ARG;
     if (num_seqs > KMC_SPARSE_MAX_SEQS) return KMC_ERR_INVALID_ARG;
-    DParams p;
-    p.k = k;
-    p.out = out;
-    p.shared = shared;
-    p.denom = denom;
+    Tiling p;
     const bool stage = triangle_tiling(p, sketches, sketch_sizes, (int64_t)num_seqs, sketch_size);
-    return launch_sketch_dist<Triangle>(p, stage, stream);
+    launch_tiles<Triangle>(p, stage, DistOut{out, shared, denom, k}, stream);
+    return (int)hipGetLastError();
 }

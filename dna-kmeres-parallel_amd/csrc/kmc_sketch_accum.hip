@@ -25,12 +25,12 @@
 // compare against a kernel argument; j = 0: every window).  N bounds the windows, so
 // with a fixed hash the expected number of tracked keys stays at or below C / 4.
 //
-//   add     the screen's walk (kmc_canon_walk.h: for_each_piece, chunk_raw, chunk_keys
-//           with the identity functor, so a window keeps its key; kmc_sketch_walk.h:
-//           the launch shape and walk_of).  A window whose hash passes the threshold
+//   add     the walk of kmc_sketch_walk.h (for_each_piece of kmc_canon_walk.h, then
+//           for_each_chunk with the identity functor, so a window keeps its key; the
+//           launch shape and walk_of).  A window whose hash passes the threshold
 //           probes from its slot: its key found, the count takes a vector atomic add
 //           (no return value), once per run of equal keys among a thread's 16
-//           windows; an empty slot found, the thread reserves an entry (the one
+//           windows (add_runs); an empty slot found, the thread reserves an entry (the one
 //           returning atomic, on `tracked`, that only a new key pays) and inserts the
 //           key with a 64-bit compare-and-swap; a slot that went to another thread
 //           gives the reservation back.  A new key is refused when C / 2 entries are
@@ -195,58 +195,27 @@ struct KeyOf {  // a window keeps its key: the slot needs the hash, the table th
 };
 
 struct AArgs {
-    const char *data;  // rounded down to 16 bytes
-    Offsets idx;
-    int64_t n;
-    int k;
-    uint32_t flags;
-    int G;
+    WalkArgs w;
     uint64_t seed;
     uint64_t maxh;  // hashes above it leave
     Table T;
 };
 
 template <bool FWD, bool BIGK>
-__device__ __forceinline__ void add_piece(const AArgs &a, const Walk &W, int64_t ps, int64_t pe, int64_t rend) {
-    const int tid = threadIdx.x;
-    const int64_t c0 = ps >> 4, c1 = ((pe - 1) >> 4) + 1;
-    ChunkRaw nx = chunk_raw(W, (c0 + tid) << 4);
-    for (int64_t cb = c0; cb < c1; cb += kBlock) {
-        const int64_t c = cb + tid;
-        unsigned long long key[16];
-        const ChunkRaw cr = nx;
-        nx = chunk_raw(W, (c + kBlock) << 4);  // next round's chunk
-        uint32_t pend = chunk_keys<FWD, BIGK>(W, cr, c << 4, ps, pe, rend, KeyOf{}, key);  // (past the piece: 0)
-        uint32_t cm = 0u;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) cm |= (uint32_t)(sketch_hash(key[j], a.seed) <= a.maxh) << j;
-        pend &= cm;
-        if (pend == 0u) continue;
-        unsigned long long last = 0;
-        uint32_t *at = nullptr;
-        uint32_t run = 0u;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            if (!((pend >> j) & 1u)) continue;
-            if (run && key[j] == last) {
-                ++run;
-                continue;
-            }
-            if (run && at) __hip_atomic_fetch_add(at, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last = key[j];
-            at = find_or_insert<true>(a.T, last, sketch_hash(last, a.seed));
-            run = 1u;
-        }
-        if (run && at) __hip_atomic_fetch_add(at, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-template <bool FWD, bool BIGK>
 __global__ __launch_bounds__(kBlock) void accum_add_kernel(AArgs a) {
     __shared__ int64_t s_first;
-    const Walk W = walk_of(a.data, a.idx, a.n, a.k, a.flags, a.G);
+    const Walk W = walk_of(a.w);
     for_each_piece(W, &s_first, [&](int64_t, int64_t ps, int64_t pe, int64_t rend) {
-        add_piece<FWD, BIGK>(a, W, ps, pe, rend);
+        for_each_chunk<FWD, BIGK>(W, ps, pe, rend, KeyOf{}, [&](const unsigned long long(&key)[16], uint32_t pend) {
+            uint32_t cm = 0u;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) cm |= (uint32_t)(sketch_hash(key[j], a.seed) <= a.maxh) << j;
+            pend &= cm;
+            if (pend)
+                add_runs(key, pend, [&](unsigned long long v) {
+                    return find_or_insert<true>(a.T, v, sketch_hash(v, a.seed));
+                });
+        });
     });
 }
 
@@ -448,7 +417,7 @@ extern "C" int kmc_sketch_accum_create(uint32_t sketch_size, int k, unsigned fla
                                        kmc_sketch_accum **out) {
     if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
     if (!sketch_size_ok(sketch_size) || !log2_slots_ok(log2_slots) || !out) return KMC_ERR_INVALID_ARG;
-    if (flags & ~(KMC_CANON_SOFTMASK | KMC_CANON_FORWARD)) return KMC_ERR_INVALID_ARG;
+    if (!walk_flags_ok(flags)) return KMC_ERR_INVALID_ARG;
     *out = nullptr;
     kmc_sketch_accum *a = new (std::nothrow) kmc_sketch_accum();
     if (!a) return KMC_ERR_NOMEM;
@@ -478,8 +447,8 @@ extern "C" int kmc_sketch_accum_add(kmc_sketch_accum *a, const char *data, const
                                     uint64_t data_bytes, hipStream_t stream) {
     if (!a || num_seqs > kMaxSeqs) return KMC_ERR_INVALID_ARG;
     if (num_seqs == 0) return KMC_OK;
-    if (!indices || (data_bytes > 0 && !data)) return KMC_ERR_INVALID_ARG;
-    if (data_bytes >= (1ull << 62) || a->N + data_bytes >= (1ull << 62)) return KMC_ERR_INVALID_ARG;
+    if (!walk_ptrs_ok(data, indices, data_bytes)) return KMC_ERR_INVALID_ARG;
+    if (!walk_sizes_ok(num_seqs, data_bytes) || a->N + data_bytes >= (1ull << 62)) return KMC_ERR_INVALID_ARG;
     int device = 0, cus = 0;
     if (int e = current_device_cus(&device, &cus)) return e;
     const uint64_t C = 1ull << a->lg, N = a->N + data_bytes;
@@ -499,27 +468,12 @@ extern "C" int kmc_sketch_accum_add(kmc_sketch_accum *a, const char *data, const
         a->j = j;
         a->active = to;
     }
-    // any `data` pointer: rounded down to 16 bytes, every offset moved up by the difference
-    const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
-    AArgs g;
-    g.data = data - mis;
-    g.idx = Offsets{indices, (int64_t)data_bytes, (int64_t)mis};
-    g.n = (int64_t)num_seqs;
-    g.k = a->k;
-    g.flags = a->flags;
-    g.G = walk_groups(data_bytes, cus);
-    g.seed = a->seed;
-    g.maxh = max_hash(a->j);
-    g.T = table_of(a, a->active);
-    const bool fwd = a->flags & KMC_CANON_FORWARD, big = a->k >= 16;
-    const dim3 grid((unsigned)g.G), block(kBlock);
-    if (fwd) {
-        if (big) hipLaunchKernelGGL((accum_add_kernel<true, true>), grid, block, 0, stream, g);
-        else hipLaunchKernelGGL((accum_add_kernel<true, false>), grid, block, 0, stream, g);
-    } else {
-        if (big) hipLaunchKernelGGL((accum_add_kernel<false, true>), grid, block, 0, stream, g);
-        else hipLaunchKernelGGL((accum_add_kernel<false, false>), grid, block, 0, stream, g);
-    }
+    const AArgs g{walk_args(data, indices, num_seqs, data_bytes, a->k, a->flags, cus), a->seed, max_hash(a->j),
+                  table_of(a, a->active)};
+    for_walk(a->flags, a->k, [&](auto fwd, auto big) {
+        hipLaunchKernelGGL((accum_add_kernel<decltype(fwd)::value, decltype(big)::value>), dim3((unsigned)g.w.G),
+                           dim3(kBlock), 0, stream, g);
+    });
     if (hipError_t he = hipGetLastError()) return (int)he;
     a->N = N;
     return KMC_OK;

@@ -11,9 +11,9 @@
 // cluster of its own at every threshold.
 //
 //   init     parent[i] = i
-//   link     the triangle's tiling (Triangle and triangle_tiling of
-//            kmc_sketch_triangle.h; stage_rows and tile_pairs of kmc_sketch_pair.h, staged
-//            or not as sketch_dist_kernel), with a sink that applies the rule and, on a
+//   link     the tile loop of kmc_sketch_pair.h (sketch_tile_kernel, staged or not) over
+//            the triangle's tiling (Triangle and triangle_tiling of
+//            kmc_sketch_triangle.h), with a consumer that applies the rule and, on a
 //            link, unites the two records in the forest `parent`:
 //                find both roots (follow parent until parent[x] == x);
 //                hook the larger root under the smaller by a compare-and-swap that
@@ -94,27 +94,21 @@ __global__ __launch_bounds__(kLabelBlock) void cluster_init_kernel(uint32_t *par
         parent[i] = (uint32_t)i;
 }
 
-// sketch_dist_kernel's tile loop over the triangle (p.out, p.shared, p.denom and p.k unused)
-template <bool STAGE>
-__global__ __launch_bounds__(kDistBlock) void cluster_link_kernel(DParams p, uint32_t *parent, double min_jaccard) {
-    __shared__ uint64_t buf[STAGE ? kDistElems : 1];
-    const int tid = threadIdx.x, Tq = p.Tq, Tr = p.Tr, s = (int)p.s;
-    for (int64_t t = blockIdx.x; t < p.ntiles; t += gridDim.x) {
-        TileRows A, B;
-        Triangle::tile(p, t, buf, A, B);
-        if constexpr (STAGE) {
-            __syncthreads();  // the last tile's readers are done
-            stage_rows(A, Tq, s, tid);
-            stage_rows(B, Tr, s, tid);
-            __syncthreads();
-        }
-        tile_pairs<STAGE>(A, B, Tq, Tr, s, tid,
-                          [&](int64_t i, int64_t j) { return Triangle::counts(i, j) && p.qs[i] > 0 && p.qs[j] > 0; },
-                          [&](int, int, int64_t i, int64_t j, uint32_t sh, uint32_t dn) {
-                              if (linked(sh, dn, min_jaccard)) unite(parent, (uint32_t)i, (uint32_t)j);
-                          });
+// The consumer of the link launch (sketch_tile_kernel over the triangle): the pairs of
+// two non-empty rows, and a union for every one that is linked.
+struct LinkUnion {
+    static constexpr bool kEpilogue = false;
+    using Lds = NoLds;
+    uint32_t *parent;
+    double min_jaccard;
+    __device__ __forceinline__ bool counts(const Tiling &p, int64_t i, int64_t j) const {
+        return p.qs[i] > 0 && p.qs[j] > 0;  // (the triangle: one row set)
     }
-}
+    template <class Shape>
+    __device__ __forceinline__ void sink(const Tiling &, Lds &, int64_t i, int64_t j, uint32_t sh, uint32_t dn) const {
+        if (linked(sh, dn, min_jaccard)) unite(parent, (uint32_t)i, (uint32_t)j);
+    }
+};
 
 // after the link launch: plain loads see every hook
 __global__ __launch_bounds__(kLabelBlock) void cluster_flatten_kernel(const uint32_t *parent, int64_t n,
@@ -181,7 +175,7 @@ extern "C" int kmc_sketch_cluster(const uint64_t *sketches, const uint32_t *sket
                                   uint32_t sketch_size, double min_jaccard, uint32_t *labels, uint32_t *cluster_index,
                                   uint32_t *num_clusters, void *workspace, size_t workspace_bytes, hipStream_t stream) {
     if (!cluster_args_ok(num_seqs, sketch_size)) return KMC_ERR_INVALID_ARG;
-    if (!(min_jaccard >= 0.0 && min_jaccard <= 1.0)) return KMC_ERR_INVALID_ARG;  // (NaN among them)
+    if (!min_jaccard_ok(min_jaccard)) return KMC_ERR_INVALID_ARG;
     if (!labels) return KMC_ERR_INVALID_ARG;
     if (num_seqs == 0) return num_clusters ? (int)hipMemsetAsync(num_clusters, 0, sizeof(uint32_t), stream) : KMC_OK;
     if (!sketches || !sketch_sizes) return KMC_ERR_INVALID_ARG;
@@ -195,18 +189,9 @@ extern "C" int kmc_sketch_cluster(const uint64_t *sketches, const uint32_t *sket
     const unsigned grid = (unsigned)(blocks < kMaxGridX ? blocks : kMaxGridX);
     hipLaunchKernelGGL(cluster_init_kernel, dim3(grid), dim3(kLabelBlock), 0, stream, L.parent, n);
     if (n > 1) {
-        DParams p;
-        p.k = 0;
-        p.out = nullptr;
-        p.shared = p.denom = nullptr;
+        Tiling p;
         const bool stage = triangle_tiling(p, sketches, sketch_sizes, n, sketch_size);
-        const unsigned tgrid = (unsigned)(p.ntiles < kMaxGridX ? p.ntiles : kMaxGridX);
-        if (stage)
-            hipLaunchKernelGGL(cluster_link_kernel<true>, dim3(tgrid), dim3(kDistBlock), 0, stream, p, L.parent,
-                               min_jaccard);
-        else
-            hipLaunchKernelGGL(cluster_link_kernel<false>, dim3(tgrid), dim3(kDistBlock), 0, stream, p, L.parent,
-                               min_jaccard);
+        launch_tiles<Triangle>(p, stage, LinkUnion{L.parent, min_jaccard}, stream);
     }
     const bool rank = cluster_index || num_clusters;
     hipLaunchKernelGGL(cluster_flatten_kernel, dim3(grid), dim3(kLabelBlock), 0, stream, L.parent, n, labels,

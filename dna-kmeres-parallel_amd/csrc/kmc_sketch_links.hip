@@ -8,10 +8,11 @@
 // {i, j, shared, denom} and, beside it, mash_distance(shared, denom, k): the float of
 // kmc_sketch_distances[_rect] for that pair.
 //
-// One kernel over both shapes (Triangle of kmc_sketch_triangle.h, Rectangle of
-// kmc_sketch_rectangle.h), staged or not, with the tiling of the distance kernels: the
-// tile loop of cluster_link_kernel with another sink.  tile_pairs hands the sink one pair
-// per wavefront, from lane 0; a listed pair goes to the tile's buffer in LDS (at most
+// The tile loop of kmc_sketch_pair.h (sketch_tile_kernel) over both shapes (Triangle of
+// kmc_sketch_triangle.h, Rectangle of kmc_sketch_rectangle.h), staged or not, with the
+// tiling of the distance kernels and the consumer LinkOut, the only one with an epilogue.
+// tile_pairs hands its sink one pair per wavefront, from lane 0 (LinkOut::sink); a listed
+// pair goes to the tile's buffer in LDS (at most
 // Tq x Tr <= kTileMax^2 entries of 16 bytes) at a position taken from an LDS counter.
 // Behind a barrier one thread reserves the tile's block of the output,
 //     base = atomic add(*num_links, count)       (64-bit, relaxed, agent scope)
@@ -51,68 +52,61 @@ constexpr int kLinkTile = kTileMax * kTileMax;  // entries of one tile at most
 static_assert(sizeof(kmc_sketch_link) == 16 && sizeof(kmc_sketch_link) == sizeof(uint4), "one 16-byte store per entry");
 static_assert(kLinkTile <= kDistBlock, "a thread per entry of a tile");  // (tile_edge and tile_shape cap both edges at kTileMax)
 
+// The consumer of both entry points (sketch_tile_kernel over either shape): the pairs
+// of two non-empty rows; a linked one goes to the tile's buffer, and the epilogue
+// reserves the tile's block of the output and writes it.
 struct LinkOut {
+    static constexpr bool kEpilogue = true;
+    struct Lds {
+        uint4 found[kLinkTile];   // the tile's listed pairs: {i, j, shared, denom}
+        uint32_t taken;           // positions handed out since the launch began
+        unsigned long long base;  // the tile's first entry in the output
+    };
+    double min_jaccard;
+    int k;
     uint4 *links;  // kmc_sketch_link[capacity], or null
     float *dist;   // [capacity], or null
     uint64_t capacity;
     unsigned long long *num_links;
-};
+    uint32_t seen;  // `taken` before this tile, every thread's own (the host: 0)
 
-// sketch_dist_kernel's tile loop over a shape (p.out, p.shared and p.denom unused)
-template <class Shape, bool STAGE>
-__global__ __launch_bounds__(kDistBlock) void sketch_links_kernel(DParams p, double min_jaccard, LinkOut o) {
-    __shared__ uint64_t buf[STAGE ? kDistElems : 1];
-    __shared__ uint4 found[kLinkTile];  // the tile's listed pairs: {i, j, shared, denom}
-    __shared__ uint32_t taken;          // positions handed out since the launch began
-    __shared__ unsigned long long base; // the tile's first entry in the output
-    const int tid = threadIdx.x, Tq = p.Tq, Tr = p.Tr, s = (int)p.s;
-    if (tid == 0) taken = 0;  // (published by the first tile's top barrier)
-    uint32_t seen = 0;        // `taken` before this tile
-    for (int64_t t = blockIdx.x; t < p.ntiles; t += gridDim.x) {
-        TileRows A, B;
-        Shape::tile(p, t, buf, A, B);
-        __syncthreads();  // the last tile's readers are done: of the rows, of found and of base
-        if constexpr (STAGE) {
-            stage_rows(A, Tq, s, tid);
-            stage_rows(B, Tr, s, tid);
-            __syncthreads();
-        }
-        tile_pairs<STAGE>(A, B, Tq, Tr, s, tid,
-                          [&](int64_t i, int64_t j) { return Shape::counts(i, j) && p.qs[i] > 0 && p.rs[j] > 0; },
-                          [&](int, int, int64_t i, int64_t j, uint32_t sh, uint32_t dn) {
-                              if (!linked(sh, dn, min_jaccard)) return;
-                              // a pair is handed over once: fewer than Tq * Tr <= kLinkTile positions per tile
-                              const uint32_t at = atomicAdd(&taken, 1u) - seen;
-                              if (at < (uint32_t)kLinkTile) found[at] = make_uint4((uint32_t)i, (uint32_t)j, sh, dn);
-                          });
-        __syncthreads();  // the tile's pairs are in found
-        const uint32_t now = taken;  // (the same in every thread: nothing is appended before the next top barrier)
+    __device__ __forceinline__ void begin(Lds &L, int tid) const {
+        if (tid == 0) L.taken = 0;  // (published by the first tile's top barrier)
+    }
+    // the last tile's readers are done, of found and of base too: the unstaged loop
+    // has no barrier of its own here
+    template <bool STAGE>
+    __device__ __forceinline__ void top() const {
+        if constexpr (!STAGE) __syncthreads();
+    }
+    __device__ __forceinline__ bool counts(const Tiling &p, int64_t i, int64_t j) const {
+        return p.qs[i] > 0 && p.rs[j] > 0;
+    }
+    template <class Shape>
+    __device__ __forceinline__ void sink(const Tiling &, Lds &L, int64_t i, int64_t j, uint32_t sh, uint32_t dn) const {
+        if (!linked(sh, dn, min_jaccard)) return;
+        // a pair is handed over once: fewer than Tq * Tr <= kLinkTile positions per tile
+        const uint32_t at = atomicAdd(&L.taken, 1u) - seen;
+        if (at < (uint32_t)kLinkTile) L.found[at] = make_uint4((uint32_t)i, (uint32_t)j, sh, dn);
+    }
+    // (behind the barrier after the tile's pairs: they are in found)
+    __device__ __forceinline__ void epilogue(const Tiling &, Lds &L, int tid) {
+        const uint32_t now = L.taken;  // (the same in every thread: nothing is appended before the next top barrier)
         const uint32_t count = now - seen;
         seen = now;
-        if (count == 0) continue;
+        if (count == 0) return;
         if (tid == 0)
-            base = __hip_atomic_fetch_add(o.num_links, (unsigned long long)count, __ATOMIC_RELAXED,
-                                          __HIP_MEMORY_SCOPE_AGENT);
+            L.base = __hip_atomic_fetch_add(num_links, (unsigned long long)count, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
-        const uint64_t at = (uint64_t)base + (uint64_t)tid;
-        if ((uint32_t)tid < count && tid < kLinkTile && at < o.capacity) {
-            const uint4 e = found[tid];
-            o.links[at] = e;
-            if (o.dist) o.dist[at] = mash_distance(e.z, e.w, p.k);
+        const uint64_t at = (uint64_t)L.base + (uint64_t)tid;
+        if ((uint32_t)tid < count && tid < kLinkTile && at < capacity) {
+            const uint4 e = L.found[tid];
+            links[at] = e;
+            if (dist) dist[at] = mash_distance(e.z, e.w, k);
         }
     }
-}
-
-template <class Shape>
-inline int launch_links(const DParams &p, bool stage, double min_jaccard, const LinkOut &o, hipStream_t stream) {
-    const unsigned grid = (unsigned)(p.ntiles < kMaxGridX ? p.ntiles : kMaxGridX);
-    if (stage)
-        hipLaunchKernelGGL((sketch_links_kernel<Shape, true>), dim3(grid), dim3(kDistBlock), 0, stream, p, min_jaccard, o);
-    else
-        hipLaunchKernelGGL((sketch_links_kernel<Shape, false>), dim3(grid), dim3(kDistBlock), 0, stream, p, min_jaccard,
-                           o);
-    return (int)hipGetLastError();
-}
+};
 
 // what both entry points refuse before the rows are looked at, in the header's order
 inline int links_args(uint64_t rows_a, uint64_t rows_b, uint32_t sketch_size, int k, double min_jaccard,
@@ -120,18 +114,17 @@ inline int links_args(uint64_t rows_a, uint64_t rows_b, uint32_t sketch_size, in
     if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
     if (!sketch_size_ok(sketch_size)) return KMC_ERR_INVALID_ARG;
     if (rows_a > KMC_SPARSE_MAX_SEQS || rows_b > KMC_SPARSE_MAX_SEQS) return KMC_ERR_INVALID_ARG;
-    if (!(min_jaccard >= 0.0 && min_jaccard <= 1.0)) return KMC_ERR_INVALID_ARG;  // (NaN among them)
+    if (!min_jaccard_ok(min_jaccard)) return KMC_ERR_INVALID_ARG;
     if (!num_links) return KMC_ERR_INVALID_ARG;
     if (!links && capacity > 0) return KMC_ERR_INVALID_ARG;
     return KMC_OK;
 }
 
-inline LinkOut link_out(int k, DParams &p, kmc_sketch_link *links, float *dist, uint64_t capacity, uint64_t *num_links) {
-    p.k = k;
-    p.out = nullptr;
-    p.shared = p.denom = nullptr;
+inline LinkOut link_out(double min_jaccard, int k, kmc_sketch_link *links, float *dist, uint64_t capacity,
+                        uint64_t *num_links) {
     // (null links: capacity is 0, links_args saw to it, and nothing is written)
-    return LinkOut{reinterpret_cast<uint4 *>(links), dist, capacity, reinterpret_cast<unsigned long long *>(num_links)};
+    return LinkOut{min_jaccard, k, reinterpret_cast<uint4 *>(links), dist, capacity,
+                   reinterpret_cast<unsigned long long *>(num_links), 0u};
 }
 
 }  // namespace
@@ -148,10 +141,10 @@ extern "C" int kmc_sketch_links(const uint64_t *sketches, const uint32_t *sketch
     if ((uintptr_t)links % 16) return KMC_ERR_ALIGNMENT;
     if (hipError_t he = hipMemsetAsync(num_links, 0, sizeof(uint64_t), stream)) return (int)he;
     if (!pairs) return KMC_OK;
-    DParams p;
-    const LinkOut o = link_out(k, p, links, dist, capacity, num_links);
+    Tiling p;
     const bool stage = triangle_tiling(p, sketches, sketch_sizes, (int64_t)num_seqs, sketch_size);
-    return launch_links<Triangle>(p, stage, min_jaccard, o, stream);
+    launch_tiles<Triangle>(p, stage, link_out(min_jaccard, k, links, dist, capacity, num_links), stream);
+    return (int)hipGetLastError();
 }
 
 extern "C" int kmc_sketch_links_rect(const uint64_t *q_sketches, const uint32_t *q_sizes, uint64_t num_queries,
@@ -164,9 +157,9 @@ extern "C" int kmc_sketch_links_rect(const uint64_t *q_sketches, const uint32_t 
     if ((uintptr_t)links % 16) return KMC_ERR_ALIGNMENT;
     if (hipError_t he = hipMemsetAsync(num_links, 0, sizeof(uint64_t), stream)) return (int)he;
     if (!pairs) return KMC_OK;
-    DParams p;
-    const LinkOut o = link_out(k, p, links, dist, capacity, num_links);
+    Tiling p;
     const bool stage = rectangle_tiling(p, q_sketches, q_sizes, (int64_t)num_queries, r_sketches, r_sizes,
                                         (int64_t)num_refs, sketch_size);
-    return launch_links<Rectangle>(p, stage, min_jaccard, o, stream);
+    launch_tiles<Rectangle>(p, stage, link_out(min_jaccard, k, links, dist, capacity, num_links), stream);
+    return (int)hipGetLastError();
 }

@@ -4,12 +4,15 @@
 //   a pair          pair_counts, mash_distance and linked: a pair has the same shared,
 //                   denom, float and link wherever it is computed
 //   a tile          stage_rows, tile_pairs (one wavefront per pair of a Tq x Tr tile)
-//                   and sketch_dist_kernel, the packed triangle (kmc_sketch.hip) and
-//                   the query x reference rectangle (kmc_sketch_query.hip) as shape
-//                   policies; the top-hits search streams its own tiles through
+//                   and sketch_tile_kernel, the one loop over the tiles of a Tiling:
+//                   the packed triangle and the query x reference rectangle are its
+//                   shape policies (kmc_sketch_triangle.h, kmc_sketch_rectangle.h);
+//                   the distances (DistOut, here), the clustering and the pair list
+//                   are its consumers, each beside its entry point; launch_tiles
+//                   launches it.  The top-hits search streams its own tiles through
 //                   tile_pairs
 //   host            tile_edge / tile_shape, for_cap, pow2_at_least, ceil_div and the
-//                   two argument checks every entry point makes
+//                   argument checks the entry points share
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -38,6 +41,7 @@ constexpr uint64_t kFill = ~0ull;  // after a row's values, and the padding of e
 
 inline bool sketch_size_ok(uint32_t s) { return s >= 1 && s <= KMC_SKETCH_MAX_SIZE; }
 inline bool canon_k_ok(int k) { return k >= 1 && k <= KMC_CANON_MAX_K; }
+inline bool min_jaccard_ok(double x) { return x >= 0.0 && x <= 1.0; }  // (NaN: no)
 
 __host__ __device__ inline int pow2_at_least(int64_t v) {
     int p = 1;
@@ -224,54 +228,90 @@ __device__ __forceinline__ void tile_pairs(const TileRows &A, const TileRows &B,
     }
 }
 
-// All pairs of m query rows and n reference rows that a shape counts, in tiles of
-// Tq x Tr.  A Shape gives
-//   tile    the two row sets of tile t, staged at buf and buf + Tq * s
-//   counts  whether the pair (i, j) is one of the shape's
-//   index   where the pair's results go
-struct DParams {
+// The tiling of m query rows against n reference rows in tiles of Tq x Tr, filled by
+// the shape's host function (triangle_tiling, rectangle_tiling): the rows and the
+// geometry, nothing of what a consumer does with a pair.
+struct Tiling {
     const uint64_t *q, *r;
     const uint32_t *qs, *rs;
     int64_t m, n;
     int64_t nrt, ntiles;  // tile columns; tiles
     uint32_t s;
-    int k, Tq, Tr;
-    float *out;
-    uint32_t *shared, *denom;
+    int Tq, Tr;
 };
 
-template <class Shape, bool STAGE>
-__global__ __launch_bounds__(kDistBlock) void sketch_dist_kernel(DParams p) {
+struct NoLds {};  // the LDS state of a consumer that has no epilogue
+
+// All pairs that a shape counts, tile by tile, handed to a consumer: the one tile loop
+// of the distances, the clustering and the pair list.  A Shape gives
+//   tile    the two row sets of tile t, staged at buf and buf + Tq * s
+//   counts  whether the pair (i, j) is one of the shape's
+//   index   where a pair's results go in the shape's own output order
+// A Consumer is a small struct passed by value (its outputs and its threshold) with
+//   counts(p, i, j)                     what else a pair must meet to be counted at all
+//   sink<Shape>(p, L, i, j, sh, dn)     lane 0 of the pair's wavefront, with its counts
+//   kEpilogue, Lds                      whether the whole workgroup runs a step after a
+//       tile's pairs, behind a barrier, on LDS state L of the consumer's own type:
+//       begin(L, tid) before the first tile, top<STAGE>() where a tile starts (the
+//       staged loop has a barrier there; what the consumer needs beyond it is its own),
+//       epilogue(p, L, tid) after the barrier behind the pairs.  Without one (NoLds)
+//       the loop holds none of these, no LDS and no barrier for it.
+template <class Shape, bool STAGE, class Consumer>
+__global__ __launch_bounds__(kDistBlock) void sketch_tile_kernel(Tiling p, Consumer c) {
     __shared__ uint64_t buf[STAGE ? kDistElems : 1];  // query rows: [a * s], reference rows: [(Tq + b) * s]
+    __shared__ typename Consumer::Lds L;
     const int tid = threadIdx.x, Tq = p.Tq, Tr = p.Tr, s = (int)p.s;
+    if constexpr (Consumer::kEpilogue) c.begin(L, tid);
     for (int64_t t = blockIdx.x; t < p.ntiles; t += gridDim.x) {
         TileRows A, B;
         Shape::tile(p, t, buf, A, B);
+        if constexpr (Consumer::kEpilogue) c.template top<STAGE>();
         if constexpr (STAGE) {
             __syncthreads();  // the last tile's readers are done
             stage_rows(A, Tq, s, tid);
             stage_rows(B, Tr, s, tid);
             __syncthreads();
         }
-        tile_pairs<STAGE>(A, B, Tq, Tr, s, tid, [](int64_t i, int64_t j) { return Shape::counts(i, j); },
+        tile_pairs<STAGE>(A, B, Tq, Tr, s, tid,
+                          [&](int64_t i, int64_t j) { return Shape::counts(i, j) && c.counts(p, i, j); },
                           [&](int, int, int64_t i, int64_t j, uint32_t sh, uint32_t dn) {
-                              const int64_t o = Shape::index(p, i, j);
-                              p.out[o] = mash_distance(sh, dn, p.k);
-                              if (p.shared) p.shared[o] = sh;
-                              if (p.denom) p.denom[o] = dn;
+                              c.template sink<Shape>(p, L, i, j, sh, dn);
                           });
+        if constexpr (Consumer::kEpilogue) {
+            __syncthreads();  // the tile's pairs went through the sink
+            c.epilogue(p, L, tid);
+        }
     }
 }
 
-template <class Shape>
-inline int launch_sketch_dist(const DParams &p, bool stage, hipStream_t stream) {
+// staged or not, one workgroup per tile up to the grid's limit (the caller reads the
+// launch's error with its others)
+template <class Shape, class Consumer>
+inline void launch_tiles(const Tiling &p, bool stage, const Consumer &c, hipStream_t stream) {
     const unsigned grid = (unsigned)(p.ntiles < kMaxGridX ? p.ntiles : kMaxGridX);
     if (stage)
-        hipLaunchKernelGGL((sketch_dist_kernel<Shape, true>), dim3(grid), dim3(kDistBlock), 0, stream, p);
+        hipLaunchKernelGGL((sketch_tile_kernel<Shape, true, Consumer>), dim3(grid), dim3(kDistBlock), 0, stream, p, c);
     else
-        hipLaunchKernelGGL((sketch_dist_kernel<Shape, false>), dim3(grid), dim3(kDistBlock), 0, stream, p);
-    return (int)hipGetLastError();
+        hipLaunchKernelGGL((sketch_tile_kernel<Shape, false, Consumer>), dim3(grid), dim3(kDistBlock), 0, stream, p, c);
 }
+
+// The consumer of kmc_sketch_distances and kmc_sketch_distances_rect: every pair of the
+// shape, its distance (and counts, where asked for) at the shape's index.
+struct DistOut {
+    static constexpr bool kEpilogue = false;
+    using Lds = NoLds;
+    float *out;
+    uint32_t *shared, *denom;  // or null
+    int k;
+    __device__ __forceinline__ bool counts(const Tiling &, int64_t, int64_t) const { return true; }
+    template <class Shape>
+    __device__ __forceinline__ void sink(const Tiling &p, Lds &, int64_t i, int64_t j, uint32_t sh, uint32_t dn) const {
+        const int64_t o = Shape::index(p, i, j);
+        out[o] = mash_distance(sh, dn, k);
+        if (shared) shared[o] = sh;
+        if (denom) denom[o] = dn;
+    }
+};
 
 }  // namespace
 }  // namespace kmc

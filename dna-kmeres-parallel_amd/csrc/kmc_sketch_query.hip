@@ -7,8 +7,8 @@
 //
 // kmc_sketch_distances_rect: the m x n rectangle is cut into tiles of Tq query rows
 // by Tr reference rows; a workgroup stages the Tq + Tr rows of a tile in LDS and its
-// 16 wavefronts take the tile's pairs, one wavefront per pair: sketch_dist_kernel of
-// kmc_sketch_pair.h, the triangle's kernel, with the shape Rectangle of
+// 16 wavefronts take the tile's pairs, one wavefront per pair: sketch_tile_kernel of
+// kmc_sketch_pair.h, the triangle's kernel and consumer, with the shape Rectangle of
 // kmc_sketch_rectangle.h (shared with the pair list, kmc_sketch_links.hip).  T is the
 // triangle's edge (tile_edge over kDistElems), Tq = min(T, m), Tr = min(kTileMax,
 // kDistElems / s - Tq, n) (tile_shape): a short query set leaves its room to the
@@ -315,14 +315,11 @@ extern "C" int kmc_sketch_distances_rect(const uint64_t *q_sketches, const uint3
     if (!q_sketches || !q_sizes || !r_sketches || !r_sizes || !out) return KMC_ERR_INVALID_ARG;
     if (!sketch_size_ok(sketch_size)) return KMC_ERR_INVALID_ARG;
     if (num_queries > KMC_SPARSE_MAX_SEQS || num_refs > KMC_SPARSE_MAX_SEQS) return KMC_ERR_INVALID_ARG;
-    DParams p;
-    p.k = k;
-    p.out = out;
-    p.shared = shared;
-    p.denom = denom;
+    Tiling p;
     const bool stage = rectangle_tiling(p, q_sketches, q_sizes, (int64_t)num_queries, r_sketches, r_sizes,
                                         (int64_t)num_refs, sketch_size);
-    return launch_sketch_dist<Rectangle>(p, stage, stream);
+    launch_tiles<Rectangle>(p, stage, DistOut{out, shared, denom, k}, stream);
+    return (int)hipGetLastError();
 }
 
 extern "C" size_t kmc_sketch_nearest_workspace_size(uint64_t num_queries, uint64_t num_refs, uint32_t sketch_size,

@@ -21,15 +21,15 @@
 //           value inserts it with a 64-bit compare-and-swap: equal values of several
 //           rows meet in one slot.  The largest value goes through an LDS maximum per
 //           workgroup into one 64-bit atomic maximum.
-//   count   the sketcher's walk (kmc_canon_walk.h: for_each_piece, chunk_raw,
-//           chunk_keys with the hash functor) over the same ranges of the same launch
-//           shape (kmc_sketch_walk.h), with no per-record state, no LDS set, no
-//           barrier inside a piece and no cut merge: a record matters only for which
-//           windows exist.  A window's hash h leaves after one compare when h > maxv
-//           (reference rows are bottom-s sets: almost every window of a mixture);
-//           the others probe the table and add to the multiplicity with a vector
-//           global atomic (no return value).  A thread adds once per run of equal
-//           hashes among its 16 windows (a homopolymer run is one add of 16, not 16).
+//   count   the walk of kmc_sketch_walk.h (for_each_piece of kmc_canon_walk.h, then
+//           for_each_chunk with the hash functor) over the ranges and the launch shape
+//           of the sketcher, with no per-record state, no LDS set, no barrier inside
+//           a piece and no cut merge: a record matters only for which windows exist.
+//           A window's hash h leaves after one compare when h > maxv (reference rows
+//           are bottom-s sets: almost every window of a mixture); the others probe
+//           the table and add to the multiplicity with a vector global atomic (no
+//           return value), once per run of equal hashes among a thread's 16 windows
+//           (add_runs).
 //           The offsets are clamped to [0, data_bytes] and moved by data & 15 as they
 //           are read (Offsets), so the call needs no workspace.
 //   results one workgroup per reference row: each value is looked up, the found
@@ -201,59 +201,14 @@ __global__ __launch_bounds__(kBuildBlock) void screen_build_kernel(BArgs a) {
 using Walk = WalkOf<Offsets>;
 
 struct CArgs {
-    const char *data;  // rounded down to 16 bytes
-    Offsets idx;
-    int64_t n;
-    int k;
-    uint32_t flags;
-    int G;
+    WalkArgs w;
     uint64_t seed;
     void *index;
     uint64_t index_bytes;
 };
 
-// The windows of record piece [ps, pe): every hash at or below maxv (or UINT64_MAX,
-// when that is indexed) is looked up and counted.
-template <bool FWD, bool BIGK>
-__device__ __forceinline__ void count_piece(const Table &T, uint64_t maxv, bool has_ff, const Walk &W, const HashOf hf,
-                                            int64_t ps, int64_t pe, int64_t rend) {
-    const int tid = threadIdx.x;
-    const int64_t c0 = ps >> 4, c1 = ((pe - 1) >> 4) + 1;
-    ChunkRaw nx = chunk_raw(W, (c0 + tid) << 4);
-    for (int64_t cb = c0; cb < c1; cb += kBlock) {
-        const int64_t c = cb + tid;
-        unsigned long long h[16];
-        const ChunkRaw cr = nx;
-        nx = chunk_raw(W, (c + kBlock) << 4);  // next round's chunk
-        uint32_t pend = chunk_keys<FWD, BIGK>(W, cr, c << 4, ps, pe, rend, hf, h);  // (past the piece: 0)
-        uint32_t cm = 0u;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) cm |= (uint32_t)(h[j] <= maxv) << j;
-        if (has_ff) {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) cm |= (uint32_t)(h[j] == kFill) << j;
-        }
-        pend &= cm;
-        if (pend == 0u) continue;
-        uint64_t last = 0;
-        uint32_t *at = nullptr;
-        uint32_t run = 0u;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            if (!((pend >> j) & 1u)) continue;
-            if (run && h[j] == last) {
-                ++run;
-                continue;
-            }
-            if (run && at) __hip_atomic_fetch_add(at, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last = h[j];
-            at = find(T, last, has_ff);
-            run = 1u;
-        }
-        if (run && at) __hip_atomic_fetch_add(at, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
+// Every window's hash at or below maxv (or UINT64_MAX, when that is indexed) is looked
+// up and counted.
 template <bool FWD, bool BIGK>
 __global__ __launch_bounds__(kBlock) void screen_count_kernel(CArgs a) {
     __shared__ int64_t s_first;
@@ -261,10 +216,20 @@ __global__ __launch_bounds__(kBlock) void screen_count_kernel(CArgs a) {
     if (!T.ok) return;
     const uint64_t maxv = T.hd->maxv;
     const bool has_ff = T.hd->has_ff != 0u;
-    const Walk W = walk_of(a.data, a.idx, a.n, a.k, a.flags, a.G);
+    const Walk W = walk_of(a.w);
     const HashOf hf{a.seed};
     for_each_piece(W, &s_first, [&](int64_t, int64_t ps, int64_t pe, int64_t rend) {
-        count_piece<FWD, BIGK>(T, maxv, has_ff, W, hf, ps, pe, rend);
+        for_each_chunk<FWD, BIGK>(W, ps, pe, rend, hf, [&](const unsigned long long(&h)[16], uint32_t pend) {
+            uint32_t cm = 0u;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) cm |= (uint32_t)(h[j] <= maxv) << j;
+            if (has_ff) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) cm |= (uint32_t)(h[j] == kFill) << j;
+            }
+            pend &= cm;
+            if (pend) add_runs(h, pend, [&](uint64_t v) { return find(T, v, has_ff); });
+        });
     });
 }
 
@@ -490,35 +455,17 @@ extern "C" int kmc_sketch_screen_build(const uint64_t *r_sketches, const uint32_
 extern "C" int kmc_sketch_screen_count(void *index, size_t index_bytes, const char *data, const int64_t *indices,
                                        uint64_t num_seqs, uint64_t data_bytes, int k, unsigned flags, uint64_t seed,
                                        hipStream_t stream) {
-    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
-    if (num_seqs > kMaxSeqs || data_bytes >= (1ull << 62)) return KMC_ERR_INVALID_ARG;
-    if (flags & ~(KMC_CANON_SOFTMASK | KMC_CANON_FORWARD)) return KMC_ERR_INVALID_ARG;
+    if (int e = walk_check(k, num_seqs, data_bytes, flags)) return e;
     if (num_seqs == 0) return KMC_OK;
-    if (!indices || (data_bytes > 0 && !data)) return KMC_ERR_INVALID_ARG;
+    if (!walk_ptrs_ok(data, indices, data_bytes)) return KMC_ERR_INVALID_ARG;
     if (int e = index_check(index, index_bytes, layout_bytes(kMinSlots))) return e;
     int device = 0, cus = 0;
     if (int e = current_device_cus(&device, &cus)) return e;
-    // any `data` pointer: rounded down to 16 bytes, every offset moved up by the difference
-    const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
-    CArgs a;
-    a.data = data - mis;
-    a.idx = Offsets{indices, (int64_t)data_bytes, (int64_t)mis};
-    a.n = (int64_t)num_seqs;
-    a.k = k;
-    a.flags = flags;
-    a.G = walk_groups(data_bytes, cus);
-    a.seed = seed;
-    a.index = index;
-    a.index_bytes = index_bytes;
-    const bool fwd = flags & KMC_CANON_FORWARD, big = k >= 16;
-    const dim3 g((unsigned)a.G), b(kBlock);
-    if (fwd) {
-        if (big) hipLaunchKernelGGL((screen_count_kernel<true, true>), g, b, 0, stream, a);
-        else hipLaunchKernelGGL((screen_count_kernel<true, false>), g, b, 0, stream, a);
-    } else {
-        if (big) hipLaunchKernelGGL((screen_count_kernel<false, true>), g, b, 0, stream, a);
-        else hipLaunchKernelGGL((screen_count_kernel<false, false>), g, b, 0, stream, a);
-    }
+    const CArgs a{walk_args(data, indices, num_seqs, data_bytes, k, flags, cus), seed, index, index_bytes};
+    for_walk(flags, k, [&](auto fwd, auto big) {
+        hipLaunchKernelGGL((screen_count_kernel<decltype(fwd)::value, decltype(big)::value>), dim3((unsigned)a.w.G),
+                           dim3(kBlock), 0, stream, a);
+    });
     return (int)hipGetLastError();
 }
 

@@ -26,9 +26,9 @@
 //            [widx[gofs[g]], widx[gofs[g + 1]]).  Conservative: a non-empty span may
 //            hold no window, and telling so would cost a scan of the group's records.
 //
-//   prep    widx[r] = clamp(indices[r], 0, data_bytes) + (data & 15): the offsets
-//           over the 16-byte aligned buffer, as the canonical counter's host does;
-//           gofs for Groups
+//   prep    widx[r] = clamp(indices[r], 0, data_bytes) + (data & 15) (Offsets of
+//           kmc_sketch_walk.h): the offsets over the 16-byte aligned buffer, as the
+//           canonical counter's host does; gofs for Groups
 //   fill    size 0 and a row of UINT64_MAX for every unit that neither the cut merge
 //           (a span over a cut) nor the walk (an exact, non-empty span) is certain to
 //           write: the records of no window; every group inside one range, of which
@@ -36,7 +36,8 @@
 //           LDS.  A record with a window is never filled: no row is written twice.
 //   walk    G workgroups; workgroup w walks cpw = ceil(chunks / G) 16-byte chunks of
 //           the units' records (both ends read on the device), record piece by piece
-//           (walk_piece, the one chunk loop).  A valid window with hash h is a
+//           (walk_piece, a body of for_each_chunk of kmc_sketch_walk.h, the chunk loop
+//           of all three walks).  A valid window with hash h is a
 //           candidate iff the set is not full or h < T (T: the set's largest value
 //           once it holds s), and h is not in the set (a binary search, so a repeated
 //           key is staged once per merge at most and low-complexity input costs
@@ -110,14 +111,8 @@ constexpr int kStage = kBlock;
 constexpr int kWaves = kBlock / 64;
 
 struct Args {
-    const char *data;        // rounded down to 16 bytes
-    const int64_t *indices;  // the caller's
-    int64_t *widx;           // [n + 1] offsets over `data`
-    int64_t n;
-    int64_t data_bytes, mis;
-    int k;
-    uint32_t flags;
-    int G;
+    WalkArgs w;     // (w.idx: the caller's offsets, read by prep only)
+    int64_t *widx;  // [n + 1] offsets over w.data
     uint32_t s;
     uint64_t seed;
     uint64_t *part;   // [2 G][s]
@@ -150,16 +145,16 @@ struct MArgs {  // kmc_sketch_merge_groups
 //   unit_of     the unit of record R, at or after unit `from`; end: its records end
 struct Records {
     static constexpr bool kExactSpan = true;
-    static __device__ __forceinline__ int64_t count(const Args &a) { return a.n; }
+    static __device__ __forceinline__ int64_t count(const Args &a) { return a.w.n; }
     static __device__ __forceinline__ void records(const Args &a, int64_t &r0, int64_t &r1) {
         r0 = 0;
-        r1 = a.n;
+        r1 = a.w.n;
     }
     static __device__ __forceinline__ int64_t start(const Args &a, int64_t u) { return a.widx[u]; }
     static __device__ __forceinline__ void bytes(const Args &a, int64_t u, int64_t &gs, int64_t &ge) {
         const int64_t ra = a.widx[u], re = a.widx[u + 1];
         gs = ra;
-        ge = ra + (re - ra - a.k > 0 ? re - ra - a.k : 0);
+        ge = ra + (re - ra - a.w.k > 0 ? re - ra - a.w.k : 0);
     }
     static __device__ __forceinline__ int64_t unit_of(const Args &, int64_t R, int64_t) { return R; }
     static __device__ __forceinline__ int64_t end(const Args &, int64_t u) { return u + 1; }
@@ -199,20 +194,7 @@ template <class Units>
 __device__ __forceinline__ Walk make_walk(const Args &a) {
     int64_t r0, r1;
     Units::records(a, r0, r1);
-    Walk W;
-    W.data = a.data;
-    W.idx = a.widx + r0;
-    W.n = r1 - r0;
-    W.lo = a.widx[r0];
-    W.hi = a.widx[r1];
-    if (W.hi < W.lo) W.hi = W.lo;
-    W.k = a.k;
-    W.flags = a.flags;
-    W.c_lo = W.lo >> 4;
-    const int64_t chunks = W.hi > W.lo ? ((W.hi + 15) >> 4) - W.c_lo : 0;
-    const int64_t cpw = (chunks + a.G - 1) / a.G;
-    W.cpw = cpw > 1 ? cpw : 1;
-    return W;
+    return walk_of<const int64_t *>(a.w.data, a.widx + r0, r1 - r0, a.w.k, a.w.flags, a.w.G);
 }
 
 // The span of unit u clipped to the walked bytes; empty: ge <= gs.
@@ -244,16 +226,12 @@ __device__ __forceinline__ void span_ranges(const Walk &W, int G, const Span &S,
 
 // ng < 0: no groups
 __global__ __launch_bounds__(256) void sketch_prep_kernel(Args a) {
-    const int64_t top = a.n > a.ng ? a.n : a.ng;
+    const int64_t top = a.w.n > a.ng ? a.w.n : a.ng;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i <= top; i += (int64_t)gridDim.x * 256) {
-        if (i <= a.n) {
-            int64_t x = a.indices[i];
-            x = x < 0 ? 0 : (x > a.data_bytes ? a.data_bytes : x);
-            a.widx[i] = x + a.mis;
-        }
+        if (i <= a.w.n) a.widx[i] = a.w.idx[i];
         if (i <= a.ng) {
             const int64_t x = a.group_offsets[i];
-            a.gofs[i] = x < 0 ? 0 : (x > a.n ? a.n : x);
+            a.gofs[i] = x < 0 ? 0 : (x > a.w.n ? a.w.n : x);
         }
     }
 }
@@ -386,14 +364,8 @@ template <bool FWD, bool BIGK, int CAP>
 __device__ __forceinline__ void walk_piece(SetLds<CAP> &L, const Walk &W, const HashOf hf, int64_t ps, int64_t pe,
                                            int64_t rend, int s, int &m, uint32_t &staged, uint64_t &T, int &ci) {
     const int tid = threadIdx.x;
-    const int64_t c0 = ps >> 4, c1 = ((pe - 1) >> 4) + 1;
-    ChunkRaw nx = chunk_raw(W, (c0 + tid) << 4);
-    for (int64_t cb = c0; cb < c1; cb += kBlock) {
-        const int64_t c = cb + tid;
-        unsigned long long h[16];
-        const ChunkRaw cr = nx;
-        nx = chunk_raw(W, (c + kBlock) << 4);  // next round's chunk
-        uint32_t pend = chunk_keys<FWD, BIGK>(W, cr, c << 4, ps, pe, rend, hf, h);  // (past the piece: 0)
+    // (entered by every thread in every round, pend == 0 included: the barriers below)
+    for_each_chunk<FWD, BIGK>(W, ps, pe, rend, hf, [&](const unsigned long long(&h)[16], uint32_t pend) {
         for (;;) {
             const bool full = m == s;
             uint32_t cm = 0u;
@@ -435,7 +407,7 @@ __device__ __forceinline__ void walk_piece(SetLds<CAP> &L, const Walk &W, const 
             staged = 0;
             if (total == (uint32_t)kStage) break;  // (else some lanes still hold candidates)
         }
-    }
+    });
 }
 
 // Size 0 and a row of UINT64_MAX, before the walk, for every unit whose row neither
@@ -449,7 +421,7 @@ __global__ __launch_bounds__(256) void sketch_fill_kernel(Args a) {
         if (S.any()) {
             if (Units::kExactSpan) continue;  // the walk meets a window of it
             int64_t w0, w1;
-            span_ranges(W, a.G, S, w0, w1);
+            span_ranges(W, a.w.G, S, w0, w1);
             if (w1 > w0) continue;  // the cut merge's
         }
         uint64_t *row = a.sketches + u * (int64_t)s;
@@ -526,7 +498,7 @@ __global__ __launch_bounds__(kBlock) void sketch_cut_merge_kernel(Args a) {
     const Span S = unit_span<Units>(W, a, u);
     if (S.gs >= cut || S.ge <= cut) return;  // nothing before the cut, or nothing from it on
     int64_t w0, w1;
-    span_ranges(W, a.G, S, w0, w1);
+    span_ranges(W, a.w.G, S, w0, w1);
     if (w0 != b) return;  // an earlier cut's workgroup has the unit
     int m = 0;
     uint64_t T = kFill;
@@ -579,15 +551,13 @@ inline SLayout layout(void *base, int64_t n, int G, uint32_t s, int64_t ng = -1)
 }
 
 inline bool seq_args_ok(uint64_t num_seqs, uint64_t data_bytes, uint32_t sketch_size) {
-    return sketch_size_ok(sketch_size) && num_seqs <= kMaxSeqs && data_bytes < (1ull << 62);
+    return sketch_size_ok(sketch_size) && walk_sizes_ok(num_seqs, data_bytes);
 }
 
-// what both entry points refuse before anything else, in this order
+// what both entry points refuse before anything else: k, then every other argument
 inline int seq_check(int k, uint64_t num_seqs, uint64_t data_bytes, uint32_t sketch_size, unsigned flags) {
-    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
-    if (!seq_args_ok(num_seqs, data_bytes, sketch_size)) return KMC_ERR_INVALID_ARG;
-    if (flags & ~(KMC_CANON_SOFTMASK | KMC_CANON_FORWARD)) return KMC_ERR_INVALID_ARG;
-    return KMC_OK;
+    if (int e = walk_check(k, num_seqs, data_bytes, flags)) return e;
+    return sketch_size_ok(sketch_size) ? KMC_OK : KMC_ERR_INVALID_ARG;
 }
 
 DeviceCache q_ws;  // library-owned workspace
@@ -601,24 +571,14 @@ int sketch_units(const char *data, const int64_t *indices, uint64_t num_seqs, ui
     int device = 0, cus = 0;
     if (int e = current_device_cus(&device, &cus)) return e;
     const int64_t n = (int64_t)num_seqs;
-    const int G = walk_groups(data_bytes, cus);
+    Args a;
+    a.w = walk_args(data, indices, num_seqs, data_bytes, k, flags, cus);  // (the offsets' rule: applied by prep)
+    const int G = a.w.G;
     SLayout L;
     if (int e = bind_layout(q_ws, device, workspace, workspace_bytes, 8,
                             [&](void *b) { return layout(b, n, G, sketch_size, ng); }, &L))
         return e;
-    // any `data` pointer: rounded down to 16 bytes, every offset moved up by the
-    // difference (kmc_count_canonical_hash's rule, applied on the device by prep)
-    const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
-    Args a;
-    a.data = data - mis;
-    a.indices = indices;
     a.widx = L.widx;
-    a.n = n;
-    a.data_bytes = (int64_t)data_bytes;
-    a.mis = (int64_t)mis;
-    a.k = k;
-    a.flags = flags;
-    a.G = G;
     a.s = sketch_size;
     a.seed = seed;
     a.part = L.part;
@@ -634,15 +594,10 @@ int sketch_units(const char *data, const int64_t *indices, uint64_t num_seqs, ui
                        st, a);
     for_cap(sketch_size, [&](auto cap) {
         constexpr int CAP = decltype(cap)::value;
-        const bool fwd = flags & KMC_CANON_FORWARD, big = k >= 16;
         const dim3 g((unsigned)G), b(kBlock);
-        if (fwd) {
-            if (big) hipLaunchKernelGGL((sketch_walk_kernel<Units, true, true, CAP>), g, b, 0, st, a);
-            else hipLaunchKernelGGL((sketch_walk_kernel<Units, true, false, CAP>), g, b, 0, st, a);
-        } else {
-            if (big) hipLaunchKernelGGL((sketch_walk_kernel<Units, false, true, CAP>), g, b, 0, st, a);
-            else hipLaunchKernelGGL((sketch_walk_kernel<Units, false, false, CAP>), g, b, 0, st, a);
-        }
+        for_walk(flags, k, [&](auto fwd, auto big) {
+            hipLaunchKernelGGL((sketch_walk_kernel<Units, decltype(fwd)::value, decltype(big)::value, CAP>), g, b, 0, st, a);
+        });
         if (G > 1) hipLaunchKernelGGL((sketch_cut_merge_kernel<Units, CAP>), dim3((unsigned)G - 1), b, 0, st, a);
     });
     return (int)hipGetLastError();
@@ -673,8 +628,7 @@ extern "C" int kmc_sketch_from_sequences(const char *data, const int64_t *indice
                                          size_t workspace_bytes, hipStream_t stream) {
     if (int e = seq_check(k, num_seqs, data_bytes, sketch_size, flags)) return e;
     if (num_seqs == 0) return KMC_OK;
-    if (!indices || !sketches || !sketch_sizes) return KMC_ERR_INVALID_ARG;
-    if (data_bytes > 0 && !data) return KMC_ERR_INVALID_ARG;
+    if (!walk_ptrs_ok(data, indices, data_bytes) || !sketches || !sketch_sizes) return KMC_ERR_INVALID_ARG;
     return sketch_units<Records>(data, indices, num_seqs, data_bytes, nullptr, -1, k, flags, sketch_size, seed,
                                  sketches, sketch_sizes, workspace, workspace_bytes, stream);
 }
@@ -700,8 +654,7 @@ extern "C" int kmc_sketch_from_sequences_grouped(const char *data, const int64_t
     if (num_groups == 0) return KMC_OK;
     if (!group_offsets) return KMC_ERR_INVALID_ARG;
     if (num_seqs == 0) return KMC_OK;
-    if (!indices || !sketches || !sketch_sizes) return KMC_ERR_INVALID_ARG;
-    if (data_bytes > 0 && !data) return KMC_ERR_INVALID_ARG;
+    if (!walk_ptrs_ok(data, indices, data_bytes) || !sketches || !sketch_sizes) return KMC_ERR_INVALID_ARG;
     return sketch_units<Groups>(data, indices, num_seqs, data_bytes, group_offsets, (int64_t)num_groups, k, flags,
                                 sketch_size, seed, sketches, sketch_sizes, workspace, workspace_bytes, stream);
 }

@@ -1,15 +1,24 @@
-// kmc_sketch_walk.h — the geometry of the sketch path's walks over the record buffer,
-// shared by the direct sketcher (kmc_sketch_seq.hip), the screen
-// (kmc_sketch_screen.hip) and the abundance accumulator (kmc_sketch_accum.hip): the
-// workgroup shape, the number of ranges of a call, the walk's view for
-// kmc_canon_walk.h, the offsets read as they are clamped and the hash a window
-// stores.  One definition each, so that all walk the same bytes with the same launch.
+// kmc_sketch_walk.h — the sketch path's walks over the record buffer, shared by the
+// direct sketcher (kmc_sketch_seq.hip), the screen (kmc_sketch_screen.hip) and the
+// abundance accumulator (kmc_sketch_accum.hip).  One definition each, so that all walk
+// the same bytes with the same launch and a fix reaches all three:
+//   geometry   the workgroup shape, the number of ranges of a call, the walk's view for
+//              kmc_canon_walk.h, the offsets read as they are clamped, the hash a
+//              window stores
+//   device     for_each_chunk, the chunk loop of a record piece with its prefetch, and
+//              add_runs, one atomic add per run of equal values among a thread's windows
+//   host       the arguments every walk takes (WalkArgs, walk_args), the checks of the
+//              caller's input and for_walk, the dispatch on orientation and key width
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
+#include "kmc.h"
+#include "kmc_canon_walk.h"
 #include "kmc_internal.h"
+#include "kmc_sketch_pair.h"
 
 namespace kmc {
 namespace {
@@ -78,6 +87,54 @@ struct HashOf {
     __device__ __forceinline__ unsigned long long operator()(uint64_t key) const { return sketch_hash(key, seed); }
 };
 
+// The chunk loop of record piece [ps, pe) (for_each_piece of kmc_canon_walk.h): a
+// round is kBlock consecutive 16-byte chunks, one per thread, whose 48 bytes were
+// loaded a round ahead (chunk_raw: the next round's loads are issued before this
+// round's keys are made, so one chunk per thread stays in flight).  body(h, pend) gets
+// out(key) of the chunk's 16 windows and the mask of those that exist, in EVERY thread
+// in EVERY round, pend == 0 (past the piece) included: the trip count is the
+// workgroup's, so a body may hold a barrier.  A body with nothing to do returns.
+template <bool FWD, bool BIGK, class Idx, class Out, class Body>
+__device__ __forceinline__ void for_each_chunk(const WalkOf<Idx> &W, int64_t ps, int64_t pe, int64_t rend, Out out,
+                                               Body &&body) {
+    const int tid = threadIdx.x;
+    const int64_t c0 = ps >> 4, c1 = ((pe - 1) >> 4) + 1;
+    ChunkRaw nx = chunk_raw(W, (c0 + tid) << 4);
+    for (int64_t cb = c0; cb < c1; cb += kBlock) {
+        const int64_t c = cb + tid;
+        unsigned long long h[16];
+        const ChunkRaw cr = nx;
+        nx = chunk_raw(W, (c + kBlock) << 4);  // next round's chunk
+        body(h, chunk_keys<FWD, BIGK>(W, cr, c << 4, ps, pe, rend, out, h));  // (past the piece: 0)
+    }
+}
+
+// The windows of `pend` among a thread's 16, counted: equal neighbours are one run,
+// find(value) says where the value's count is kept (null: nowhere), and a run is one
+// relaxed agent-scope add of its length (a homopolymer run is one add of 16, not 16).
+template <class Find>
+__device__ __forceinline__ void add_runs(const unsigned long long (&v)[16], uint32_t pend, Find find) {
+    unsigned long long last = 0;
+    uint32_t *at = nullptr;
+    uint32_t run = 0u;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        if (!((pend >> j) & 1u)) continue;
+        if (run && v[j] == last) {
+            ++run;
+            continue;
+        }
+        if (run && at) __hip_atomic_fetch_add(at, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = v[j];
+        at = find(last);
+        run = 1u;
+    }
+    if (run && at) __hip_atomic_fetch_add(at, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------
 // walking workgroups: one range of at least kMinChunks chunks each over the chunks
 // data_bytes can hold (for any alignment of `data`), kWgPerCu per CU at most
 inline int walk_groups(uint64_t data_bytes, int cus) {
@@ -86,6 +143,57 @@ inline int walk_groups(uint64_t data_bytes, int cus) {
     uint64_t g = (chunks + kMinChunks - 1) / kMinChunks;
     if (g > cap) g = cap;
     return (int)(g < 1 ? 1 : g);
+}
+
+// What every walk's kernel takes of the caller's input.  Any `data` pointer: it is
+// rounded down to 16 bytes and every offset moved up by the difference
+// (kmc_count_canonical_hash's rule), as the offsets are read.
+struct WalkArgs {
+    const char *data;  // rounded down to 16 bytes
+    Offsets idx;       // [n + 1]
+    int64_t n;
+    int k;
+    uint32_t flags;
+    int G;
+};
+
+inline WalkArgs walk_args(const char *data, const int64_t *indices, uint64_t num_seqs, uint64_t data_bytes, int k,
+                          unsigned flags, int cus) {
+    const uintptr_t mis = reinterpret_cast<uintptr_t>(data) & 15u;
+    return WalkArgs{data - mis, Offsets{indices, (int64_t)data_bytes, (int64_t)mis}, (int64_t)num_seqs, k, flags,
+                    walk_groups(data_bytes, cus)};
+}
+
+__device__ __forceinline__ WalkOf<Offsets> walk_of(const WalkArgs &a) {
+    return walk_of(a.data, a.idx, a.n, a.k, a.flags, a.G);
+}
+
+// The checks of a walk's input, one definition each; an entry point applies them in
+// the order its contract states.
+inline bool walk_sizes_ok(uint64_t num_seqs, uint64_t data_bytes) {
+    return num_seqs <= kMaxSeqs && data_bytes < (1ull << 62);
+}
+inline bool walk_flags_ok(unsigned flags) { return !(flags & ~(KMC_CANON_SOFTMASK | KMC_CANON_FORWARD)); }
+inline bool walk_ptrs_ok(const char *data, const int64_t *indices, uint64_t data_bytes) {
+    return indices && (data_bytes == 0 || data);
+}
+// k, then the sizes, then the flags: what the sketcher and the screen refuse first
+inline int walk_check(int k, uint64_t num_seqs, uint64_t data_bytes, unsigned flags) {
+    if (!canon_k_ok(k)) return KMC_ERR_UNSUPPORTED_K;
+    return walk_sizes_ok(num_seqs, data_bytes) && walk_flags_ok(flags) ? KMC_OK : KMC_ERR_INVALID_ARG;
+}
+
+// f(FWD, BIGK), the orientation and the key width of a call as std::bool_constants (for_cap's style)
+template <class F>
+inline void for_walk(unsigned flags, int k, F &&f) {
+    const bool fwd = flags & KMC_CANON_FORWARD, big = k >= 16;
+    if (fwd) {
+        if (big) f(std::true_type{}, std::true_type{});
+        else f(std::true_type{}, std::false_type{});
+    } else {
+        if (big) f(std::false_type{}, std::true_type{});
+        else f(std::false_type{}, std::false_type{});
+    }
 }
 
 }  // namespace
