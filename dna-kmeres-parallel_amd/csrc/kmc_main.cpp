@@ -33,7 +33,9 @@
 // made, are grouped at Mash distance D (kmc_sketch_cluster -> clusters.tsv) instead of compared.
 // --pairs D: the pairs of sketches within Mash distance D with their counts and distances
 // (kmc_sketch_links -> pairs.tsv; with --query FILE kmc_sketch_links_rect -> query_pairs.tsv)
-// instead of every distance.
+// instead of every distance.  --recruit FILE: the input files are one k-mer set in the accumulator
+// and every record of FILE is matched against it (kmc_match_from_accum -> read_matches.tsv,
+// read_matches_summary.tsv).
 // GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
@@ -95,6 +97,10 @@ struct Options {
     bool cluster_set = false;
     double pairs = 0.0;  // --pairs D: the list of the pairs within Mash distance D instead of every distance
     bool pairs_set = false;
+    std::vector<std::string> recruit;  // --recruit FILE (repeatable): the reads matched against the inputs' k-mers
+    long min_hits = 1;                 // --min-hits H: a listed record has at least H hits
+    double min_fraction = 0.0;         // --min-fraction F: and hits >= F * sampled
+    bool min_hits_set = false, min_fraction_set = false;
 };
 
 // auto: FASTQ exactly when the name ends in .fq or .fastq, whatever the case
@@ -119,6 +125,8 @@ void usage(FILE *f) {
             "       kmc --canonical --sketch S --sketch-direct --per-file --spectrum B [--min-abundance auto] [options] <a.fastq> ...\n"
             "       kmc --canonical --sketch S [--sketch-direct] [--per-file] --cluster D [options] <input.fasta> ...\n"
             "       kmc --canonical --sketch S [--sketch-direct] [--per-file] --pairs D [--query q.fasta] [options] <input.fasta> ...\n"
+            "       kmc -k K --canonical --recruit reads.fastq [--recruit more.fq] [--min-abundance M] [--min-hits H]\n"
+            "           [--min-fraction F] --accum-slots L [--batch BYTES] [options] <host.fasta> <phage.fasta> ...\n"
             "       kmc synth OUT.fa RECORDS LENGTH [SEED]   (benchmark input, SURVEY.md 8(d))\n"
             "  -k K              k-mer length (default %d, the reference's K); dense path 1..%d,\n"
             "                    --canonical 1..%d\n"
@@ -245,6 +253,21 @@ void usage(FILE *f) {
             "                    written.  With --query FILE (and no --top): every query sketch against every\n"
             "                    reference sketch (kmc_sketch_links_rect), <out>/query_pairs.tsv with lines\n"
             "                    query<TAB>ref<TAB>shared<TAB>denom<TAB>distance sorted by (query, ref)\n"
+            "  --recruit FILE    with --canonical and --accum-slots L (repeatable): all input files are added to one\n"
+            "                    abundance accumulator of 2^L slots, the k-mer set (a FASTQ input batch by batch),\n"
+            "                    and every record of FILE is matched against it (kmc_match_from_accum; a FASTQ\n"
+            "                    FILE batch by batch, --batch).  <out>/read_matches.tsv gets, after a header line,\n"
+            "                    one line file<TAB>record<TAB>windows<TAB>sampled<TAB>hits per listed record, in file\n"
+            "                    order, then record order (record: 0-based within its file; windows: its valid\n"
+            "                    k-mers; sampled: those below the set's hash limit, all of them when the table held\n"
+            "                    every k-mer; hits: those in the set at least --min-abundance M times, default 1;\n"
+            "                    auto is refused).  <out>/read_matches_summary.tsv gets, after a header line, one line\n"
+            "                    per FILE: file, path, records, listed, limit, exact, sampled, hits.  A table that\n"
+            "                    held only the k-mers below a hash limit is no error: they are a uniform sample and\n"
+            "                    hits / sampled estimates the fraction; `exact` and `limit` say so.  Not with --sketch,\n"
+            "                    --screen, --query, --cluster, --pairs, --distances or --spectrum\n"
+            "  --min-hits H      with --recruit: a record is listed when hits >= H (default 1)\n"
+            "  --min-fraction F  with --recruit: and hits >= F * sampled, F in 0..1 (default 0)\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
@@ -376,6 +399,26 @@ int parse(int argc, char **argv, Options &o) {
                 fprintf(stderr, "kmc: --pairs takes a Mash distance in 0..1\n");
                 return usage(stderr), 2;
             }
+        } else if (a == "--recruit") {
+            o.recruit.push_back(next("--recruit"));
+        } else if (a == "--min-hits") {
+            char *end = nullptr;
+            const char *v = next("--min-hits");
+            o.min_hits = strtol(v, &end, 10);
+            o.min_hits_set = true;
+            if (end == v || *end != '\0' || o.min_hits < 0 || o.min_hits > (long)UINT32_MAX) {
+                fprintf(stderr, "kmc: --min-hits must be in 0..%u\n", UINT32_MAX);
+                return usage(stderr), 2;
+            }
+        } else if (a == "--min-fraction") {
+            char *end = nullptr;
+            const char *v = next("--min-fraction");
+            o.min_fraction = strtod(v, &end);
+            o.min_fraction_set = true;
+            if (end == v || *end != '\0' || !(o.min_fraction >= 0.0 && o.min_fraction <= 1.0)) {
+                fprintf(stderr, "kmc: --min-fraction takes a fraction in 0..1\n");
+                return usage(stderr), 2;
+            }
         } else if (a == "--softmask") {
             o.softmask = true;
         } else if (a == "--host-loader") {
@@ -391,11 +434,40 @@ int parse(int argc, char **argv, Options &o) {
         }
     }
     if (o.input.empty()) return usage(stderr), 2;
-    if (!o.more_inputs.empty() && !o.per_file) return fprintf(stderr, "kmc: more than one input file\n"), 2;
+    if (!o.more_inputs.empty() && !o.per_file && o.recruit.empty()) return fprintf(stderr, "kmc: more than one input file\n"), 2;
     if (o.dropin && o.k != KMC_DROPIN_K)
         return fprintf(stderr, "kmc: --dropin is the k = %d reference launch\n", KMC_DROPIN_K), 2;
     if (o.canonical ? (o.k < 1 || o.k > KMC_CANON_MAX_K) : (o.k < 1 || o.k > KMC_DENSE_MAX_K))
         return fprintf(stderr, "kmc: k = %d out of range\n", o.k), 2;
+    if ((o.min_hits_set || o.min_fraction_set) && o.recruit.empty()) {
+        fprintf(stderr, "kmc: --min-hits and --min-fraction select the lines of --recruit\n");
+        return usage(stderr), 2;
+    }
+    if (!o.recruit.empty()) {
+        if (!o.canonical) {
+            fprintf(stderr, "kmc: --recruit needs --canonical\n");
+            return usage(stderr), 2;
+        }
+        if (o.sketch > 0 || !o.screen.empty() || !o.query.empty() || o.cluster_set || o.pairs_set || o.canon_distances ||
+            o.spectrum > 0) {
+            fprintf(stderr, "kmc: --recruit matches reads against the k-mers of the input files: not with --sketch, "
+                            "--screen, --query, --cluster, --pairs, --distances or --spectrum\n");
+            return usage(stderr), 2;
+        }
+        if (o.min_abundance_auto) {
+            fprintf(stderr, "kmc: --recruit takes the count a k-mer needs as --min-abundance M: not --min-abundance auto\n");
+            return usage(stderr), 2;
+        }
+        if (!o.accum_slots_set || o.accum_slots == 0) {
+            fprintf(stderr, "kmc: --recruit needs --accum-slots L, the size of the k-mer set's table\n");
+            return usage(stderr), 2;
+        }
+        if (o.max_seqs_set && o.max_seqs > 0) {
+            fprintf(stderr, "kmc: --recruit reads every file whole: not with --max-seqs above 0\n");
+            return usage(stderr), 2;
+        }
+        o.max_seqs = 0;
+    }
     if ((o.sketch > 0 || o.min_count_set) && !o.canonical) {
         fprintf(stderr, "kmc: --sketch and --min-count need --canonical\n");
         return usage(stderr), 2;
@@ -416,7 +488,7 @@ int parse(int argc, char **argv, Options &o) {
         fprintf(stderr, "kmc: --per-file needs --canonical --sketch S --sketch-direct\n");
         return usage(stderr), 2;
     }
-    if (o.min_abundance > 0 && !o.per_file) {
+    if (o.min_abundance > 0 && !o.per_file && o.recruit.empty()) {
         fprintf(stderr, "kmc: --min-abundance needs --canonical --sketch S --sketch-direct --per-file\n");
         return usage(stderr), 2;
     }
@@ -432,7 +504,7 @@ int parse(int argc, char **argv, Options &o) {
         fprintf(stderr, "kmc: --spectrum reads every file whole: not with --max-seqs above 0\n");
         return usage(stderr), 2;
     }
-    if ((o.accum_slots_set || o.batch_set) && o.min_abundance == 0 && o.spectrum == 0) {
+    if ((o.accum_slots_set || o.batch_set) && o.min_abundance == 0 && o.spectrum == 0 && o.recruit.empty()) {
         fprintf(stderr, "kmc: --accum-slots and --batch shape the pass of --min-abundance or --spectrum\n");
         return usage(stderr), 2;
     }
@@ -491,6 +563,7 @@ int parse(int argc, char **argv, Options &o) {
         std::vector<std::string> files{o.input};
         files.insert(files.end(), o.more_inputs.begin(), o.more_inputs.end());
         files.insert(files.end(), o.screen.begin(), o.screen.end());
+        files.insert(files.end(), o.recruit.begin(), o.recruit.end());
         if (!o.query.empty()) files.push_back(o.query);
         for (const std::string &f : files)
             if (is_fastq(o, f))
@@ -820,6 +893,14 @@ uint32_t accum_log2_slots(const Options &o, uint32_t s) {
     return lg;
 }
 
+// the accumulator's level for `bytes` added to a table of 2^lg slots, the library's rule (kmc.h):
+// the smallest j with ceil(bytes / 2^j) <= 2^lg / 4; adds of no record do not count
+uint32_t accum_level(uint64_t bytes, uint32_t lg) {
+    uint32_t j = 0;
+    while (((bytes + ((1ull << j) - 1)) >> j) > (1ull << (lg - 2))) ++j;
+    return j;
+}
+
 // --per-file --min-abundance M: every file is one pass of the accumulator, reset in between;
 // a FASTQ file batch by batch, every add on st behind its batch's parse (the next batch's
 // writes are ordered behind that add), a FASTA file loaded whole and added in one call
@@ -898,8 +979,7 @@ int accum_files(const Options &o, const std::vector<std::string> &files, const c
         HIPCHK(hipMemcpyAsync(&size, d_sz + f, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(stats, d_stats.get(), sizeof stats, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));  // before the file's buffers go
-        uint32_t j = 0;  // the library's rule (kmc.h) for the bytes added
-        while (((bytes + ((1ull << j) - 1)) >> j) > (1ull << (lg - 2))) ++j;
+        const uint32_t j = accum_level(bytes, lg);
         if (!o.quiet) {
             printf("%s %zu: %s: %" PRIu64 " records, %" PRIu64 " batches, sketch size %u, j %u, complete %d", what, f,
                    path.c_str(), records, batches, size, j, (int)stats[0]);
@@ -956,6 +1036,138 @@ int sketch_files(const Options &o, const std::vector<std::string> &files, const 
         if (!o.quiet)
             printf("%s %zu: %s: %" PRIu64 " records, sketch size %u\n", what, f, files[f].c_str(), r.n, size);
     }
+    return 0;
+}
+
+// f(data, idx, records, bytes) over the batches of one file on st: a FASTQ file batch by
+// batch through the reader (the next batch's writes are ordered behind what f put on st), a
+// FASTA file loaded whole, one batch.  The batch's buffers live until f returns.
+template <class F>
+int for_each_batch(const Options &o, const std::string &path, hipStream_t st, uint64_t *batches, F &&f) {
+    *batches = 0;
+    if (is_fastq(o, path)) {
+        kmc_fastq_reader *rd = nullptr;
+        const int orc = kmc_fastq_open(path.c_str(), o.batch, &rd);
+        if (orc) return fprintf(stderr, "kmc: %s: %s\n", path.c_str(), kmc_error_string(orc)), 1;
+        const FastqReader reader(rd);
+        for (;;) {
+            const char *d_data = nullptr;
+            const int64_t *d_idx = nullptr;
+            uint64_t nb = 0, ns = 0;
+            const int rc = kmc_fastq_next(rd, &d_data, &nb, &d_idx, &ns, st);
+            if (rc == KMC_ERR_FORMAT) return malformed(path, ns);
+            KMCCHK(rc);
+            if (!d_data) break;
+            if (int e = f(d_data, d_idx, ns, nb)) return e;
+            ++*batches;
+        }
+        return 0;
+    }
+    Options of = o;
+    of.input = path;
+    of.quiet = true;
+    Records r;
+    if (int e = load(of, st, r)) return e;
+    *batches = 1;
+    return f(r.data.get(), r.idx.get(), r.n, r.bytes);
+}
+
+// --recruit: the input files are one k-mer set in the abundance accumulator; every record
+// of every --recruit file is matched against it, batch by batch on st
+int run_recruit(const Options &o, hipStream_t st) {
+    const unsigned flags = o.softmask ? KMC_CANON_SOFTMASK : 0u;
+    const uint32_t lg = (uint32_t)o.accum_slots, M = o.min_abundance > 0 ? (uint32_t)o.min_abundance : 1u;
+    kmc_sketch_accum *acc = nullptr;
+    KMCCHK(kmc_sketch_accum_create(1, o.k, flags, KMC_SKETCH_DEFAULT_SEED, lg, &acc));
+    const Accum accum(acc);
+    std::vector<std::string> files{o.input};
+    files.insert(files.end(), o.more_inputs.begin(), o.more_inputs.end());
+    uint64_t added = 0;  // the bytes of all adds: the level j is the library's rule for them (kmc.h)
+    for (size_t f = 0; f < files.size(); ++f) {
+        uint64_t records = 0, batches = 0;
+        const int e = for_each_batch(o, files[f], st, &batches,
+                                     [&](const char *d, const int64_t *idx, uint64_t ns, uint64_t nb) {
+            KMCCHK(kmc_sketch_accum_add(acc, d, idx, ns, nb, st));
+            HIPCHK(hipStreamSynchronize(st));  // before the batch's buffers go
+            records += ns;
+            if (ns > 0) added += nb;  // (the library leaves N as it is for a call of no record)
+            return 0;
+        });
+        if (e) return e;
+        if (!o.quiet)
+            printf("Set %zu: %s: %" PRIu64 " records, %" PRIu64 " batches\n", f, files[f].c_str(), records, batches);
+    }
+    // the level only says whether `limit` is its bound or a refused k-mer's hash (the warning below);
+    // limit and exact themselves are always the library's
+    const uint32_t j = accum_level(added, lg);
+    const uint64_t bound = j == 0 ? UINT64_MAX : 1ull << (64 - j);
+    File f_rec(fopen((o.out_dir + "/read_matches.tsv").c_str(), "w"));
+    File f_sum(fopen((o.out_dir + "/read_matches_summary.tsv").c_str(), "w"));
+    if (!f_rec || !f_sum) return fprintf(stderr, "kmc: cannot write %s/read_matches.tsv\n", o.out_dir.c_str()), 1;
+    fprintf(f_rec.get(), "file\trecord\twindows\tsampled\thits\n");
+    fprintf(f_sum.get(), "file\tpath\trecords\tlisted\tlimit\texact\tsampled\thits\n");
+    DevBuf<uint32_t> d_out;  // windows, sampled, hits of one batch: three arrays of `cap`
+    DevBuf<uint64_t> d_stats;
+    DevBuf<int64_t> d_none;  // the offsets of a call of no record
+    HIPCHK(dev_alloc(d_stats, 4));
+    HIPCHK(dev_alloc(d_out, 3));  // (never null: a batch or a file may hold no record)
+    HIPCHK(dev_alloc(d_none, 1));
+    HIPCHK(hipMemsetAsync(d_none.get(), 0, sizeof(int64_t), st));
+    uint64_t cap = 1;
+    std::vector<uint32_t> out;
+    // what the set is, for a file of no batch: the stats of a match of no record
+    uint64_t of_set[4] = {0, 0, 0, 0};
+    KMCCHK(kmc_match_from_accum(acc, nullptr, d_none.get(), 0, 0, M, nullptr, nullptr, d_out.get(), d_stats.get(), st));
+    HIPCHK(hipMemcpyAsync(of_set, d_stats.get(), sizeof of_set, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    bool lost = false;
+    for (size_t f = 0; f < o.recruit.size(); ++f) {
+        uint64_t records = 0, listed = 0, batches = 0;
+        uint64_t total[4] = {of_set[0], of_set[1], 0, 0};
+        const int e = for_each_batch(o, o.recruit[f], st, &batches,
+                                     [&](const char *d, const int64_t *idx, uint64_t ns, uint64_t nb) {
+            if (ns > cap) {
+                HIPCHK(dev_alloc(d_out, 3 * ns));
+                cap = ns;
+            }
+            uint32_t *d_win = d_out.get(), *d_smp = d_win + cap, *d_hit = d_smp + cap;
+            KMCCHK(kmc_match_from_accum(acc, d, idx, ns, nb, M, d_win, d_smp, d_hit, d_stats.get(), st));
+            out.resize(3 * ns);
+            uint64_t stats[4] = {0, 0, 0, 0};
+            if (ns > 0) {
+                HIPCHK(hipMemcpyAsync(out.data(), d_win, ns * 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(out.data() + ns, d_smp, ns * 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(out.data() + 2 * ns, d_hit, ns * 4, hipMemcpyDeviceToHost, st));
+            }
+            HIPCHK(hipMemcpyAsync(stats, d_stats.get(), sizeof stats, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));  // before the batch's buffers go
+            total[0] = stats[0];
+            total[1] = stats[1];
+            total[2] += stats[2];
+            total[3] += stats[3];
+            for (uint64_t r = 0; r < ns; ++r) {
+                const uint32_t win = out[r], smp = out[ns + r], hit = out[2 * ns + r];
+                if (hit >= (uint64_t)o.min_hits && (double)hit >= o.min_fraction * (double)smp) {
+                    fprintf(f_rec.get(), "%zu\t%" PRIu64 "\t%u\t%u\t%u\n", f, records + r, win, smp, hit);
+                    ++listed;
+                }
+            }
+            records += ns;
+            return 0;
+        });
+        if (e) return e;
+        fprintf(f_sum.get(), "%zu\t%s\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t%d\t%" PRIu64 "\t%" PRIu64 "\n", f,
+                o.recruit[f].c_str(), records, listed, total[1], (int)total[0], total[2], total[3]);
+        if (!o.quiet)
+            printf("Recruit %zu: %s: %" PRIu64 " records, %" PRIu64 " batches, %" PRIu64 " listed, j %u, exact %d\n", f,
+                   o.recruit[f].c_str(), records, batches, listed, j, (int)total[0]);
+        lost = lost || total[1] < bound;
+    }
+    if (lost)
+        fprintf(stderr, "kmc: the table of 2^%u slots refused k-mers: the set is the sample below a smaller hash limit "
+                        "than its level's (read_matches_summary.tsv); raise --accum-slots to keep more\n", lg);
+    if ((fclose(f_rec.release()) != 0) | (fclose(f_sum.release()) != 0))
+        return fprintf(stderr, "kmc: cannot write %s/read_matches.tsv\n", o.out_dir.c_str()), 1;
     return 0;
 }
 
@@ -1320,6 +1532,7 @@ int run(const Options &o) {
     const Stream st(s);
     if (!o.query.empty()) return run_query(o, s);
     if (!o.screen.empty()) return run_screen(o, s);
+    if (!o.recruit.empty()) return run_recruit(o, s);
     if (o.per_file) return run_per_file(o, s);
     Records r;  // (after the stream: released before it)
     if (int e = load(o, s, r)) return e;

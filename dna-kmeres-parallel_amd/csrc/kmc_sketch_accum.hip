@@ -65,6 +65,24 @@
 //           and its entry count and count sum to the header's `spec` words, once.  It
 //           writes hist, stats and `spec` only.
 //
+//   match   kmc_match_from_accum: per record, how many of its windows are valid, how
+//           many of those are sampled (all of them, or hash < the same `limit`) and how
+//           many of those are in the active table with count >= min_count.  The table is
+//           only read.  A lookup probes from hash & mask and ends at the first empty slot
+//           or after kChain probes; that is exact, because insertion (add and purge
+//           alike) never places a key further than that from its slot and past no empty
+//           slot, and nothing is ever deleted from a table in place: a key that is in the
+//           table is found, and a key below `limit` that was added is in the table.
+//           The unit that owns a record piece is a WAVE (for_each_wave_piece and
+//           for_each_wave_chunk of kmc_sketch_walk.h): the call's chunk range is cut
+//           into G * kBlock / 64 ranges, a round is 64 chunks, and a piece ends with a
+//           wave reduction of three popcounts, no barrier and no LDS.  The outputs are
+//           cleared on the stream first; the wave's first lane stores a record's three
+//           numbers when the record lies wholly in its range and adds them with vector
+//           atomics when the record is cut between waves.  Equal neighbouring keys among
+//           a lane's sampled windows are one probe (add_runs' rule), and stats[2..3]
+//           take one 64-bit add per wave.
+//
 // The device code trusts the host arguments only: every slot index is masked, every
 // chain is bounded by kChain <= C, the list's cursor is checked against C.
 //
@@ -349,6 +367,109 @@ __global__ void accum_spectrum_stats_kernel(SArgs a) {
     a.stats[3] = a.hd->spec[1];
 }
 
+// ---------------------------------------------------------------------------
+// match
+// ---------------------------------------------------------------------------
+struct MArgs {
+    WalkArgs w;
+    uint64_t seed, maxh;
+    uint32_t j, min_count;
+    const Header *hd;
+    const unsigned long long *keys;  // the active table
+    const uint32_t *counts;
+    uint32_t mask, chain;
+    uint32_t *windows, *sampled, *hits;  // [n], cleared; windows and sampled may be null
+    unsigned long long *stats;           // [4] or null; [2] and [3] cleared
+};
+
+// whether the table holds `key` (hash h) with a count of at least m: the chain from the
+// key's slot to the first empty slot, kChain probes at most
+__device__ __forceinline__ bool table_has(const MArgs &a, unsigned long long key, unsigned long long h, uint32_t m) {
+    uint32_t i = (uint32_t)h & a.mask;
+    for (uint32_t step = 0; step < a.chain; ++step) {
+        const unsigned long long x = a.keys[i];
+        if (x == key) return a.counts[i] >= m;
+        if (x == kFill) return false;
+        i = (i + 1) & a.mask;
+    }
+    return false;
+}
+
+// one record's word: no other wave has a piece of the record (a plain store over the
+// cleared word), or a relaxed agent-scope add
+__device__ __forceinline__ void credit(uint32_t *out, int64_t r, uint32_t v, bool whole) {
+    if (!out) return;
+    if (whole) out[r] = v;
+    else if (v) __hip_atomic_fetch_add(out + r, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <bool FWD, bool BIGK>
+__global__ __launch_bounds__(kBlock) void accum_match_kernel(MArgs a) {
+    const Walk W = wave_walk_of(a.w);
+    bool all;
+    const unsigned long long limit = limit_of(a, &all);
+    const uint32_t m = a.min_count > 1 ? a.min_count : 1u;
+    const bool first = (threadIdx.x & (kWave - 1)) == 0;
+    unsigned long long tot_s = 0ull, tot_h = 0ull;  // this lane's share of the wave's sums
+    for_each_wave_piece(W, [&](int64_t r, int64_t ps, int64_t pe, int64_t rend, bool whole) {
+        uint32_t nv = 0u, ns = 0u, nh = 0u;
+        for_each_wave_chunk<FWD, BIGK>(W, ps, pe, rend, KeyOf{}, [&](const unsigned long long(&key)[16], uint32_t pend) {
+            if (!pend) return;
+            uint32_t sm = pend;
+            if (!all) {
+                uint32_t cm = 0u;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) cm |= (uint32_t)(sketch_hash(key[j], a.seed) < limit) << j;
+                sm &= cm;
+            }
+            // the sampled windows that are hits: equal neighbours are one run, one probe
+            uint32_t hm = 0u;
+            unsigned long long last = 0ull;
+            bool run = false, hit = false;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                if (!((sm >> j) & 1u)) continue;
+                if (!(run && key[j] == last)) {
+                    last = key[j];
+                    hit = table_has(a, last, sketch_hash(last, a.seed), m);
+                    run = true;
+                }
+                hm |= (uint32_t)hit << j;
+            }
+            nv += __popc(pend);
+            ns += __popc(sm);
+            nh += __popc(hm);
+        });
+        tot_s += ns;
+        tot_h += nh;
+        const uint32_t v = a.windows ? wave_sum(nv) : 0u, s = a.sampled ? wave_sum(ns) : 0u, h = wave_sum(nh);
+        if (first) {
+            credit(a.windows, r, v, whole);
+            credit(a.sampled, r, s, whole);
+            credit(a.hits, r, h, whole);
+        }
+    });
+    if (a.stats) {  // one add per wave and word
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+            tot_s += __shfl_xor(tot_s, off, kWave);
+            tot_h += __shfl_xor(tot_h, off, kWave);
+        }
+        if (first && tot_s) atomicAdd(a.stats + 2, tot_s);
+        if (first && tot_h) atomicAdd(a.stats + 3, tot_h);
+    }
+}
+
+// stats of a match before its walk: {all, limit, 0, 0}
+__global__ void accum_match_stats_kernel(MArgs a) {
+    bool all;
+    const unsigned long long limit = limit_of(a, &all);
+    a.stats[0] = all ? 1u : 0u;
+    a.stats[1] = limit;
+    a.stats[2] = 0ull;
+    a.stats[3] = 0ull;
+}
+
 inline unsigned slot_grid(uint64_t C) {
     const uint64_t b = (C + kSlotBlock - 1) / kSlotBlock;
     return (unsigned)(b < 4096 ? b : 4096);
@@ -532,6 +653,45 @@ extern "C" int kmc_spectrum_from_accum(kmc_sketch_accum *a, uint32_t num_bins, u
     hipLaunchKernelGGL(accum_spectrum_kernel, dim3(slot_grid(C)), dim3(kSlotBlock), (size_t)num_bins * 4, stream, g);
     if (hipError_t he = hipGetLastError()) return (int)he;
     if (stats) hipLaunchKernelGGL(accum_spectrum_stats_kernel, dim3(1), dim3(1), 0, stream, g);
+    return (int)hipGetLastError();
+}
+
+extern "C" int kmc_match_from_accum(kmc_sketch_accum *a, const char *data, const int64_t *indices, uint64_t num_seqs,
+                                    uint64_t data_bytes, uint32_t min_count, uint32_t *windows, uint32_t *sampled,
+                                    uint32_t *hits, uint64_t *stats, hipStream_t stream) {
+    if (!a || !hits || num_seqs > kMaxSeqs) return KMC_ERR_INVALID_ARG;
+    if (!walk_ptrs_ok(data, indices, data_bytes) || !walk_sizes_ok(num_seqs, data_bytes)) return KMC_ERR_INVALID_ARG;
+    MArgs g;
+    g.seed = a->seed;
+    g.maxh = max_hash(a->j);
+    g.j = a->j;
+    g.min_count = min_count;
+    g.hd = a->L.hd;
+    g.keys = a->L.keys[a->active];
+    g.counts = a->L.counts[a->active];
+    const Table T = table_of(a, a->active);
+    g.mask = T.mask;
+    g.chain = T.chain;
+    g.windows = windows;
+    g.sampled = sampled;
+    g.hits = hits;
+    g.stats = reinterpret_cast<unsigned long long *>(stats);
+    g.w = WalkArgs{};
+    if (stats) {
+        hipLaunchKernelGGL(accum_match_stats_kernel, dim3(1), dim3(1), 0, stream, g);
+        if (hipError_t he = hipGetLastError()) return (int)he;
+    }
+    if (num_seqs == 0) return KMC_OK;
+    int device = 0, cus = 0;
+    if (int e = current_device_cus(&device, &cus)) return e;
+    g.w = walk_args(data, indices, num_seqs, data_bytes, a->k, a->flags, cus);
+    for (uint32_t *out : {windows, sampled, hits})
+        if (out)
+            if (hipError_t he = hipMemsetAsync(out, 0, (size_t)num_seqs * 4, stream)) return (int)he;
+    for_walk(a->flags, a->k, [&](auto fwd, auto big) {
+        hipLaunchKernelGGL((accum_match_kernel<decltype(fwd)::value, decltype(big)::value>), dim3((unsigned)g.w.G),
+                           dim3(kBlock), 0, stream, g);
+    });
     return (int)hipGetLastError();
 }
 

@@ -7,6 +7,9 @@
 //              window stores
 //   device     for_each_chunk, the chunk loop of a record piece with its prefetch, and
 //              add_runs, one atomic add per run of equal values among a thread's windows
+//              for_each_wave_piece and for_each_wave_chunk, the same two loops with a wave
+//              as the unit that owns a record piece (the per-record match of the
+//              abundance accumulator)
 //   host       the arguments every walk takes (WalkArgs, walk_args), the checks of the
 //              caller's input and for_walk, the dispatch on orientation and key width
 #pragma once
@@ -133,6 +136,74 @@ __device__ __forceinline__ void add_runs(const unsigned long long (&v)[16], uint
 }
 
 // ---------------------------------------------------------------------------
+// the wave as the unit (the per-record walks: a piece of a 150-base read fills 10 of
+// a wave's 64 lanes, not 10 of a workgroup's 1024)
+// ---------------------------------------------------------------------------
+constexpr int kWave = 64;
+constexpr int kWavesPerBlock = kBlock / kWave;  // the units of a workgroup: 16 / 1
+
+// a 64-bit value of the wave's first lane, in every lane (and in scalar registers)
+__device__ __forceinline__ int64_t wave_first(int64_t x) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
+    return (int64_t)((uint64_t)lo | ((uint64_t)hi << 32));
+}
+
+// the sum of x over the wave's lanes, in every lane
+__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, kWave);
+    return x;
+}
+
+// for_each_piece of kmc_canon_walk.h with the wave as the unit: the wave's chunk range
+// and its record pieces, f(r, ps, pe, rend, whole); whole: the piece is all of the
+// record's windows, so no other wave has a piece of r.  The first record is found by
+// the wave's first lane and broadcast; r, ps, pe and rend are the same in every lane.
+// No barrier and no LDS: the waves of a workgroup do not wait for each other.
+template <class P, class F>
+__device__ __forceinline__ void for_each_wave_piece(const P &p, F &&f) {
+    const int64_t u = (int64_t)blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const int64_t cb = p.c_lo + u * p.cpw;
+    const int64_t wlo = std::max<int64_t>(cb << 4, p.lo), whi = std::min<int64_t>((cb + p.cpw) << 4, p.hi);
+    if (wlo >= whi) return;
+    int64_t a = 0;
+    if ((threadIdx.x & (kWave - 1)) == 0) {  // last record r with idx[r] <= wlo
+        int64_t b = p.n - 1;
+        while (a < b) {
+            const int64_t m = (a + b + 1) >> 1;
+            if (p.idx[m] <= wlo) a = m; else b = m - 1;
+        }
+    }
+    for (int64_t r = wave_first(a); r < p.n; ++r) {
+        const int64_t s = p.idx[r], e = p.idx[r + 1];
+        if (s >= whi) break;
+        const int64_t nw = e - s - p.k > 0 ? e - s - p.k : 0;
+        const int64_t ps = std::max(s, wlo), pe = std::min(s + nw, whi);
+        if (ps >= pe) continue;
+        f(r, ps, pe, e, ps == s && pe == s + nw);
+    }
+}
+
+// for_each_chunk with the wave as the unit: a round is kWave consecutive chunks, one
+// per lane, loaded a round ahead; body(h, pend) in every lane in every round of the
+// wave's own trip count.
+template <bool FWD, bool BIGK, class Idx, class Out, class Body>
+__device__ __forceinline__ void for_each_wave_chunk(const WalkOf<Idx> &W, int64_t ps, int64_t pe, int64_t rend, Out out,
+                                                    Body &&body) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t c0 = ps >> 4, c1 = ((pe - 1) >> 4) + 1;
+    ChunkRaw nx = chunk_raw(W, (c0 + lane) << 4);
+    for (int64_t cb = c0; cb < c1; cb += kWave) {
+        const int64_t c = cb + lane;
+        unsigned long long h[16];
+        const ChunkRaw cr = nx;
+        if (cb + kWave < c1) nx = chunk_raw(W, (c + kWave) << 4);  // next round's chunk (wave-uniform)
+        body(h, chunk_keys<FWD, BIGK>(W, cr, c << 4, ps, pe, rend, out, h));  // (past the piece: 0)
+    }
+}
+
+// ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
 // walking workgroups: one range of at least kMinChunks chunks each over the chunks
@@ -166,6 +237,12 @@ inline WalkArgs walk_args(const char *data, const int64_t *indices, uint64_t num
 
 __device__ __forceinline__ WalkOf<Offsets> walk_of(const WalkArgs &a) {
     return walk_of(a.data, a.idx, a.n, a.k, a.flags, a.G);
+}
+
+// the same view cut into one range per WAVE of the G workgroups (for_each_wave_piece:
+// W.cpw is a wave's chunks)
+__device__ __forceinline__ WalkOf<Offsets> wave_walk_of(const WalkArgs &a) {
+    return walk_of(a.data, a.idx, a.n, a.k, a.flags, a.G * kWavesPerBlock);
 }
 
 // The checks of a walk's input, one definition each; an entry point applies them in

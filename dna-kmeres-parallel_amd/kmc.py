@@ -267,6 +267,7 @@ def _load(path):
     L.kmc_sketch_accum_free.argtypes = [_P]
     L.kmc_sketch_accum_free.restype = None
     L.kmc_spectrum_from_accum.argtypes = [_P, ctypes.c_uint32, _P, _P, _P]
+    L.kmc_match_from_accum.argtypes = [_P, _P, _P, _U64, _U64, ctypes.c_uint32, _P, _P, _P, _P, _P]
     L.kmc_spectrum_summarize.argtypes = [_P, ctypes.c_uint32, _U64, ctypes.POINTER(SpectrumSummary)]
     L.minKmeres2_hip.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.kmc_count_canonical_hash.argtypes = [_P, _P, _U64, ctypes.c_int, ctypes.c_uint, _P, _P, _U64, _P,
@@ -878,7 +879,9 @@ class SketchAccum:
     (row int64 [s]: uint64 hashes ascending, then all-ones fill; size int32 [1];
     stats int64 [4]: complete, limit, tracked, qualifying, or None) and leaves the
     accumulator as it is; spectrum(num_bins) gives the abundance spectrum of what was
-    added (kmc_spectrum_from_accum), and leaves it as it is too; reset() empties it.  `log2_slots`: the table's size, 0 for
+    added (kmc_spectrum_from_accum), and leaves it as it is too; match(data, indices)
+    says per record how many of its k-mers are among what was added
+    (kmc_match_from_accum), and leaves it as it is too; reset() empties it.  `log2_slots`: the table's size, 0 for
     the default (kmc.h).  The handle belongs to the library it was created in.
 
         with kmc.SketchAccum(1000, 21) as acc:
@@ -942,6 +945,39 @@ class SketchAccum:
         _check(self._lib.kmc_spectrum_from_accum(h, int(num_bins), _dptr(hist), _dptr(st), _stream(stream)),
                "kmc_spectrum_from_accum")
         return hist, st
+
+    def match(self, data, indices, min_count=1, windows=True, sampled=True, stats=True, data_bytes=None, out=None,
+              stream=None):
+        """kmc_match_from_accum: per record of (data, indices: as add) how many of its
+        windows are valid, how many of those are sampled (all of them when the table
+        held everything, else those with a hash below the limit finish() reports) and
+        how many of those are in the set with count >= min_count.  Returns (windows,
+        sampled, hits: int32 [n] holding uint32 numbers; stats int64 [4]: exact, limit,
+        sum of sampled, sum of hits), with None for what was not asked for.  It leaves
+        the accumulator as it is.  `windows`, `sampled`: True for a new tensor, False or
+        None for none, or the caller's own int32 tensor [n]; `stats`: the same with an
+        int64 tensor [4]; `out`: the caller's own hits."""
+        import torch
+        h = self._handle()
+        n = int(indices.numel() - 1)
+        if data_bytes is None:
+            data_bytes = data.numel()
+        with _on(stream):
+            dv = torch.device("cuda", torch.cuda.current_device())
+
+            def take(want, count, dtype):
+                if isinstance(want, torch.Tensor):
+                    return want
+                return torch.empty(max(count, 0), dtype=dtype, device=dv) if want else None
+            win, smp = take(windows, n, torch.int32), take(sampled, n, torch.int32)
+            hit = out if out is not None else take(True, n, torch.int32)
+            st = take(stats, 4, torch.int64)
+            # (no record: an empty tensor has no address, and the library refuses a null hits; nothing is written there)
+            hits_at = hit if hit.numel() else torch.empty(1, dtype=torch.int32, device=dv)
+        _check(self._lib.kmc_match_from_accum(h, _dptr(data), _dptr(indices), n, int(data_bytes), int(min_count),
+                                              _dptr(win), _dptr(smp), _dptr(hits_at), _dptr(st), _stream(stream)),
+               "kmc_match_from_accum")
+        return win, smp, hit, st
 
     def reset(self, stream=None):
         _check(self._lib.kmc_sketch_accum_reset(self._handle(), _stream(stream)), "kmc_sketch_accum_reset")

@@ -929,6 +929,48 @@ KMC_API int kmc_spectrum_summarize(const uint64_t *hist, uint32_t num_bins, uint
                                    kmc_spectrum_summary *out);
 
 /* ------------------------------------------------------------------------ */
+/* Matching records against everything added to an accumulator, per record: how many
+ * of a read's k-mers are in the set (read recruitment, host or contaminant depletion,
+ * reads made of k-mers seen once).  The accumulator is an exact counted k-mer set: it
+ * holds every canonical key with a hash below limit with its exact count, so with
+ * `all` the fraction hits / windows of a record is exact, and otherwise the table is a
+ * uniform sample of the k-mers at rate limit / 2^64, the same sample for every
+ * sequence hashed with the handle's seed: hits / sampled is an unbiased estimate of
+ * the fraction of all the record's windows that are in the set.
+ *
+ * kmc_match_from_accum: data, indices, num_seqs, data_bytes as kmc_sketch_accum_add
+ * (any alignment, offsets clamped); windows, validity, keys, flags, k, seed and hash are
+ * the handle's; limit and `all` exactly those of kmc_sketch_accum_finish and
+ * kmc_spectrum_from_accum (limit = min(2^(64 - j), lost); all: j = 0 and nothing lost).
+ * A valid window is sampled iff all, or its hash < limit; a sampled window is a hit iff
+ * its key is in the active table with count >= max(min_count, 1).
+ *   windows  device uint32[num_seqs], may be NULL: the valid windows of record r
+ *   sampled  device uint32[num_seqs], may be NULL: those of them that are sampled
+ *   hits     device uint32[num_seqs]: those of them that are hits
+ *            Every entry 0 .. num_seqs - 1 is overwritten (a record with no window:
+ *            zeros); nothing a former call left there is read.  Exact while a record
+ *            has fewer than 2^32 windows, modulo 2^32 beyond, with no stray access.
+ *   stats    device uint64[4], may be NULL:
+ *            [0] exact    1 iff all
+ *            [1] limit    the exclusive bound; UINT64_MAX when unbounded
+ *            [2] sampled  the sum of `sampled` over the records, in 64 bits
+ *            [3] hits     the sum of `hits` over the records, in 64 bits
+ * It only reads the accumulator and writes its outputs only: add, match, add, match,
+ * finish, spectrum is a valid sequence, and finish and spectrum give the same bits with
+ * and without a match in between.  Asynchronous on `stream`, no host read-back; the
+ * launches depend on the host arguments and the handle's host state only; no workspace
+ * and no library-owned buffer; calls on one accumulator are ordered by the caller.
+ * KMC_ERR_INVALID_ARG, judged before any device is touched, for a null handle, a null
+ * hits, a null indices, null data with data_bytes > 0, num_seqs above 2^40, data_bytes
+ * of 2^62 or more.  num_seqs == 0: KMC_OK, nothing is written except stats when given,
+ * with zeros in [2] and [3].
+ * (The name follows kmc_spectrum_from_accum: the kmc_sketch_accum_* functions are the
+ * handle's life cycle.) */
+KMC_API int kmc_match_from_accum(kmc_sketch_accum *a, const char *data, const int64_t *indices, uint64_t num_seqs,
+                                 uint64_t data_bytes, uint32_t min_count, uint32_t *windows, uint32_t *sampled,
+                                 uint32_t *hits, uint64_t *stats, hipStream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* Tracing (the reference times step 1 with cudaEvents, main.cu:262-300): when set,
  * every following dense count call on this host thread records `before` right
  * before its histogram kernel and `after` right after it, on the call's stream,

@@ -584,6 +584,83 @@ def accum_main(args, dev):
     print(json.dumps(rec), flush=True)
 
 
+def match_main(args, dev):
+    """--match: kmc_match_from_accum on a read set (2.6 M records of 150 bases) and on long
+    records (8 x 50 Mbase), k = 21, against a table of 2^26 slots filled from 100 Mbase;
+    half of each input is drawn from what was added, half is unrelated.  Beside it, in this
+    process, the piece-per-workgroup walks on the same bytes: kmc_sketch_accum_add (into a
+    second accumulator, reset before every add; reset is timed alone and subtracted) and
+    kmc_sketch_screen_count against the index of the set's sketch.  The outputs of a call
+    are asserted equal to a second call's before anything is timed; HIP events, 2 warm-ups,
+    median of 5."""
+    k, lg, runs = 21, 26, 5
+    set_len = max(int(50_000_000 * args.scale), 5000)
+    sdata = torch.empty(2 * (set_len + 1), dtype=torch.uint8, device=dev)
+    kmc.synth_fill(sdata, 2, set_len, 0x5EED0008)
+    sidx = torch.from_numpy(kmc.synth_indices(2, set_len)).to(dev)
+    acc, other = kmc.SketchAccum(1, k, log2_slots=lg), kmc.SketchAccum(1, k, log2_slots=lg)
+    acc.add(sdata, sidx)
+    sk, sz = kmc.sketch_from_sequences(sdata, sidx, k, 1000)
+    index = kmc.sketch_screen_build(sk, sz)
+
+    def reads():
+        n, ln = max(int(2_600_000 * args.scale), 64), 150
+        d = torch.empty(n * (ln + 1), dtype=torch.uint8, device=dev)
+        kmc.synth_fill(d, n, ln, 0x5EED0010)
+        step = max((sdata.numel() - ln) // (n // 2 + 1), 1)
+        d.view(n, ln + 1)[::2, :ln] = sdata.unfold(0, ln, step)[:(n + 1) // 2]  # pieces of the set, every `step` bytes
+        return d, torch.from_numpy(kmc.synth_indices(n, ln)).to(dev), n, ln
+
+    def long_records():
+        n, ln = 8, set_len
+        d = torch.empty(n * (ln + 1), dtype=torch.uint8, device=dev)
+        kmc.synth_fill(d, n, ln, 0x5EED0011)
+        d.view(n, ln + 1)[::2] = sdata.view(2, ln + 1).repeat(2, 1)
+        return d, torch.from_numpy(kmc.synth_indices(n, ln)).to(dev), n, ln
+
+    with open(args.out, "a") as out:
+        for name, make in (("read_set", reads), ("long_records", long_records)):
+            d, i, n, ln = make()
+            one, two = acc.match(d, i), acc.match(d, i)
+            torch.cuda.synchronize()
+            assert all(torch.equal(a, b) for a, b in zip(one, two)), name
+            win, smp, hit, st = one
+            st = [int(x) for x in st.cpu().numpy().view(np.uint64)]
+            # (a read cut over the end of one of the set's records holds its terminator and loses windows)
+            assert n * (ln - k + 1) - 2 * ln <= int(win.long().sum()) <= n * (ln - k + 1)
+            assert st[2] == int(smp.long().sum()) and st[3] == int(hit.long().sum())
+            frac = (hit[::2].long().sum().item() / max(smp[::2].long().sum().item(), 1),
+                    hit[1::2].long().sum().item() / max(smp[1::2].long().sum().item(), 1))
+            assert frac[0] > 0.98 and frac[1] < 0.01, (name, frac)  # (a piece over the set's record end loses windows)
+
+            def reset_and_add():
+                other.reset()
+                other.add(d, i)
+            rec = {
+                "input": name, "records": n, "record_len": ln, "k": k, "log2_slots": lg, "set_bases": 2 * set_len,
+                "stats": st, "hit_fraction_drawn": frac[0], "hit_fraction_unrelated": frac[1],
+                "outputs_equal_second_call": True,
+                "kmc_match_from_accum": timed(lambda: acc.match(d, i), runs),
+                "kmc_match_from_accum_hits_only": timed(
+                    lambda: acc.match(d, i, windows=False, sampled=False, stats=False), runs),
+                "reset_and_add": timed(reset_and_add, runs),
+                "kmc_sketch_accum_reset": timed(lambda: other.reset(), runs),
+                "kmc_sketch_screen_count": timed(lambda: kmc.sketch_screen_count(index, d, i, k), runs),
+            }
+            add_ms = rec["reset_and_add"]["ms_median"] - rec["kmc_sketch_accum_reset"]["ms_median"]
+            rec["kmc_sketch_accum_add_ms"] = add_ms
+            rec["match_over_screen_count"] = rec["kmc_match_from_accum"]["ms_median"] / \
+                rec["kmc_sketch_screen_count"]["ms_median"]
+            rec["match_over_add"] = rec["kmc_match_from_accum"]["ms_median"] / add_ms
+            out.write(json.dumps(rec) + "\n")
+            out.flush()
+            print(json.dumps(rec), flush=True)
+            del d, i, one, two, win, smp, hit
+            torch.cuda.empty_cache()
+    acc.close()
+    other.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(HERE), "profiles", "pr_sketch.jsonl"))
@@ -627,8 +704,16 @@ def main():
                          "with counts (where the triangle fits) and kmc_sketch_cluster on the rows of --cluster (the "
                          "list asserted; 1 warm-up, median of --runs, of a third of them and at least 3 at 65536 "
                          "rows); --out profiles/pr_sketch_links.jsonl")
+    ap.add_argument("--match", action="store_true",
+                    help="time kmc_match_from_accum on 2.6 M reads of 150 bases and on 8 x 50 Mbase (k = 21, half of "
+                         "each drawn from the set) against a table of 2^26 slots filled from 100 Mbase, beside "
+                         "kmc_sketch_accum_add and kmc_sketch_screen_count on the same records (outputs asserted equal "
+                         "to a second call's; 2 warm-ups, median of 5); appends to --out "
+                         "profiles/pr_accum_match.jsonl")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.match:
+        return match_main(args, dev)
     if args.links:
         return links_main(args, dev)
     if args.cluster:
