@@ -13,7 +13,9 @@
 //   3. validation, one thread per complete record (fq_validate_kernel): its five
 //      line starts give the four lines; len + 1 is stored per record and the
 //      smallest index of a record that breaks a rule is kept with a 64-bit
-//      atomicMin.  Nothing has been written to the caller's buffers so far;
+//      atomicMin.  Nothing has been written to the caller's data and indices so
+//      far; the first of the five line starts is the record's raw offset, stored
+//      when the caller asked for them (kmc_fastq_parse_device_ex);
 //   4. the exclusive scan of len + 1 over the records is `indices`;
 //   5. write (fq_write_kernel), one pass over the raw tiles: byte p of line 4r + 1
 //      goes to indices[r] + (p - lstart[4r + 1]), the byte that ends the sequence
@@ -57,6 +59,7 @@ struct QParams {
     uint8_t *out;
     uint64_t out_cap;
     const int64_t *idx;   // [nrec + 1], pass 5
+    int64_t *rawidx;      // [nrec + 1] or null: where each record's raw text starts, and where the last one ends
 };
 
 // 1. newlines per tile
@@ -112,8 +115,11 @@ __global__ __launch_bounds__(kFqVBlock) void fq_validate_kernel(QParams p) {
         const uint64_t len = e[1] - s[1];
         const bool ok = e[0] > s[0] && p.raw[s[0]] == '@' && e[2] > s[2] && p.raw[s[2]] == '+' && e[3] - s[3] == len;
         p.reclen[r] = (uint32_t)(len + 1);
+        if (p.rawidx) p.rawidx[r] = (int64_t)s[0];
         if (!ok) atomicMin((unsigned long long *)&p.result[0], (unsigned long long)r);
     } else if (r == p.nrec) {
+        // (lstart[nl + 1] = n + 1 stands for the '\n' a final input's last line lacks)
+        if (p.rawidx) p.rawidx[r] = (int64_t)std::min<uint64_t>(p.lstart[4 * p.nrec], (uint64_t)p.n);
         if (p.final) {  // fewer than four lines are left over: all of them empty
             bool ok = true;
             for (uint64_t l = 4 * p.nrec; l < p.nlines; ++l) {
@@ -213,9 +219,11 @@ constexpr uint64_t kFqMaxRaw = 1ull << 33;
 // Parses the complete records of raw[0, n); `get_idx(num_records)` supplies the
 // offsets buffer (num_records + 1 entries) once the input is known to be well
 // formed and the count is known, or returns null to stop with the count only.
-template <class GetIdx>
+// raw_idx(num_records) likewise supplies the buffer of the raw offsets, before the
+// records are judged, or null for none.
+template <class GetIdx, class GetRawIdx>
 int fq_parse(const char *raw, uint64_t n, int final, char *out, uint64_t out_cap, GetIdx &&get_idx,
-             uint64_t *num_seqs, uint64_t *data_bytes, uint64_t *consumed, hipStream_t st) {
+             GetRawIdx &&raw_idx, uint64_t *num_seqs, uint64_t *data_bytes, uint64_t *consumed, hipStream_t st) {
     *num_seqs = 0;
     *data_bytes = 0;
     *consumed = 0;
@@ -224,6 +232,8 @@ int fq_parse(const char *raw, uint64_t n, int final, char *out, uint64_t out_cap
         int64_t *idx = get_idx((uint64_t)0);
         if (!idx) return 0;
         const int64_t zero = 0;
+        int64_t *ridx = raw_idx((uint64_t)0);
+        if (ridx && (he = hipMemcpyAsync(ridx, &zero, 8, hipMemcpyHostToDevice, st))) return (int)he;
         if ((he = hipMemcpyAsync(idx, &zero, 8, hipMemcpyHostToDevice, st)) || (he = hipStreamSynchronize(st)))
             return (int)he;
         return 0;
@@ -253,6 +263,7 @@ int fq_parse(const char *raw, uint64_t n, int final, char *out, uint64_t out_cap
     p.nrec = (p.final ? p.nlines : p.nl) / 4;
     if ((e = q_ws[1].get(device, q_line_layout(nullptr, p, bsum), &ws))) return e;
     q_line_layout(ws, p, bsum);
+    p.rawidx = raw_idx(p.nrec);
     // line starts -> every record judged, before anything of the caller's is written
     hipLaunchKernelGGL(fq_lstart_kernel, dim3((unsigned)p.ntiles), dim3(kFpBlock), 0, st, p);
     hipLaunchKernelGGL(fq_validate_kernel, dim3((unsigned)(p.nrec / kFqVBlock + 1)), dim3(kFqVBlock), 0, st, p);
@@ -294,9 +305,10 @@ int fq_parse_args(const char *raw, uint64_t raw_bytes, const char *data, uint64_
 
 using namespace kmc;
 
-extern "C" int kmc_fastq_parse_device(const char *raw, uint64_t raw_bytes, int final, char *data, uint64_t data_cap,
-                                      int64_t *indices, uint64_t indices_cap, uint64_t *num_seqs,
-                                      uint64_t *data_bytes, uint64_t *consumed, hipStream_t stream) {
+extern "C" int kmc_fastq_parse_device_ex(const char *raw, uint64_t raw_bytes, int final, char *data, uint64_t data_cap,
+                                         int64_t *indices, uint64_t indices_cap, uint64_t *num_seqs,
+                                         uint64_t *data_bytes, uint64_t *consumed, int64_t *raw_indices,
+                                         hipStream_t stream) {
     if (int e = fq_parse_args(raw, raw_bytes, data, data_cap, indices, num_seqs, data_bytes, consumed)) return e;
     bool too_small = false;
     auto get_idx = [&](uint64_t nrec) -> int64_t * {
@@ -306,9 +318,18 @@ extern "C" int kmc_fastq_parse_device(const char *raw, uint64_t raw_bytes, int f
         }
         return indices;
     };
-    const int rc = fq_parse(raw, raw_bytes, final, data, data_cap, get_idx, num_seqs, data_bytes, consumed, stream);
+    auto raw_idx = [&](uint64_t nrec) -> int64_t * { return indices_cap < nrec + 1 ? nullptr : raw_indices; };
+    const int rc = fq_parse(raw, raw_bytes, final, data, data_cap, get_idx, raw_idx, num_seqs, data_bytes, consumed,
+                            stream);
     if (!rc && too_small) return KMC_ERR_CAPACITY;
     return rc;
+}
+
+extern "C" int kmc_fastq_parse_device(const char *raw, uint64_t raw_bytes, int final, char *data, uint64_t data_cap,
+                                      int64_t *indices, uint64_t indices_cap, uint64_t *num_seqs,
+                                      uint64_t *data_bytes, uint64_t *consumed, hipStream_t stream) {
+    return kmc_fastq_parse_device_ex(raw, raw_bytes, final, data, data_cap, indices, indices_cap, num_seqs, data_bytes,
+                                     consumed, nullptr, stream);
 }
 
 extern "C" int kmc_fastq_load_device(const char *path, int64_t max_seqs, char **data, uint64_t *data_bytes,
@@ -334,7 +355,8 @@ extern "C" int kmc_fastq_load_device(const char *path, int64_t max_seqs, char **
         return *indices;
     };
     if (!rc) {
-        rc = fq_parse(raw, n, 1, *data, cap, get_idx, num_seqs, data_bytes, &consumed, stream);
+        rc = fq_parse(raw, n, 1, *data, cap, get_idx, [](uint64_t) -> int64_t * { return nullptr; }, num_seqs,
+                      data_bytes, &consumed, stream);
         if (!rc && no_idx) rc = KMC_ERR_NOMEM;
     }
     (void)hipFree(raw);
@@ -368,6 +390,11 @@ struct kmc_fastq_reader {
     uint64_t data_cap = 0;
     int64_t *idx = nullptr;    // device: their offsets
     uint64_t idx_cap = 0;
+    bool keep_raw = false;     // KMC_FASTQ_KEEP_RAW
+    int64_t *raw_idx = nullptr;  // device, idx_cap entries when keep_raw: the records' raw offsets
+    uint64_t raw_end = 0;      // raw_idx[batch's records] on the host
+    uint64_t batch_seqs = 0;   // records of the last batch
+    int state = 0;             // 0: no batch yet, 1: a batch is held, 2: after the last batch
     uint64_t records = 0;      // records of the batches before this one
     bool eof = false, done = false;
     int failed = 0;            // a failed call's code: the reader stays failed
@@ -435,12 +462,15 @@ int fq_next(kmc_fastq_reader *rd, uint64_t *num_seqs, uint64_t *data_bytes, hipS
             if (!rd->idx) {
                 rd->idx_cap = std::max<uint64_t>(rd->idx_cap, rd->have / 64 + 2);
                 if (hipMalloc(&rd->idx, rd->idx_cap * 8) != hipSuccess) return KMC_ERR_NOMEM;
+                if (rd->keep_raw && hipMalloc(&rd->raw_idx, rd->idx_cap * 8) != hipSuccess) return KMC_ERR_NOMEM;
             }
-            const int rc = kmc_fastq_parse_device(rd->raw, rd->have, rd->eof, rd->data, rd->data_cap, rd->idx,
-                                                  rd->idx_cap, num_seqs, data_bytes, &consumed, st);
+            const int rc = kmc_fastq_parse_device_ex(rd->raw, rd->have, rd->eof, rd->data, rd->data_cap, rd->idx,
+                                                     rd->idx_cap, num_seqs, data_bytes, &consumed, rd->raw_idx, st);
             if (rc == KMC_ERR_CAPACITY && *num_seqs + 1 > rd->idx_cap) {
                 (void)hipFree(rd->idx);
                 rd->idx = nullptr;
+                if (rd->raw_idx) (void)hipFree(rd->raw_idx);
+                rd->raw_idx = nullptr;
                 rd->idx_cap = *num_seqs + 1 + *num_seqs / 4;
                 continue;
             }
@@ -452,6 +482,16 @@ int fq_next(kmc_fastq_reader *rd, uint64_t *num_seqs, uint64_t *data_bytes, hipS
             rd->records += *num_seqs;
             rd->done = rd->eof;
             rd->used = rd->eof ? rd->have : consumed;
+            rd->batch_seqs = *num_seqs;
+            rd->raw_end = consumed;
+            if (rd->keep_raw && rd->eof) {  // (blank lines may follow the last record of a file)
+                int64_t end = 0;
+                hipError_t he;
+                if ((he = hipMemcpyAsync(&end, rd->raw_idx + *num_seqs, 8, hipMemcpyDeviceToHost, st)) ||
+                    (he = hipStreamSynchronize(st)))
+                    return (int)he;
+                rd->raw_end = (uint64_t)end;
+            }
             return 0;
         }
         want = std::max<uint64_t>(rd->have, rd->batch);  // no complete record yet: twice the bytes
@@ -460,10 +500,10 @@ int fq_next(kmc_fastq_reader *rd, uint64_t *num_seqs, uint64_t *data_bytes, hipS
 
 }  // namespace
 
-extern "C" int kmc_fastq_open(const char *path, uint64_t batch_bytes, kmc_fastq_reader **out) {
+extern "C" int kmc_fastq_open_ex(const char *path, uint64_t batch_bytes, unsigned flags, kmc_fastq_reader **out) {
     if (!path || !out) return KMC_ERR_INVALID_ARG;
     *out = nullptr;
-    if (batch_bytes >= kFqMaxRaw / 2) return KMC_ERR_INVALID_ARG;
+    if (batch_bytes >= kFqMaxRaw / 2 || (flags & ~KMC_FASTQ_KEEP_RAW)) return KMC_ERR_INVALID_ARG;
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return KMC_ERR_IO;
     kmc_fastq_reader *rd = new (std::nothrow) kmc_fastq_reader;
@@ -473,7 +513,27 @@ extern "C" int kmc_fastq_open(const char *path, uint64_t batch_bytes, kmc_fastq_
     }
     rd->fd = fd;
     rd->batch = batch_bytes ? (batch_bytes + 15) & ~(uint64_t)15 : (256ull << 20);
+    rd->keep_raw = (flags & KMC_FASTQ_KEEP_RAW) != 0;
     *out = rd;
+    return 0;
+}
+
+extern "C" int kmc_fastq_open(const char *path, uint64_t batch_bytes, kmc_fastq_reader **out) {
+    return kmc_fastq_open_ex(path, batch_bytes, 0u, out);
+}
+
+extern "C" int kmc_fastq_raw(kmc_fastq_reader *rd, const char **raw, uint64_t *raw_bytes, const int64_t **raw_indices) {
+    if (!rd || !raw || !raw_bytes || !raw_indices) return KMC_ERR_INVALID_ARG;
+    *raw = nullptr;
+    *raw_indices = nullptr;
+    *raw_bytes = 0;
+    if (!rd->keep_raw) return KMC_ERR_INVALID_ARG;
+    if (rd->failed) return rd->failed;
+    if (rd->state == 0) return KMC_ERR_INVALID_ARG;
+    if (rd->state == 2) return 0;
+    *raw = rd->raw;
+    *raw_indices = rd->raw_idx;
+    *raw_bytes = rd->raw_end;
     return 0;
 }
 
@@ -488,7 +548,10 @@ extern "C" int kmc_fastq_next(kmc_fastq_reader *rd, const char **data, uint64_t 
         *num_seqs = rd->failed_at;
         return rd->failed;
     }
-    if (rd->done) return 0;
+    if (rd->done) {
+        rd->state = 2;
+        return 0;
+    }
     const int rc = fq_next(rd, num_seqs, data_bytes, stream);
     if (rc) {
         rd->failed = rc;
@@ -497,6 +560,7 @@ extern "C" int kmc_fastq_next(kmc_fastq_reader *rd, const char **data, uint64_t 
         *data_bytes = 0;
         return rc;
     }
+    rd->state = 1;
     *data = rd->data;
     *indices = rd->idx;
     return 0;
@@ -508,6 +572,7 @@ extern "C" void kmc_fastq_close(kmc_fastq_reader *rd) {
     if (rd->raw) (void)hipFree(rd->raw);
     if (rd->data) (void)hipFree(rd->data);
     if (rd->idx) (void)hipFree(rd->idx);
+    if (rd->raw_idx) (void)hipFree(rd->raw_idx);
     if (rd->fd >= 0) close(rd->fd);
     delete rd;
 }

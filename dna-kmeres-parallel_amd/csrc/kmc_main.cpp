@@ -35,7 +35,9 @@
 // (kmc_sketch_links -> pairs.tsv; with --query FILE kmc_sketch_links_rect -> query_pairs.tsv)
 // instead of every distance.  --recruit FILE: the input files are one k-mer set in the accumulator
 // and every record of FILE is matched against it (kmc_match_from_accum -> read_matches.tsv,
-// read_matches_summary.tsv).
+// read_matches_summary.tsv); --write-recruited / --write-rest: the listed records, or the others, as
+// the raw FASTQ text of the input (kmc_match_select, kmc_select_records on the reader's raw batch ->
+// recruited_<f>.fastq, rest_<f>.fastq).
 // GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
@@ -54,6 +56,7 @@
 
 #include "kmc.h"
 #include "kmc_internal.h"
+#include "kmc_stage.h"
 
 namespace {
 
@@ -101,6 +104,7 @@ struct Options {
     long min_hits = 1;                 // --min-hits H: a listed record has at least H hits
     double min_fraction = 0.0;         // --min-fraction F: and hits >= F * sampled
     bool min_hits_set = false, min_fraction_set = false;
+    bool write_recruited = false, write_rest = false;  // --write-recruited, --write-rest: the reads themselves
 };
 
 // auto: FASTQ exactly when the name ends in .fq or .fastq, whatever the case
@@ -126,7 +130,8 @@ void usage(FILE *f) {
             "       kmc --canonical --sketch S [--sketch-direct] [--per-file] --cluster D [options] <input.fasta> ...\n"
             "       kmc --canonical --sketch S [--sketch-direct] [--per-file] --pairs D [--query q.fasta] [options] <input.fasta> ...\n"
             "       kmc -k K --canonical --recruit reads.fastq [--recruit more.fq] [--min-abundance M] [--min-hits H]\n"
-            "           [--min-fraction F] --accum-slots L [--batch BYTES] [options] <host.fasta> <phage.fasta> ...\n"
+            "           [--min-fraction F] --accum-slots L [--batch BYTES] [--write-recruited] [--write-rest] [options]\n"
+            "           <host.fasta> <phage.fasta> ...\n"
             "       kmc synth OUT.fa RECORDS LENGTH [SEED]   (benchmark input, SURVEY.md 8(d))\n"
             "  -k K              k-mer length (default %d, the reference's K); dense path 1..%d,\n"
             "                    --canonical 1..%d\n"
@@ -268,6 +273,12 @@ void usage(FILE *f) {
             "                    --screen, --query, --cluster, --pairs, --distances or --spectrum\n"
             "  --min-hits H      with --recruit: a record is listed when hits >= H (default 1)\n"
             "  --min-fraction F  with --recruit: and hits >= F * sampled, F in 0..1 (default 0)\n"
+            "  --write-recruited with --recruit, every FILE in FASTQ: <out>/recruited_<f>.fastq (f: the file's number\n"
+            "                    in read_matches.tsv) gets the listed records of FILE as the raw bytes of the input,\n"
+            "                    headers, qualities and line ends included, in input order (kmc_match_select,\n"
+            "                    kmc_select_records on each batch's raw text, then device to file)\n"
+            "  --write-rest      the same for the records that are not listed: <out>/rest_<f>.fastq (depletion).\n"
+            "                    Either option holds one more raw batch of device memory (--batch), shared by both\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
@@ -419,6 +430,10 @@ int parse(int argc, char **argv, Options &o) {
                 fprintf(stderr, "kmc: --min-fraction takes a fraction in 0..1\n");
                 return usage(stderr), 2;
             }
+        } else if (a == "--write-recruited") {
+            o.write_recruited = true;
+        } else if (a == "--write-rest") {
+            o.write_rest = true;
         } else if (a == "--softmask") {
             o.softmask = true;
         } else if (a == "--host-loader") {
@@ -441,6 +456,10 @@ int parse(int argc, char **argv, Options &o) {
         return fprintf(stderr, "kmc: k = %d out of range\n", o.k), 2;
     if ((o.min_hits_set || o.min_fraction_set) && o.recruit.empty()) {
         fprintf(stderr, "kmc: --min-hits and --min-fraction select the lines of --recruit\n");
+        return usage(stderr), 2;
+    }
+    if ((o.write_recruited || o.write_rest) && o.recruit.empty()) {
+        fprintf(stderr, "kmc: --write-recruited and --write-rest write the reads of --recruit\n");
         return usage(stderr), 2;
     }
     if (!o.recruit.empty()) {
@@ -467,6 +486,13 @@ int parse(int argc, char **argv, Options &o) {
             return usage(stderr), 2;
         }
         o.max_seqs = 0;
+        if (o.write_recruited || o.write_rest)
+            for (const std::string &f : o.recruit)
+                if (!is_fastq(o, f)) {
+                    fprintf(stderr, "kmc: --write-recruited and --write-rest write FASTQ records: %s is not FASTQ "
+                                    "(--format, or a .fq / .fastq name)\n", f.c_str());
+                    return usage(stderr), 2;
+                }
     }
     if ((o.sketch > 0 || o.min_count_set) && !o.canonical) {
         fprintf(stderr, "kmc: --sketch and --min-count need --canonical\n");
@@ -655,6 +681,28 @@ using Fasta = std::unique_ptr<kmc_fasta, FastaFree>;
 using FastqReader = std::unique_ptr<kmc_fastq_reader, FastqClose>;
 using Accum = std::unique_ptr<kmc_sketch_accum, AccumFree>;
 using File = std::unique_ptr<FILE, FileClose>;
+
+// a file descriptor that is closed with its owner (-1: none)
+class Fd {
+public:
+    Fd() = default;
+    Fd(const Fd &) = delete;
+    Fd &operator=(const Fd &) = delete;
+    ~Fd() { reset(-1); }
+    int get() const { return fd_; }
+    void reset(int fd) {
+        if (fd_ >= 0) (void)close(fd_);
+        fd_ = fd;
+    }
+    int release() {
+        const int fd = fd_;
+        fd_ = -1;
+        return fd;
+    }
+
+private:
+    int fd_ = -1;
+};
 
 // max(count, 1) elements: an empty input still gets a pointer the entry points take
 template <class T>
@@ -1041,15 +1089,19 @@ int sketch_files(const Options &o, const std::vector<std::string> &files, const 
 
 // f(data, idx, records, bytes) over the batches of one file on st: a FASTQ file batch by
 // batch through the reader (the next batch's writes are ordered behind what f put on st), a
-// FASTA file loaded whole, one batch.  The batch's buffers live until f returns.
+// FASTA file loaded whole, one batch.  The batch's buffers live until f returns.  With
+// `reader` the FASTQ reader is opened with `flags` and *reader is it while f runs (null for FASTA).
 template <class F>
-int for_each_batch(const Options &o, const std::string &path, hipStream_t st, uint64_t *batches, F &&f) {
+int for_each_batch(const Options &o, const std::string &path, hipStream_t st, uint64_t *batches, F &&f,
+                   unsigned flags = 0, kmc_fastq_reader **current = nullptr) {
     *batches = 0;
+    if (current) *current = nullptr;
     if (is_fastq(o, path)) {
         kmc_fastq_reader *rd = nullptr;
-        const int orc = kmc_fastq_open(path.c_str(), o.batch, &rd);
+        const int orc = kmc_fastq_open_ex(path.c_str(), o.batch, flags, &rd);
         if (orc) return fprintf(stderr, "kmc: %s: %s\n", path.c_str(), kmc_error_string(orc)), 1;
         const FastqReader reader(rd);
+        if (current) *current = rd;
         for (;;) {
             const char *d_data = nullptr;
             const int64_t *d_idx = nullptr;
@@ -1121,9 +1173,31 @@ int run_recruit(const Options &o, hipStream_t st) {
     HIPCHK(hipMemcpyAsync(of_set, d_stats.get(), sizeof of_set, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     bool lost = false;
+    // --write-recruited, --write-rest: the flags and the kept bytes of one batch, and the way to the file
+    const bool writing = o.write_recruited || o.write_rest;
+    DevBuf<uint32_t> d_keep;
+    DevBuf<char> d_sel;
+    DevBuf<uint64_t> d_counts;
+    uint64_t keep_cap = 0, sel_cap = 0;
+    kmc::Drainer drainer;
+    if (writing) {
+        HIPCHK(dev_alloc(d_counts, 2));
+        KMCCHK(drainer.init((size_t)std::min<uint64_t>(o.batch ? o.batch : (256ull << 20), kmc::kStageChunk)));
+    }
     for (size_t f = 0; f < o.recruit.size(); ++f) {
         uint64_t records = 0, listed = 0, batches = 0;
         uint64_t total[4] = {of_set[0], of_set[1], 0, 0};
+        // [0]: recruited_<f>.fastq (invert 0), [1]: rest_<f>.fastq (invert 1)
+        Fd fd[2];
+        std::string name[2];
+        uint64_t written[2] = {0, 0};
+        for (int w = 0; w < 2; ++w) {
+            if (!(w == 0 ? o.write_recruited : o.write_rest)) continue;
+            name[w] = o.out_dir + (w == 0 ? "/recruited_" : "/rest_") + std::to_string(f) + ".fastq";
+            fd[w].reset(open(name[w].c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666));
+            if (fd[w].get() < 0) return fprintf(stderr, "kmc: cannot write %s\n", name[w].c_str()), 1;
+        }
+        kmc_fastq_reader *rd = nullptr;
         const int e = for_each_batch(o, o.recruit[f], st, &batches,
                                      [&](const char *d, const int64_t *idx, uint64_t ns, uint64_t nb) {
             if (ns > cap) {
@@ -1140,6 +1214,33 @@ int run_recruit(const Options &o, hipStream_t st) {
                 HIPCHK(hipMemcpyAsync(out.data() + 2 * ns, d_hit, ns * 4, hipMemcpyDeviceToHost, st));
             }
             HIPCHK(hipMemcpyAsync(stats, d_stats.get(), sizeof stats, hipMemcpyDeviceToHost, st));
+            if (writing) {  // the same rule on the device, then the selected raw text, once per output
+                const char *d_raw = nullptr;
+                const int64_t *d_ridx = nullptr;
+                uint64_t raw_bytes = 0;
+                KMCCHK(kmc_fastq_raw(rd, &d_raw, &raw_bytes, &d_ridx));
+                if (ns > keep_cap) {
+                    HIPCHK(dev_alloc(d_keep, ns));
+                    keep_cap = ns;
+                }
+                if (raw_bytes > sel_cap) {
+                    HIPCHK(dev_alloc(d_sel, raw_bytes));
+                    sel_cap = raw_bytes;
+                }
+                KMCCHK(kmc_match_select(d_smp, d_hit, ns, (uint32_t)o.min_hits, o.min_fraction, d_keep.get(), nullptr, st));
+                for (int w = 0; w < 2 && ns > 0; ++w) {
+                    if (fd[w].get() < 0) continue;
+                    uint64_t counts[2] = {0, 0};
+                    KMCCHK(kmc_select_records(d_raw, d_ridx, ns, raw_bytes, d_keep.get(), w, d_sel.get(), sel_cap, nullptr,
+                                              d_counts.get(), nullptr, 0, st));
+                    HIPCHK(hipMemcpyAsync(counts, d_counts.get(), sizeof counts, hipMemcpyDeviceToHost, st));
+                    HIPCHK(hipStreamSynchronize(st));
+                    const int wrc = drainer.drain(fd[w].get(), d_sel.get(), counts[1], st);
+                    if (wrc == KMC_ERR_IO) return fprintf(stderr, "kmc: cannot write %s\n", name[w].c_str()), 1;
+                    KMCCHK(wrc);
+                    written[w] += counts[0];
+                }
+            }
             HIPCHK(hipStreamSynchronize(st));  // before the batch's buffers go
             total[0] = stats[0];
             total[1] = stats[1];
@@ -1154,8 +1255,15 @@ int run_recruit(const Options &o, hipStream_t st) {
             }
             records += ns;
             return 0;
-        });
+        }, writing ? KMC_FASTQ_KEEP_RAW : 0u, &rd);
         if (e) return e;
+        for (int w = 0; w < 2; ++w) {
+            if (fd[w].get() < 0) continue;
+            if (close(fd[w].release()) != 0) return fprintf(stderr, "kmc: cannot write %s\n", name[w].c_str()), 1;
+            if (written[w] != (w == 0 ? listed : records - listed))  // the host's rule and the device's are one
+                return fprintf(stderr, "kmc: %s holds %" PRIu64 " records, read_matches.tsv lists %" PRIu64 " of %" PRIu64 "\n",
+                               name[w].c_str(), written[w], listed, records), 1;
+        }
         fprintf(f_sum.get(), "%zu\t%s\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t%d\t%" PRIu64 "\t%" PRIu64 "\n", f,
                 o.recruit[f].c_str(), records, listed, total[1], (int)total[0], total[2], total[3]);
         if (!o.quiet)

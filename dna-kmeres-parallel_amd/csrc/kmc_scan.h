@@ -1,7 +1,9 @@
 // kmc_scan.h — exclusive prefix sum of a uint32 array into uint64 offsets, on
 // the device, in three launches (per-tile totals, one-block scan of the totals,
 // per-tile apply).  Shared by the radix partition (bucket offsets) and the
-// canonical table compaction (output positions).
+// canonical table compaction (output positions).  excl_scan_u64 is the same scan
+// of uint64 inputs (the kept byte lengths of kmc_select_records: a record may hold
+// 4 GiB and more), summed modulo 2^64 like the other.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -44,7 +46,8 @@ __device__ __forceinline__ bool scan_gated_off(const uint32_t *gate) {
     return gate != nullptr && __hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
 }
 
-__global__ __launch_bounds__(kScanBlock) void scan_reduce_kernel(const uint32_t *in, int64_t m, uint64_t *bsum,
+template <class T>
+__global__ __launch_bounds__(kScanBlock) void scan_reduce_kernel(const T *in, int64_t m, uint64_t *bsum,
                                                                  const uint32_t *gate) {
     __shared__ uint64_t sh[kScanBlock / 64];
     if (scan_gated_off(gate)) return;
@@ -73,7 +76,8 @@ __global__ __launch_bounds__(kScanBlock) void scan_blocks_kernel(uint64_t *bsum,
     }
 }
 
-__global__ __launch_bounds__(kScanBlock) void scan_apply_kernel(const uint32_t *in, int64_t m, const uint64_t *bsum,
+template <class T>
+__global__ __launch_bounds__(kScanBlock) void scan_apply_kernel(const T *in, int64_t m, const uint64_t *bsum,
                                                                 uint64_t *out, const uint32_t *gate) {
     __shared__ uint64_t sh[kScanBlock / 64];
     if (scan_gated_off(gate)) return;
@@ -96,12 +100,23 @@ __global__ __launch_bounds__(kScanBlock) void scan_apply_kernel(const uint32_t *
 // gate: see scan_gated_off
 inline int64_t scan_tiles(int64_t m) { return (m + kScanTile - 1) / kScanTile; }
 
+template <class T>
+inline void excl_scan(const T *in, int64_t m, uint64_t *bsum, uint64_t *out, hipStream_t st, const uint32_t *gate) {
+    const int64_t nt = scan_tiles(m) > 0 ? scan_tiles(m) : 1;
+    hipLaunchKernelGGL(scan_reduce_kernel<T>, dim3((unsigned)nt), dim3(kScanBlock), 0, st, in, m, bsum, gate);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(kScanBlock), 0, st, bsum, nt, gate);
+    hipLaunchKernelGGL(scan_apply_kernel<T>, dim3((unsigned)nt), dim3(kScanBlock), 0, st, in, m, bsum, out, gate);
+}
+
 inline void excl_scan_u32(const uint32_t *in, int64_t m, uint64_t *bsum, uint64_t *out, hipStream_t st,
                           const uint32_t *gate = nullptr) {
-    const int64_t nt = scan_tiles(m) > 0 ? scan_tiles(m) : 1;
-    hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)nt), dim3(kScanBlock), 0, st, in, m, bsum, gate);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(kScanBlock), 0, st, bsum, nt, gate);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nt), dim3(kScanBlock), 0, st, in, m, bsum, out, gate);
+    excl_scan<uint32_t>(in, m, bsum, out, st, gate);
+}
+
+// the same of uint64 inputs
+inline void excl_scan_u64(const uint64_t *in, int64_t m, uint64_t *bsum, uint64_t *out, hipStream_t st,
+                          const uint32_t *gate = nullptr) {
+    excl_scan<uint64_t>(in, m, bsum, out, st, gate);
 }
 
 }  // namespace

@@ -88,6 +88,75 @@ private:
     uint64_t turn_ = 0;
 };
 
+// The twin of Stager, device memory -> file through two pinned buffers: the copy of
+// chunk i + 1 overlaps the write() of chunk i.  Only write() is used on the
+// descriptor, so it may be a pipe.
+class Drainer {
+public:
+    Drainer() = default;
+    Drainer(const Drainer &) = delete;
+    Drainer &operator=(const Drainer &) = delete;
+    ~Drainer() { release(); }
+
+    // two pinned buffers of `chunk` bytes (called once, before drain)
+    int init(size_t chunk) {
+        chunk_ = std::max<size_t>(chunk, 16);
+        for (int b = 0; b < 2; ++b) {
+            if (hipHostMalloc(&pin_[b], chunk_, hipHostMallocDefault) != hipSuccess) return KMC_ERR_NOMEM;
+            if (hipEventCreateWithFlags(&done_[b], hipEventDisableTiming) != hipSuccess) return KMC_ERR_NOMEM;
+        }
+        return 0;
+    }
+
+    // Writes src[0, bytes) (device; the copies issued on st, behind the work that fills
+    // src) to fd.  Returns when every byte is written: KMC_ERR_IO for a failed or
+    // short write.
+    int drain(int fd, const char *src, uint64_t bytes, hipStream_t st) {
+        uint64_t sent = 0;     // bytes whose copy is issued
+        size_t len[2] = {0, 0};
+        int pending = -1;      // the buffer whose copy is in flight
+        while (sent < bytes || pending >= 0) {
+            int issued = -1;
+            if (sent < bytes) {
+                issued = pending < 0 ? 0 : 1 - pending;
+                len[issued] = (size_t)std::min<uint64_t>(chunk_, bytes - sent);
+                if (hipError_t he = hipMemcpyAsync(pin_[issued], src + sent, len[issued], hipMemcpyDeviceToHost, st))
+                    return (int)he;
+                if (hipError_t he = hipEventRecord(done_[issued], st)) return (int)he;
+                sent += len[issued];
+            }
+            if (pending >= 0) {  // the last chunk goes to the file while this one is copied
+                if (hipError_t he = hipEventSynchronize(done_[pending])) return (int)he;
+                size_t put = 0;
+                while (put < len[pending]) {
+                    const ssize_t w = write(fd, pin_[pending] + put, len[pending] - put);
+                    if (w <= 0) return KMC_ERR_IO;
+                    put += (size_t)w;
+                }
+            }
+            pending = issued;
+        }
+        return 0;
+    }
+
+    void release() {
+        for (int b = 0; b < 2; ++b) {
+            if (done_[b]) {
+                (void)hipEventSynchronize(done_[b]);  // (a copy a failed drain left in flight)
+                (void)hipEventDestroy(done_[b]);
+            }
+            if (pin_[b]) (void)hipHostFree(pin_[b]);
+            done_[b] = nullptr;
+            pin_[b] = nullptr;
+        }
+    }
+
+private:
+    char *pin_[2] = {nullptr, nullptr};
+    hipEvent_t done_[2] = {nullptr, nullptr};
+    size_t chunk_ = 0;
+};
+
 // The whole of a regular file in device memory: *raw (hipMalloc, *n + 16 bytes; the
 // caller frees it), the copies complete on return.
 inline int stage_file(const char *path, char **raw, uint64_t *n, hipStream_t st) {

@@ -44,6 +44,7 @@ KMC_ERR_CAPACITY = 1009
 KMC_ERR_RECORD_TOO_LONG = 1010
 KMC_ERR_INTERNAL = 1011
 KMC_ERR_FORMAT = 1012
+KMC_FASTQ_KEEP_RAW = 1
 
 
 class KmcError(RuntimeError):
@@ -212,6 +213,14 @@ def _load(path):
     L.kmc_fastq_next.argtypes = [_P, ctypes.POINTER(_P), ctypes.POINTER(_U64), ctypes.POINTER(_P),
                                  ctypes.POINTER(_U64), _P]
     L.kmc_fastq_close.argtypes = [_P]
+    L.kmc_fastq_parse_device_ex.argtypes = [_P, _U64, ctypes.c_int, _P, _U64, _P, _U64, ctypes.POINTER(_U64),
+                                            ctypes.POINTER(_U64), ctypes.POINTER(_U64), _P, _P]
+    L.kmc_fastq_open_ex.argtypes = [ctypes.c_char_p, _U64, ctypes.c_uint, ctypes.POINTER(_P)]
+    L.kmc_fastq_raw.argtypes = [_P, ctypes.POINTER(_P), ctypes.POINTER(_U64), ctypes.POINTER(_P)]
+    L.kmc_select_records_workspace_size.restype = ctypes.c_size_t
+    L.kmc_select_records_workspace_size.argtypes = [_U64, _U64]
+    L.kmc_select_records.argtypes = [_P, _P, _U64, _U64, _P, ctypes.c_int, _P, _U64, _P, _P, _P, ctypes.c_size_t, _P]
+    L.kmc_match_select.argtypes = [_P, _P, _U64, ctypes.c_uint32, ctypes.c_double, _P, _P, _P]
     L.kmc_fastq_close.restype = None
     L.kmc_pair_distances_workspace_size.restype = ctypes.c_size_t
     L.kmc_pair_distances_workspace_size.argtypes = [_U64, ctypes.c_int, ctypes.c_int]
@@ -1002,6 +1011,67 @@ SPECTRUM_MAX_BINS = 8192
 SpectrumResult = collections.namedtuple("SpectrumResult", [f[0] for f in SpectrumSummary._fields_])
 
 
+def select_records_workspace_size(num_recs, src_bytes):
+    return int(lib().kmc_select_records_workspace_size(int(num_recs), int(src_bytes)))
+
+
+def select_records(src, offsets, keep, invert=False, capacity=None, offsets_out=True, src_bytes=None, workspace=None,
+                   out=None, stream=None):
+    """kmc_select_records: the records src[offsets[r]:offsets[r+1]] (src uint8, offsets
+    int64 [n+1], on the device) with (keep[r] != 0) != invert, concatenated in input
+    order.  keep: int32 or uint32 [n]; any non-zero value selects, so the hits of
+    SketchAccum.match serve.  Returns (dst uint8 [capacity], dst_offsets int64 [n+1] or
+    None, counts int64 [2]: the selected records and their bytes), all on the device
+    and nothing read back: dst[:counts[1]] and dst_offsets[:counts[0] + 1] are the
+    result, a record buffer again.  capacity: None for src's size, which always
+    suffices; 0 counts only.  offsets_out: True for a new tensor, False for none, or
+    the caller's own; out: the caller's own (dst, counts)."""
+    import torch
+    n = int(offsets.numel() - 1)
+    if src_bytes is None:
+        src_bytes = src.numel()
+    with _on(stream):
+        dv = torch.device("cuda", torch.cuda.current_device())
+        if out is not None:
+            dst, counts = out
+            cap = dst.numel() if capacity is None else int(capacity)
+        else:
+            cap = int(src_bytes) if capacity is None else int(capacity)
+            dst = torch.empty(cap, dtype=torch.uint8, device=dv)
+            counts = torch.empty(2, dtype=torch.int64, device=dv)
+        if isinstance(offsets_out, torch.Tensor):
+            doff = offsets_out
+        else:
+            doff = torch.empty(n + 1, dtype=torch.int64, device=dv) if offsets_out else None
+        # (no record: an empty tensor has no address, and the library refuses a null keep; nothing is read there)
+        keep_at = keep if keep.numel() else torch.empty(1, dtype=torch.int32, device=dv)
+    ws, ws_bytes = _ws(workspace)
+    _check(lib().kmc_select_records(_dptr(src) if src.numel() else None, _dptr(offsets), n, int(src_bytes),
+                                    _dptr(keep_at), 1 if invert else 0, _dptr(dst) if cap else None, cap, _dptr(doff),
+                                    _dptr(counts), ws, ws_bytes, _stream(stream)), "kmc_select_records")
+    return dst, doff, counts
+
+
+def match_select(sampled, hits, min_hits=1, min_fraction=0.0, count=True, out=None, stream=None):
+    """kmc_match_select: keep[r] = hits[r] >= min_hits and hits[r] >= min_fraction *
+    sampled[r] (in double), the rule of `kmc --recruit`, as int32 [n] of ones and zeros
+    on the device.  sampled may be None when min_fraction is 0.  Returns (keep,
+    num_kept int64 [1] or None)."""
+    import torch
+    n = int(hits.numel())
+    with _on(stream):
+        dv = torch.device("cuda", torch.cuda.current_device())
+        keep = out if out is not None else torch.empty(n, dtype=torch.int32, device=dv)
+        if isinstance(count, torch.Tensor):
+            kept = count
+        else:
+            kept = torch.empty(1, dtype=torch.int64, device=dv) if count else None
+    _check(lib().kmc_match_select(_dptr(sampled) if n else None, _dptr(hits) if n else None, n, int(min_hits),
+                                  float(min_fraction), _dptr(keep) if n else None, _dptr(kept), _stream(stream)),
+           "kmc_match_select")
+    return keep, kept
+
+
 def spectrum_summarize(hist, limit):
     """kmc_spectrum_summarize of a spectrum (SketchAccum.spectrum's hist, a tensor or a
     host array of uint64 bit patterns) and its limit (stats[1]): a namedtuple of the
@@ -1171,11 +1241,14 @@ def _copy_out(d, nbytes, ix, nseqs, free):
 # ---------------------------------------------------------------------------
 # FASTQ (strict four-line; include/kmc.h)
 # ---------------------------------------------------------------------------
-def parse_fastq_device(raw, final=True, stream=None):
+def parse_fastq_device(raw, final=True, stream=None, raw_indices=False):
     """GPU FASTQ parse (kmc_fastq_parse_device) of raw bytes in a uint8 device tensor:
     (data uint8 tensor, indices int64 tensor [n+1], consumed) for the complete
     records of raw; without `final` the bytes from `consumed` on belong to a record
-    that is not complete yet.  KmcError.record tells where malformed input is."""
+    that is not complete yet.  KmcError.record tells where malformed input is.
+    With raw_indices (kmc_fastq_parse_device_ex) a fourth value follows: the int64
+    tensor [n+1] of the records' raw offsets, record r's full text being
+    raw[raw_indices[r]:raw_indices[r+1]]."""
     import torch
     n = int(raw.numel())
     with _on(stream):
@@ -1189,14 +1262,22 @@ def parse_fastq_device(raw, final=True, stream=None):
     while True:
         with _on(stream):
             idx = torch.empty(cap, dtype=torch.int64, device=raw.device)
+            ridx = torch.empty(cap, dtype=torch.int64, device=raw.device) if raw_indices else None
         ns, nb, used = _U64(0), _U64(0), _U64(0)
-        rc = lib().kmc_fastq_parse_device(_dptr(raw) if n else None, n, 1 if final else 0, _dptr(data), cap_data,
-                                          _dptr(idx), cap, ctypes.byref(ns), ctypes.byref(nb), ctypes.byref(used),
-                                          _stream(stream))
+        if raw_indices:
+            rc = lib().kmc_fastq_parse_device_ex(_dptr(raw) if n else None, n, 1 if final else 0, _dptr(data), cap_data,
+                                                 _dptr(idx), cap, ctypes.byref(ns), ctypes.byref(nb), ctypes.byref(used),
+                                                 _dptr(ridx), _stream(stream))
+        else:
+            rc = lib().kmc_fastq_parse_device(_dptr(raw) if n else None, n, 1 if final else 0, _dptr(data), cap_data,
+                                              _dptr(idx), cap, ctypes.byref(ns), ctypes.byref(nb), ctypes.byref(used),
+                                              _stream(stream))
         if rc == KMC_ERR_CAPACITY and ns.value + 1 > cap:
             cap = int(ns.value) + 1
             continue
         _check(rc, "kmc_fastq_parse_device", ns.value)
+        if raw_indices:
+            return data[:nb.value], idx[:ns.value + 1], int(used.value), ridx[:ns.value + 1]
         return data[:nb.value], idx[:ns.value + 1], int(used.value)
 
 
@@ -1218,18 +1299,37 @@ class FastqReader:
     indices) or None after the last batch; iterating yields the batches.  By default
     a batch is a pair of new tensors (copies); with copy=False it is a pair of views
     of the reader's own buffers, valid until the next call, whose writes are ordered
-    on `stream` behind whatever the caller enqueued there.
+    on `stream` behind whatever the caller enqueued there.  With keep_raw=True
+    (KMC_FASTQ_KEEP_RAW) raw() returns the last batch's raw text and the records'
+    raw offsets, what select_records cuts the reads themselves from.
 
         with kmc.FastqReader(path, 1 << 28) as rd:
             for data, indices in rd:
                 kmc.sketch_screen_count(index, data, indices, k)"""
 
-    def __init__(self, path, batch_bytes=0, stream=None, copy=True):
+    def __init__(self, path, batch_bytes=0, stream=None, copy=True, keep_raw=False):
         self._h = _P()
         self._stream = stream
         self._copy = copy
         self._views = None
-        _check(lib().kmc_fastq_open(os.fsencode(path), int(batch_bytes), ctypes.byref(self._h)), "kmc_fastq_open")
+        self._seqs = 0
+        if keep_raw:
+            _check(lib().kmc_fastq_open_ex(os.fsencode(path), int(batch_bytes), KMC_FASTQ_KEEP_RAW, ctypes.byref(self._h)),
+                   "kmc_fastq_open_ex")
+        else:
+            _check(lib().kmc_fastq_open(os.fsencode(path), int(batch_bytes), ctypes.byref(self._h)), "kmc_fastq_open")
+
+    def raw(self):
+        """kmc_fastq_raw: (raw uint8 tensor [raw_bytes], raw_indices int64 tensor [n+1]) of
+        the last batch, or None after the last batch: views of the reader's own buffers,
+        valid until the next call on the reader (clone them to keep them)."""
+        if not self._h:
+            raise ValueError("the reader is closed")
+        d, ix, nb = _P(), _P(), _U64(0)
+        _check(lib().kmc_fastq_raw(self._h, ctypes.byref(d), ctypes.byref(nb), ctypes.byref(ix)), "kmc_fastq_raw")
+        if not d.value:
+            return None
+        return (_DeviceView(d.value, nb.value, "|u1").tensor(), _DeviceView(ix.value, self._seqs + 1, "<i8").tensor())
 
     def next_batch(self):
         if not self._h:
@@ -1239,6 +1339,7 @@ class FastqReader:
         rc = lib().kmc_fastq_next(self._h, ctypes.byref(d), ctypes.byref(nb), ctypes.byref(ix), ctypes.byref(ns),
                                   _stream(self._stream))
         _check(rc, "kmc_fastq_next", ns.value)
+        self._seqs = int(ns.value)
         if not d.value:
             return None
         if self._copy:

@@ -1148,6 +1148,101 @@ KMC_API int kmc_fastq_next(kmc_fastq_reader *rd, const char **data, uint64_t *da
                    uint64_t *num_seqs, hipStream_t stream);
 KMC_API void kmc_fastq_close(kmc_fastq_reader *rd);
 
+/* Where a record's raw text is.
+ * kmc_fastq_parse_device_ex is kmc_fastq_parse_device with one more output:
+ *   raw_indices  device int64[indices_cap], may be NULL (then it is
+ *                kmc_fastq_parse_device, bit for bit).  raw_indices[r] is the raw
+ *                offset of the '@' of record r; raw_indices[*num_seqs] is the offset
+ *                just past the last complete record's fourth line: its '\n' included
+ *                when there is one, raw_bytes when a final input ends without one.
+ *                Records are contiguous in strict four-line FASTQ, so the full text
+ *                of record r, line ends of either kind included, is
+ *                raw[raw_indices[r], raw_indices[r+1]): (raw, raw_indices, num_seqs)
+ *                is a record buffer for kmc_select_records.  *num_seqs + 1 entries
+ *                are written; nothing when indices_cap is too small
+ *                (KMC_ERR_CAPACITY); nothing is promised about them on KMC_ERR_FORMAT.
+ * kmc_fastq_open_ex is kmc_fastq_open with flags; flags == 0 is kmc_fastq_open, any
+ * bit but the ones below is KMC_ERR_INVALID_ARG.
+ *   KMC_FASTQ_KEEP_RAW  the reader also keeps the raw offsets of every batch (8 more
+ *                       bytes of device memory per record; nothing else changes)
+ * kmc_fastq_raw returns the last batch's raw text and its num_seqs + 1 offsets: device
+ * pointers the reader owns, valid exactly as long as that batch's data and indices
+ * (until the next call on the reader, whose writes are stream-ordered behind the
+ * caller's work); *raw_bytes = raw_indices[num_seqs] as a host value (the bytes
+ * behind it, blank lines at the end of a file, belong to no record).
+ * KMC_ERR_INVALID_ARG for a reader opened without KMC_FASTQ_KEEP_RAW, for null
+ * arguments, and before the first kmc_fastq_next; a failed reader returns its code.
+ * After the last batch (kmc_fastq_next returned *data == NULL): KMC_OK, *raw = NULL,
+ * *raw_indices = NULL, *raw_bytes = 0.  No device is touched. */
+#define KMC_FASTQ_KEEP_RAW 1u
+KMC_API int kmc_fastq_parse_device_ex(const char *raw, uint64_t raw_bytes, int final, char *data, uint64_t data_cap,
+                              int64_t *indices, uint64_t indices_cap, uint64_t *num_seqs, uint64_t *data_bytes,
+                              uint64_t *consumed, int64_t *raw_indices, hipStream_t stream);
+KMC_API int kmc_fastq_open_ex(const char *path, uint64_t batch_bytes, unsigned flags, kmc_fastq_reader **out);
+KMC_API int kmc_fastq_raw(kmc_fastq_reader *rd, const char **raw, uint64_t *raw_bytes, const int64_t **raw_indices);
+
+/* ------------------------------------------------------------------------ */
+/* Selecting records (no reference counterpart): the reads that matched, or the reads
+ * that did not, as one contiguous buffer in input order.
+ *
+ * kmc_select_records: stable compaction of byte records on the device.
+ *   Records   record r is src[offsets[r], offsets[r+1]); offsets is a device
+ *             int64[num_recs + 1], ascending, its values clamped to [0, src_bytes] on
+ *             the device; offsets that do not ascend give an unspecified result and
+ *             no stray access.  Records may be empty.  Bytes before offsets[0] and at
+ *             or after offsets[num_recs] belong to no record and are dropped.  src may
+ *             have any alignment (and so may dst).
+ *   Selection keep is a device uint32[num_recs]; record r is selected iff
+ *             (keep[r] != 0) != (invert != 0).  Any non-zero value counts, so the
+ *             hits of kmc_match_from_accum are a valid keep.
+ *   dst       receives the selected records' bytes concatenated in input order, bit
+ *             for bit, nothing added or removed.
+ *   dst_offsets  may be NULL; otherwise a device int64[num_recs + 1] of which the
+ *             first kept + 1 entries are written: entry i is where the i-th selected
+ *             record starts in dst, entry kept is the number of bytes kept.  So (dst,
+ *             dst_offsets, kept) is again a record buffer under the convention above
+ *             and can go straight into kmc_sketch_accum_add, kmc_match_from_accum and
+ *             the rest.
+ *   counts    required, device uint64[2]: the selected records and their bytes; both
+ *             are written whether or not the bytes fit.
+ *   Capacity  dst_cap >= src_bytes always suffices.  Nothing is ever written at or
+ *             beyond dst + dst_cap; when counts[1] > dst_cap the content of dst is
+ *             unspecified and the caller calls again.  dst may be NULL with dst_cap ==
+ *             0: the count-only call (the pass over the source bytes is not launched).
+ *   Overlap   dst must not overlap src: KMC_ERR_INVALID_ARG when [dst, dst + dst_cap)
+ *             and [src, src + src_bytes) share a byte.
+ *   workspace device scratch of kmc_select_records_workspace_size() bytes, 8-byte
+ *             aligned (KMC_ERR_WORKSPACE when smaller, then KMC_ERR_ALIGNMENT), or NULL
+ *             for a library-owned buffer under kmc_pair_distances' rule
+ *             (NULL-workspace calls on a device must not overlap).  The size, with
+ *             every array rounded up to 256 bytes: 4 n + 8 n + 8 (n + 1) + 8 (n + 1)
+ *             + 8 (ceil(n / 4096) + 1) for n = num_recs; src_bytes does not enter.
+ *             The query takes host numbers only and returns 0 for arguments the call
+ *             refuses.
+ * Asynchronous on `stream`, no host read-back; the launches depend on the host
+ * arguments only; nothing a former call left in the workspace is read.
+ * KMC_ERR_INVALID_ARG, judged before any device is touched: null offsets, keep or
+ * counts; null src with src_bytes > 0; null dst with dst_cap > 0; num_recs above 2^40;
+ * src_bytes of 2^62 or more.  num_recs == 0: KMC_OK, counts = {0, 0} and
+ * dst_offsets[0] = 0 when given. */
+KMC_API size_t kmc_select_records_workspace_size(uint64_t num_recs, uint64_t src_bytes);
+KMC_API int kmc_select_records(const char *src, const int64_t *offsets, uint64_t num_recs, uint64_t src_bytes,
+                       const uint32_t *keep, int invert, char *dst, uint64_t dst_cap, int64_t *dst_offsets,
+                       uint64_t *counts, void *workspace, size_t workspace_bytes, hipStream_t stream);
+
+/* kmc_match_select: the rule by which `kmc --recruit` lists a record, on the device:
+ *   keep[r] = hits[r] >= min_hits && (double)hits[r] >= min_fraction * (double)sampled[r]
+ * written as 1 or 0: one IEEE double product and one compare, so host and device
+ * agree bit for bit.  sampled, hits (kmc_match_from_accum's) and keep are device
+ * uint32[num_seqs]; sampled may be NULL when min_fraction == 0; num_kept is a device
+ * uint64 (the number of ones) and may be NULL.  Match, select and kmc_select_records
+ * chain on one stream without the host in between.  Asynchronous on `stream`, no
+ * workspace.  KMC_ERR_INVALID_ARG, before any device is touched, for a min_fraction
+ * outside [0, 1] or NaN, for null hits or keep with num_seqs > 0, for a null sampled
+ * with num_seqs > 0 and min_fraction above 0, and for num_seqs above 2^40. */
+KMC_API int kmc_match_select(const uint32_t *sampled, const uint32_t *hits, uint64_t num_seqs, uint32_t min_hits,
+                     double min_fraction, uint32_t *keep, uint64_t *num_kept, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
