@@ -37,7 +37,10 @@
 // and every record of FILE is matched against it (kmc_match_from_accum -> read_matches.tsv,
 // read_matches_summary.tsv); --write-recruited / --write-rest: the listed records, or the others, as
 // the raw FASTQ text of the input (kmc_match_select, kmc_select_records on the reader's raw batch ->
-// recruited_<f>.fastq, rest_<f>.fastq).
+// recruited_<f>.fastq, rest_<f>.fastq).  --classify: every input file is one source; after the adds
+// the inputs are read again and labelled (kmc_label_accum), and the match becomes
+// kmc_classify_from_accum -> read_sources.tsv, read_sources_summary.tsv; --write-sources: the records
+// assigned to each source (kmc_classify_select, kmc_select_records -> source_<f>_<g>.fastq).
 // GPU only: there is no CPU counting path here.
 #include <hip/hip_runtime.h>
 
@@ -48,6 +51,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <strings.h>
+#include <sys/stat.h>
 #include <memory>
 #include <string>
 #include <thread>
@@ -105,6 +109,10 @@ struct Options {
     double min_fraction = 0.0;         // --min-fraction F: and hits >= F * sampled
     bool min_hits_set = false, min_fraction_set = false;
     bool write_recruited = false, write_rest = false;  // --write-recruited, --write-rest: the reads themselves
+    bool classify = false;       // --classify: every input file is one source of the set's k-mers
+    long min_margin = 1;         // --min-margin D: a record is assigned when source_hits - next_hits >= D
+    bool min_margin_set = false;
+    bool write_sources = false;  // --write-sources: the assigned reads themselves, per source
 };
 
 // auto: FASTQ exactly when the name ends in .fq or .fastq, whatever the case
@@ -131,6 +139,8 @@ void usage(FILE *f) {
             "       kmc --canonical --sketch S [--sketch-direct] [--per-file] --pairs D [--query q.fasta] [options] <input.fasta> ...\n"
             "       kmc -k K --canonical --recruit reads.fastq [--recruit more.fq] [--min-abundance M] [--min-hits H]\n"
             "           [--min-fraction F] --accum-slots L [--batch BYTES] [--write-recruited] [--write-rest] [options]\n"
+            "       kmc -k K --canonical --recruit reads.fastq --classify [--min-margin D] [--write-sources]\n"
+            "           --accum-slots L [recruit options] host.fa phage.fa ...\n"
             "           <host.fasta> <phage.fasta> ...\n"
             "       kmc synth OUT.fa RECORDS LENGTH [SEED]   (benchmark input, SURVEY.md 8(d))\n"
             "  -k K              k-mer length (default %d, the reference's K); dense path 1..%d,\n"
@@ -279,6 +289,22 @@ void usage(FILE *f) {
             "                    kmc_select_records on each batch's raw text, then device to file)\n"
             "  --write-rest      the same for the records that are not listed: <out>/rest_<f>.fastq (depletion).\n"
             "                    Either option holds one more raw batch of device memory (--batch), shared by both\n"
+            "  --classify        with --recruit: every input file is one source, in command-line order (32 at most,\n"
+            "                    regular files: they are read twice).  After all adds the inputs are read again and\n"
+            "                    the set's k-mers labelled with the sources that hold them (kmc_label_accum);\n"
+            "                    per batch kmc_classify_from_accum replaces the match.  <out>/read_sources.tsv gets,\n"
+            "                    after a header line, the lines of read_matches.tsv with three more columns: source\n"
+            "                    (the source with the most hits, the smaller number on a tie, - for none),\n"
+            "                    source_hits (the hits that source holds) and next_hits (the most any other source\n"
+            "                    holds).  <out>/read_sources_summary.tsv gets, after a header line, per FILE one line\n"
+            "                    file, source, path, best, assigned per source (best: the listed records with that\n"
+            "                    source; assigned: those of them with source_hits - next_hits >= D) and one line\n"
+            "                    with source - and path - (best: the listed records with no source; assigned: the\n"
+            "                    listed records assigned to none).  The other outputs are as without --classify\n"
+            "  --min-margin D    with --classify: D in 0..4294967295, default 1: a tie is assigned to nobody\n"
+            "  --write-sources   with --classify, every FILE in FASTQ: <out>/source_<f>_<g>.fastq gets the records of\n"
+            "                    FILE assigned to source g as the raw bytes of the input, in input order\n"
+            "                    (kmc_classify_select, kmc_select_records)\n"
             "  --softmask        with --canonical: lowercase acgt count as bases\n"
             "  --host-loader     parse the FASTA on the host (kmc_fasta_load) instead of on the GPU\n"
             "                    (kmc_fasta_load_device); --gpus > 1 always uses the host buffer\n"
@@ -434,6 +460,19 @@ int parse(int argc, char **argv, Options &o) {
             o.write_recruited = true;
         } else if (a == "--write-rest") {
             o.write_rest = true;
+        } else if (a == "--classify") {
+            o.classify = true;
+        } else if (a == "--write-sources") {
+            o.write_sources = true;
+        } else if (a == "--min-margin") {
+            char *end = nullptr;
+            const char *v = next("--min-margin");
+            o.min_margin = strtol(v, &end, 10);
+            o.min_margin_set = true;
+            if (end == v || *end != '\0' || o.min_margin < 0 || o.min_margin > (long)UINT32_MAX) {
+                fprintf(stderr, "kmc: --min-margin must be in 0..%u\n", UINT32_MAX);
+                return usage(stderr), 2;
+            }
         } else if (a == "--softmask") {
             o.softmask = true;
         } else if (a == "--host-loader") {
@@ -460,6 +499,14 @@ int parse(int argc, char **argv, Options &o) {
     }
     if ((o.write_recruited || o.write_rest) && o.recruit.empty()) {
         fprintf(stderr, "kmc: --write-recruited and --write-rest write the reads of --recruit\n");
+        return usage(stderr), 2;
+    }
+    if ((o.classify || o.min_margin_set || o.write_sources) && o.recruit.empty()) {
+        fprintf(stderr, "kmc: --classify, --min-margin and --write-sources tell the reads of --recruit apart\n");
+        return usage(stderr), 2;
+    }
+    if ((o.min_margin_set || o.write_sources) && !o.classify) {
+        fprintf(stderr, "kmc: --min-margin and --write-sources need --classify\n");
         return usage(stderr), 2;
     }
     if (!o.recruit.empty()) {
@@ -493,6 +540,30 @@ int parse(int argc, char **argv, Options &o) {
                                     "(--format, or a .fq / .fastq name)\n", f.c_str());
                     return usage(stderr), 2;
                 }
+        if (o.write_sources)
+            for (const std::string &f : o.recruit)
+                if (!is_fastq(o, f)) {
+                    fprintf(stderr, "kmc: --write-sources writes FASTQ records: %s is not FASTQ (--format, or a .fq / "
+                                    ".fastq name)\n", f.c_str());
+                    return usage(stderr), 2;
+                }
+        if (o.classify) {
+            if (1 + o.more_inputs.size() > KMC_CLASSIFY_MAX_SOURCES) {
+                fprintf(stderr, "kmc: --classify tells %d sources apart at most: %zu input files\n",
+                        KMC_CLASSIFY_MAX_SOURCES, 1 + o.more_inputs.size());
+                return usage(stderr), 2;
+            }
+            // the inputs are read twice (add, then label): nothing is read from one that cannot be
+            std::vector<std::string> inputs{o.input};
+            inputs.insert(inputs.end(), o.more_inputs.begin(), o.more_inputs.end());
+            for (const std::string &f : inputs) {
+                struct stat sb;
+                if (stat(f.c_str(), &sb) == 0 && !S_ISREG(sb.st_mode)) {
+                    fprintf(stderr, "kmc: --classify reads every input file twice: %s is not a regular file\n", f.c_str());
+                    return 2;
+                }
+            }
+        }
     }
     if ((o.sketch > 0 || o.min_count_set) && !o.canonical) {
         fprintf(stderr, "kmc: --sketch and --min-count need --canonical\n");
@@ -1149,6 +1220,18 @@ int run_recruit(const Options &o, hipStream_t st) {
         if (!o.quiet)
             printf("Set %zu: %s: %" PRIu64 " records, %" PRIu64 " batches\n", f, files[f].c_str(), records, batches);
     }
+    if (o.classify)  // every add is done: the inputs once more, file f is source f
+        for (size_t f = 0; f < files.size(); ++f) {
+            uint64_t batches = 0;
+            KMCCHK(kmc_label_accum(acc, nullptr, nullptr, 0, 0, (uint32_t)f, st));  // (a file of no record)
+            const int e = for_each_batch(o, files[f], st, &batches,
+                                         [&](const char *d, const int64_t *idx, uint64_t ns, uint64_t nb) {
+                KMCCHK(kmc_label_accum(acc, d, idx, ns, nb, (uint32_t)f, st));
+                HIPCHK(hipStreamSynchronize(st));  // before the batch's buffers go
+                return 0;
+            });
+            if (e) return e;
+        }
     // the level only says whether `limit` is its bound or a refused k-mer's hash (the warning below);
     // limit and exact themselves are always the library's
     const uint32_t j = accum_level(added, lg);
@@ -1158,6 +1241,19 @@ int run_recruit(const Options &o, hipStream_t st) {
     if (!f_rec || !f_sum) return fprintf(stderr, "kmc: cannot write %s/read_matches.tsv\n", o.out_dir.c_str()), 1;
     fprintf(f_rec.get(), "file\trecord\twindows\tsampled\thits\n");
     fprintf(f_sum.get(), "file\tpath\trecords\tlisted\tlimit\texact\tsampled\thits\n");
+    // --classify: the votes of one batch (best, best_hits, next_hits: three arrays of `cap`) and their files
+    const uint32_t nsrc = o.classify ? (uint32_t)files.size() : 0u;
+    File f_src, f_ssum;
+    DevBuf<uint32_t> d_vote;
+    std::vector<uint32_t> vote;
+    if (o.classify) {
+        f_src.reset(fopen((o.out_dir + "/read_sources.tsv").c_str(), "w"));
+        f_ssum.reset(fopen((o.out_dir + "/read_sources_summary.tsv").c_str(), "w"));
+        if (!f_src || !f_ssum) return fprintf(stderr, "kmc: cannot write %s/read_sources.tsv\n", o.out_dir.c_str()), 1;
+        fprintf(f_src.get(), "file\trecord\twindows\tsampled\thits\tsource\tsource_hits\tnext_hits\n");
+        fprintf(f_ssum.get(), "file\tsource\tpath\tbest\tassigned\n");
+        HIPCHK(dev_alloc(d_vote, 3));
+    }
     DevBuf<uint32_t> d_out;  // windows, sampled, hits of one batch: three arrays of `cap`
     DevBuf<uint64_t> d_stats;
     DevBuf<int64_t> d_none;  // the offsets of a call of no record
@@ -1174,11 +1270,12 @@ int run_recruit(const Options &o, hipStream_t st) {
     HIPCHK(hipStreamSynchronize(st));
     bool lost = false;
     // --write-recruited, --write-rest: the flags and the kept bytes of one batch, and the way to the file
-    const bool writing = o.write_recruited || o.write_rest;
+    const bool writing = o.write_recruited || o.write_rest || o.write_sources;
     DevBuf<uint32_t> d_keep;
     DevBuf<char> d_sel;
     DevBuf<uint64_t> d_counts;
-    uint64_t keep_cap = 0, sel_cap = 0;
+    DevBuf<uint32_t> d_assign;  // --write-sources: the flags of one source
+    uint64_t keep_cap = 0, sel_cap = 0, assign_cap = 0;
     kmc::Drainer drainer;
     if (writing) {
         HIPCHK(dev_alloc(d_counts, 2));
@@ -1197,15 +1294,37 @@ int run_recruit(const Options &o, hipStream_t st) {
             fd[w].reset(open(name[w].c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666));
             if (fd[w].get() < 0) return fprintf(stderr, "kmc: cannot write %s\n", name[w].c_str()), 1;
         }
+        // --classify: per source the listed records with it as best and those of them assigned; [nsrc]: to none
+        std::vector<uint64_t> n_best(nsrc + 1, 0), n_assigned(nsrc + 1, 0), src_written(nsrc, 0);
+        std::vector<Fd> src_fd(o.write_sources ? nsrc : 0);
+        std::vector<std::string> src_name(src_fd.size());
+        for (size_t g = 0; g < src_fd.size(); ++g) {
+            src_name[g] = o.out_dir + "/source_" + std::to_string(f) + "_" + std::to_string(g) + ".fastq";
+            src_fd[g].reset(open(src_name[g].c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666));
+            if (src_fd[g].get() < 0) return fprintf(stderr, "kmc: cannot write %s\n", src_name[g].c_str()), 1;
+        }
         kmc_fastq_reader *rd = nullptr;
         const int e = for_each_batch(o, o.recruit[f], st, &batches,
                                      [&](const char *d, const int64_t *idx, uint64_t ns, uint64_t nb) {
             if (ns > cap) {
                 HIPCHK(dev_alloc(d_out, 3 * ns));
+                if (o.classify) HIPCHK(dev_alloc(d_vote, 3 * ns));
                 cap = ns;
             }
             uint32_t *d_win = d_out.get(), *d_smp = d_win + cap, *d_hit = d_smp + cap;
-            KMCCHK(kmc_match_from_accum(acc, d, idx, ns, nb, M, d_win, d_smp, d_hit, d_stats.get(), st));
+            uint32_t *d_best = d_vote.get(), *d_bh = d_best + cap, *d_nh = d_bh + cap;  // (--classify only)
+            if (o.classify) {
+                KMCCHK(kmc_classify_from_accum(acc, d, idx, ns, nb, nsrc, M, d_win, d_smp, d_hit, d_best, d_bh, d_nh, nullptr,
+                                               d_stats.get(), nullptr, 0, st));
+                vote.resize(3 * ns);
+                if (ns > 0) {
+                    HIPCHK(hipMemcpyAsync(vote.data(), d_best, ns * 4, hipMemcpyDeviceToHost, st));
+                    HIPCHK(hipMemcpyAsync(vote.data() + ns, d_bh, ns * 4, hipMemcpyDeviceToHost, st));
+                    HIPCHK(hipMemcpyAsync(vote.data() + 2 * ns, d_nh, ns * 4, hipMemcpyDeviceToHost, st));
+                }
+            } else {
+                KMCCHK(kmc_match_from_accum(acc, d, idx, ns, nb, M, d_win, d_smp, d_hit, d_stats.get(), st));
+            }
             out.resize(3 * ns);
             uint64_t stats[4] = {0, 0, 0, 0};
             if (ns > 0) {
@@ -1240,6 +1359,24 @@ int run_recruit(const Options &o, hipStream_t st) {
                     KMCCHK(wrc);
                     written[w] += counts[0];
                 }
+                // --write-sources: the listed records assigned to source g, through the same way
+                for (size_t g = 0; g < src_fd.size() && ns > 0; ++g) {
+                    uint64_t counts[2] = {0, 0};
+                    if (ns > assign_cap) {
+                        HIPCHK(dev_alloc(d_assign, ns));
+                        assign_cap = ns;
+                    }
+                    KMCCHK(kmc_classify_select(d_keep.get(), d_best, d_bh, d_nh, ns, (uint32_t)g, (uint32_t)o.min_margin,
+                                               d_assign.get(), nullptr, st));
+                    KMCCHK(kmc_select_records(d_raw, d_ridx, ns, raw_bytes, d_assign.get(), 0, d_sel.get(), sel_cap, nullptr,
+                                              d_counts.get(), nullptr, 0, st));
+                    HIPCHK(hipMemcpyAsync(counts, d_counts.get(), sizeof counts, hipMemcpyDeviceToHost, st));
+                    HIPCHK(hipStreamSynchronize(st));
+                    const int wrc = drainer.drain(src_fd[g].get(), d_sel.get(), counts[1], st);
+                    if (wrc == KMC_ERR_IO) return fprintf(stderr, "kmc: cannot write %s\n", src_name[g].c_str()), 1;
+                    KMCCHK(wrc);
+                    src_written[g] += counts[0];
+                }
             }
             HIPCHK(hipStreamSynchronize(st));  // before the batch's buffers go
             total[0] = stats[0];
@@ -1251,6 +1388,15 @@ int run_recruit(const Options &o, hipStream_t st) {
                 if (hit >= (uint64_t)o.min_hits && (double)hit >= o.min_fraction * (double)smp) {
                     fprintf(f_rec.get(), "%zu\t%" PRIu64 "\t%u\t%u\t%u\n", f, records + r, win, smp, hit);
                     ++listed;
+                    if (o.classify) {  // kmc_classify_select's rule
+                        const uint32_t best = vote[r], bh = vote[ns + r], nh = vote[2 * ns + r];
+                        const bool none = best >= nsrc;  // KMC_CLASSIFY_NONE
+                        fprintf(f_src.get(), "%zu\t%" PRIu64 "\t%u\t%u\t%u\t", f, records + r, win, smp, hit);
+                        if (none) fprintf(f_src.get(), "-\t%u\t%u\n", bh, nh);
+                        else fprintf(f_src.get(), "%u\t%u\t%u\n", best, bh, nh);
+                        ++n_best[none ? nsrc : best];
+                        ++n_assigned[!none && bh - nh >= (uint32_t)o.min_margin ? best : nsrc];
+                    }
                 }
             }
             records += ns;
@@ -1266,6 +1412,18 @@ int run_recruit(const Options &o, hipStream_t st) {
         }
         fprintf(f_sum.get(), "%zu\t%s\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t%d\t%" PRIu64 "\t%" PRIu64 "\n", f,
                 o.recruit[f].c_str(), records, listed, total[1], (int)total[0], total[2], total[3]);
+        for (size_t g = 0; g < src_fd.size(); ++g) {
+            if (close(src_fd[g].release()) != 0) return fprintf(stderr, "kmc: cannot write %s\n", src_name[g].c_str()), 1;
+            if (src_written[g] != n_assigned[g])  // the host's rule and the device's are one
+                return fprintf(stderr, "kmc: %s holds %" PRIu64 " records, read_sources.tsv assigns %" PRIu64 "\n",
+                               src_name[g].c_str(), src_written[g], n_assigned[g]), 1;
+        }
+        if (o.classify) {
+            for (uint32_t g = 0; g < nsrc; ++g)
+                fprintf(f_ssum.get(), "%zu\t%u\t%s\t%" PRIu64 "\t%" PRIu64 "\n", f, g, files[g].c_str(), n_best[g],
+                        n_assigned[g]);
+            fprintf(f_ssum.get(), "%zu\t-\t-\t%" PRIu64 "\t%" PRIu64 "\n", f, n_best[nsrc], n_assigned[nsrc]);
+        }
         if (!o.quiet)
             printf("Recruit %zu: %s: %" PRIu64 " records, %" PRIu64 " batches, %" PRIu64 " listed, j %u, exact %d\n", f,
                    o.recruit[f].c_str(), records, batches, listed, j, (int)total[0]);
@@ -1276,6 +1434,8 @@ int run_recruit(const Options &o, hipStream_t st) {
                         "than its level's (read_matches_summary.tsv); raise --accum-slots to keep more\n", lg);
     if ((fclose(f_rec.release()) != 0) | (fclose(f_sum.release()) != 0))
         return fprintf(stderr, "kmc: cannot write %s/read_matches.tsv\n", o.out_dir.c_str()), 1;
+    if (o.classify && ((fclose(f_src.release()) != 0) | (fclose(f_ssum.release()) != 0)))
+        return fprintf(stderr, "kmc: cannot write %s/read_sources.tsv\n", o.out_dir.c_str()), 1;
     return 0;
 }
 

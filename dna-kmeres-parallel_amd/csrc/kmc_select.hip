@@ -1,6 +1,7 @@
 // kmc_select.hip — stable compaction of byte records on the device
 // (kmc_select_records) and the selection rule of `kmc --recruit` as a device call
-// (kmc_match_select).  No reference counterpart: the reference keeps no read text.
+// (kmc_match_select), with the assignment rule of `kmc --recruit --classify` beside it
+// (kmc_classify_select).  No reference counterpart: the reference keeps no read text.
 //
 // The selected bytes are a monotone compaction of the source bytes, the situation
 // of fq_write_kernel (kmc_fastq_gpu.hip), and the shape is the same.  Passes:
@@ -194,6 +195,25 @@ __global__ __launch_bounds__(kSelBlock) void match_select_kernel(const uint32_t 
     }
 }
 
+// kmc_classify_select (keep may be listed: a thread reads its word before it writes it)
+__global__ __launch_bounds__(kSelBlock) void classify_select_kernel(const uint32_t *listed, const uint32_t *best,
+                                                                   const uint32_t *best_hits, const uint32_t *next_hits,
+                                                                   uint64_t n, uint32_t source, uint32_t min_margin,
+                                                                   uint32_t *keep, uint64_t *num_kept) {
+    uint64_t mine = 0;
+    for (uint64_t r = (uint64_t)blockIdx.x * kSelBlock + threadIdx.x; r < n; r += (uint64_t)gridDim.x * kSelBlock) {
+        const bool in = listed ? listed[r] != 0u : true;
+        const bool k = in && best[r] == source && best_hits[r] - next_hits[r] >= min_margin;
+        keep[r] = k ? 1u : 0u;
+        mine += k;
+    }
+    if (num_kept) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
+        if ((threadIdx.x & 63) == 0 && mine) atomicAdd((unsigned long long *)num_kept, (unsigned long long)mine);
+    }
+}
+
 unsigned sel_grid(uint64_t items, uint64_t per_block) {
     const uint64_t b = (items + per_block - 1) / per_block;
     return (unsigned)std::min<uint64_t>(std::max<uint64_t>(b, 1), kSelMaxGrid);
@@ -295,5 +315,19 @@ extern "C" int kmc_match_select(const uint32_t *sampled, const uint32_t *hits, u
     if (num_seqs == 0) return 0;
     hipLaunchKernelGGL(match_select_kernel, dim3(sel_grid(num_seqs, kSelBlock)), dim3(kSelBlock), 0, stream, sampled, hits,
                        num_seqs, min_hits, min_fraction, keep, num_kept);
+    return (int)hipGetLastError();
+}
+
+extern "C" int kmc_classify_select(const uint32_t *listed, const uint32_t *best, const uint32_t *best_hits,
+                                   const uint32_t *next_hits, uint64_t num_seqs, uint32_t source, uint32_t min_margin,
+                                   uint32_t *keep, uint64_t *num_kept, hipStream_t stream) {
+    if (source >= KMC_CLASSIFY_MAX_SOURCES) return KMC_ERR_INVALID_ARG;
+    if (num_seqs > 0 && (!best || !best_hits || !next_hits || !keep)) return KMC_ERR_INVALID_ARG;
+    if (num_seqs > kSelMaxRecs) return KMC_ERR_INVALID_ARG;
+    hipError_t he;
+    if (num_kept && (he = hipMemsetAsync(num_kept, 0, 8, stream))) return (int)he;
+    if (num_seqs == 0) return 0;
+    hipLaunchKernelGGL(classify_select_kernel, dim3(sel_grid(num_seqs, kSelBlock)), dim3(kSelBlock), 0, stream, listed,
+                       best, best_hits, next_hits, num_seqs, source, min_margin, keep, num_kept);
     return (int)hipGetLastError();
 }

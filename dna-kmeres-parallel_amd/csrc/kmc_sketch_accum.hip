@@ -83,6 +83,35 @@
 //           a lane's sampled windows are one probe (add_runs' rule), and stats[2..3]
 //           take one 64-bit add per wave.
 //
+//   label   kmc_label_accum: which source holds a key, a uint32 bitmask per slot
+//           of the active table in a second allocation of 4 C bytes that the first
+//           label call makes.  The walk is add's (for_each_piece, for_each_chunk); a
+//           sampled window (all, or hash < the same `limit`) is looked up with match's
+//           probe (table_slot) and its slot's label takes a vector atomic OR of the
+//           source's bit, once per run of equal keys.  The tables and the header are
+//           only read.  Whether the labels describe the table is host state: an add of
+//           records and a reset drop them, and the next label call clears the array on
+//           its stream first.
+//
+//   classify  kmc_classify_from_accum: match's wave walk, and per record the number of
+//           hit windows whose label has bit g, for every source g, with the best source,
+//           its score and the runner-up's.  A lane adds the labels of its chunk's hit
+//           windows into five bit planes (16 windows: counts of 0 .. 16 per source), and
+//           once per chunk adds the count of every source it saw to its wave's score row
+//           in LDS (32 words per wave, LDS atomics).  A piece ends with the wave's lanes
+//           0 .. 31 taking the row back (and zeroing it) and a wave-wide argmax; no
+//           barrier: the waves of a workgroup stay independent.  A record that lies
+//           wholly in the wave's range is stored; at most two pieces of a range are not
+//           whole records, its first (cut at the start) and its last (cut at the end),
+//           and their rows go to the workspace: two rows per wave of the launch, each
+//           tagged with its record, the tags invalidated on the stream before the walk.
+//           A record's first piece is always a range's last one, so the fix-up kernel
+//           (classify_cut_kernel) has one workgroup per wave whose last row is tagged:
+//           it adds the first rows of the following waves with the same tag, 32 lanes a
+//           row, until a row of another record shows, and writes the record's results.
+//           A piece with no hit skips the votes and the fold; best, best_hits, next_hits
+//           and scores are cleared to "none" on the stream first, as match's outputs are.
+//
 // The device code trusts the host arguments only: every slot index is masked, every
 // chain is bounded by kChain <= C, the list's cursor is checked against C.
 //
@@ -470,6 +499,253 @@ __global__ void accum_match_stats_kernel(MArgs a) {
     a.stats[3] = 0ull;
 }
 
+// ---------------------------------------------------------------------------
+// label
+// ---------------------------------------------------------------------------
+constexpr uint32_t kNoSlot = ~0u;
+constexpr int kSources = KMC_CLASSIFY_MAX_SOURCES;
+static_assert(kSources == 32 && kSources <= kWave, "a label is one word, a score row half a wave");
+
+// the slot of `key` (hash h) in a table, by table_has' chain: from the key's slot to the
+// first empty slot, `chain` probes at most; kNoSlot: the table does not hold it
+__device__ __forceinline__ uint32_t table_slot(const unsigned long long *keys, uint32_t mask, uint32_t chain,
+                                               unsigned long long key, unsigned long long h) {
+    uint32_t i = (uint32_t)h & mask;
+    for (uint32_t step = 0; step < chain; ++step) {
+        const unsigned long long x = keys[i];
+        if (x == key) return i;
+        if (x == kFill) return kNoSlot;
+        i = (i + 1) & mask;
+    }
+    return kNoSlot;
+}
+
+// the windows of `pend` whose hash is below `limit`
+__device__ __forceinline__ uint32_t sampled_of(const unsigned long long (&key)[16], uint32_t pend, uint64_t seed,
+                                               unsigned long long limit) {
+    uint32_t cm = 0u;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) cm |= (uint32_t)(sketch_hash(key[j], seed) < limit) << j;
+    return pend & cm;
+}
+
+struct LArgs {
+    WalkArgs w;
+    uint64_t seed, maxh;
+    uint32_t j, bit;  // bit: 1 << source
+    const Header *hd;
+    const unsigned long long *keys;  // the active table: only read
+    uint32_t mask, chain;
+    uint32_t *labels;  // [C]
+};
+
+template <bool FWD, bool BIGK>
+__global__ __launch_bounds__(kBlock) void accum_label_kernel(LArgs a) {
+    __shared__ int64_t s_first;
+    const Walk W = walk_of(a.w);
+    bool all;
+    const unsigned long long limit = limit_of(a, &all);
+    for_each_piece(W, &s_first, [&](int64_t, int64_t ps, int64_t pe, int64_t rend) {
+        for_each_chunk<FWD, BIGK>(W, ps, pe, rend, KeyOf{}, [&](const unsigned long long(&key)[16], uint32_t pend) {
+            if (!pend) return;
+            const uint32_t sm = all ? pend : sampled_of(key, pend, a.seed, limit);
+            unsigned long long last = 0ull;
+            bool run = false;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                if (!((sm >> j) & 1u)) continue;
+                if (run && key[j] == last) continue;  // equal neighbours: one probe, one OR
+                last = key[j];
+                run = true;
+                const uint32_t at = table_slot(a.keys, a.mask, a.chain, last, sketch_hash(last, a.seed));
+                // (a stale reading of a word that has the bit only costs the atomic)
+                if (at != kNoSlot && !(a.labels[at] & a.bit))
+                    __hip_atomic_fetch_or(a.labels + at, a.bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        });
+    });
+}
+
+// ---------------------------------------------------------------------------
+// classify
+// ---------------------------------------------------------------------------
+#ifdef KMC_DIAG_HOOKS
+constexpr int kCutBlock = 64;  // two rows a round: a cut record takes several rounds
+#else
+constexpr int kCutBlock = 1024;
+#endif
+constexpr int kCutRows = kCutBlock / kSources;  // workspace rows a round of the fix-up reads
+
+struct CArgs {
+    MArgs m;
+    const uint32_t *labels;  // [C]
+    uint32_t ns, srcmask;    // the sources 1 .. 32 and the label bits below ns
+    uint32_t *best, *best_hits, *next_hits;  // [n], cleared to none
+    uint32_t *scores;                        // [n * ns], cleared, or null
+    // the pieces that are no whole record: row 2 u is wave u's first piece (its record
+    // began before the range), row 2 u + 1 its last (its record goes on after it)
+    long long *tags;  // [2 * waves] the row's record; negative: no row
+    uint32_t *rows;   // [2 * waves][kSources]
+    int64_t waves;
+};
+
+__device__ __forceinline__ uint32_t wave_max(uint32_t x) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) x = std::max(x, (uint32_t)__shfl_xor(x, off, kWave));
+    return x;
+}
+
+// Record r's results from its score row: v is score(r, lane), 0 in the lanes at or above
+// ns.  All 64 lanes of a wave call it.
+__device__ __forceinline__ void store_votes(const CArgs &a, int64_t r, uint32_t v, int lane) {
+    const uint32_t mx = wave_max(v);
+    const int b = __ffsll((unsigned long long)__ballot(v == mx)) - 1;  // the smallest source with the largest score
+    const uint32_t nx = wave_max(lane == b ? 0u : v);
+    if (a.scores && lane < (int)a.ns) a.scores[(uint64_t)r * a.ns + lane] = v;
+    if (lane == 0) {
+        a.best[r] = mx ? (uint32_t)b : KMC_CLASSIFY_NONE;
+        a.best_hits[r] = mx;
+        a.next_hits[r] = nx;  // (mx == 0: every score is 0)
+    }
+}
+
+template <bool FWD, bool BIGK>
+__global__ __launch_bounds__(kBlock) void accum_classify_kernel(CArgs a) {
+    __shared__ uint32_t s_row[kWavesPerBlock][kSources];  // a wave's score row; no other wave touches it
+    const MArgs &g = a.m;
+    const Walk W = wave_walk_of(g.w);
+    bool all;
+    const unsigned long long limit = limit_of(g, &all);
+    const uint32_t m = g.min_count > 1 ? g.min_count : 1u;
+    const int lane = threadIdx.x & (kWave - 1);
+    const bool first = lane == 0;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    uint32_t *row = s_row[wv];
+    if (lane < kSources) __hip_atomic_store(row + lane, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    unsigned long long tot_s = 0ull, tot_h = 0ull;
+    for_each_wave_piece(W, [&](int64_t r, int64_t ps, int64_t pe, int64_t rend, bool whole) {
+        uint32_t nv = 0u, ns = 0u, nh = 0u;
+        for_each_wave_chunk<FWD, BIGK>(W, ps, pe, rend, KeyOf{}, [&](const unsigned long long(&key)[16], uint32_t pend) {
+            if (!pend) return;
+            const uint32_t sm = all ? pend : sampled_of(key, pend, g.seed, limit);
+            // match's runs; a hit window adds its label to the lane's bit planes: plane p
+            // holds bit p of the count of every source among the chunk's 16 windows
+            uint32_t hm = 0u, lab = 0u, c0 = 0u, c1 = 0u, c2 = 0u, c3 = 0u, c4 = 0u;
+            unsigned long long last = 0ull;
+            bool run = false, hit = false;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                if (!((sm >> j) & 1u)) continue;
+                if (!(run && key[j] == last)) {
+                    last = key[j];
+                    const uint32_t at = table_slot(g.keys, g.mask, g.chain, last, sketch_hash(last, g.seed));
+                    hit = at != kNoSlot && g.counts[at] >= m;
+                    lab = hit ? a.labels[at] & a.srcmask : 0u;
+                    run = true;
+                }
+                hm |= (uint32_t)hit << j;
+                uint32_t carry = lab, t;
+                t = c0 & carry; c0 ^= carry; carry = t;
+                t = c1 & carry; c1 ^= carry; carry = t;
+                t = c2 & carry; c2 ^= carry; carry = t;
+                t = c3 & carry; c3 ^= carry; carry = t;
+                c4 ^= carry;
+            }
+            nv += __popc(pend);
+            ns += __popc(sm);
+            nh += __popc(hm);
+            for (uint32_t seen = c0 | c1 | c2 | c3 | c4; seen; seen &= seen - 1u) {  // the sources this lane saw
+                const int s = __ffs(seen) - 1;
+                const uint32_t cnt = ((c0 >> s) & 1u) | (((c1 >> s) & 1u) << 1) | (((c2 >> s) & 1u) << 2) |
+                                     (((c3 >> s) & 1u) << 3) | (((c4 >> s) & 1u) << 4);
+                __hip_atomic_fetch_add(row + s, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            }
+        });
+        tot_s += ns;
+        tot_h += nh;
+        const uint32_t v = g.windows ? wave_sum(nv) : 0u, s = g.sampled ? wave_sum(ns) : 0u, h = wave_sum(nh);
+        if (first) {
+            credit(g.windows, r, v, whole);
+            credit(g.sampled, r, s, whole);
+            credit(g.hits, r, h, whole);
+        }
+        if (whole && h == 0u) return;  // no vote: the cleared outputs stand
+        // the wave's row, taken back by its own lanes (a wave's LDS operations keep their order)
+        uint32_t score = 0u;
+        if (h) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            if (lane < kSources) {
+                score = __hip_atomic_load(row + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                __hip_atomic_store(row + lane, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        }
+        if (whole) {
+            store_votes(a, r, score, lane);
+        } else {
+            const int64_t u = (int64_t)blockIdx.x * kWavesPerBlock + wv;  // < a.waves
+            const int64_t at = 2 * u + (ps > W.idx[r] ? 0 : 1);
+            if (lane < kSources) a.rows[at * kSources + lane] = score;
+            if (first) a.tags[at] = (long long)r;
+        }
+    });
+    if (g.stats) {  // one add per wave and word
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+            tot_s += __shfl_xor(tot_s, off, kWave);
+            tot_h += __shfl_xor(tot_h, off, kWave);
+        }
+        if (first && tot_s) atomicAdd(g.stats + 2, tot_s);
+        if (first && tot_h) atomicAdd(g.stats + 3, tot_h);
+    }
+}
+
+// The cut records.  A record's first piece is the last piece of its wave (tag 2 u + 1);
+// its other pieces are the first pieces of the waves after it (tags 2 w, w > u), with
+// nothing but rowless waves in between, and the first row of another record ends them.
+// One workgroup per tagged last row: kCutRows rows a round, kSources lanes a row.
+__global__ __launch_bounds__(kCutBlock) void classify_cut_kernel(CArgs a) {
+    __shared__ uint32_t s_tot[kSources];
+    const int tid = threadIdx.x, src = tid & (kSources - 1), q = tid / kSources;
+    for (int64_t u = blockIdx.x; u < a.waves; u += gridDim.x) {
+        const long long r = a.tags[2 * u + 1];
+        if (r < 0 || r >= a.m.w.n) continue;  // (workgroup-uniform, before this round's barriers)
+        if (tid < kSources) s_tot[tid] = a.rows[(2 * u + 1) * kSources + tid];
+        __syncthreads();
+        uint32_t mine = 0u;
+        for (int64_t b = u + 1; b < a.waves; b += kCutRows) {
+            const int64_t w = b + q;
+            const long long t = w < a.waves ? a.tags[2 * w] : -1ll;
+            if (t == r) mine += a.rows[2 * w * kSources + src];
+            if (__syncthreads_or(t >= 0 && t != r)) break;
+        }
+        if (mine) atomicAdd(&s_tot[src], mine);
+        __syncthreads();
+        if (tid < kWave) store_votes(a, r, tid < kSources ? s_tot[tid] : 0u, tid);
+        __syncthreads();  // before the next round's totals
+    }
+}
+
+struct CLayout {
+    long long *tags;
+    uint32_t *rows;
+    size_t bytes;
+};
+
+// two rows per wave of a launch of G workgroups
+inline CLayout classify_layout(void *base, int G) {
+    const size_t rows = 2 * (size_t)G * kWavesPerBlock;
+    Carver c(base);
+    CLayout l;
+    l.tags = c.take<long long>(rows);
+    l.rows = c.take<uint32_t>(rows * kSources);
+    l.bytes = c.total();
+    return l;
+}
+
+DeviceCache classify_ws;
+
 inline unsigned slot_grid(uint64_t C) {
     const uint64_t b = (C + kSlotBlock - 1) / kSlotBlock;
     return (unsigned)(b < 4096 ? b : 4096);
@@ -491,6 +767,9 @@ struct kmc_sketch_accum {
     uint64_t N;  // bytes added
     uint32_t j;  // the threshold's level: it never falls
     int active;  // the table the adds go to
+    // the sources of the active table's keys (kmc_label_accum)
+    uint32_t *labels;  // [C], a second allocation made by the first label call; null before it
+    bool labelled;     // the labels describe the table as it stands
 };
 
 namespace {
@@ -524,6 +803,7 @@ int start_over(kmc_sketch_accum *a, hipStream_t st) {
     a->N = 0;
     a->j = 0;
     a->active = 0;
+    a->labelled = false;
     return KMC_OK;
 }
 
@@ -548,6 +828,8 @@ extern "C" int kmc_sketch_accum_create(uint32_t sketch_size, int k, unsigned fla
     a->flags = flags;
     a->seed = seed;
     a->base = nullptr;
+    a->labels = nullptr;
+    a->labelled = false;
     if (hipMalloc(&a->base, layout(nullptr, a->s, a->lg).bytes) != hipSuccess) {
         (void)hipGetLastError();
         delete a;
@@ -597,6 +879,7 @@ extern "C" int kmc_sketch_accum_add(kmc_sketch_accum *a, const char *data, const
     });
     if (hipError_t he = hipGetLastError()) return (int)he;
     a->N = N;
+    a->labelled = false;  // the labels described the table before these records
     return KMC_OK;
 }
 
@@ -695,6 +978,121 @@ extern "C" int kmc_match_from_accum(kmc_sketch_accum *a, const char *data, const
     return (int)hipGetLastError();
 }
 
+extern "C" int kmc_label_accum(kmc_sketch_accum *a, const char *data, const int64_t *indices, uint64_t num_seqs,
+                                      uint64_t data_bytes, uint32_t source, hipStream_t stream) {
+    if (!a || source >= KMC_CLASSIFY_MAX_SOURCES || num_seqs > kMaxSeqs) return KMC_ERR_INVALID_ARG;
+    if (num_seqs > 0 && (!walk_ptrs_ok(data, indices, data_bytes) || !walk_sizes_ok(num_seqs, data_bytes)))
+        return KMC_ERR_INVALID_ARG;
+    const size_t C = (size_t)1 << a->lg;
+    if (!a->labels && hipMalloc(reinterpret_cast<void **>(&a->labels), C * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        a->labels = nullptr;
+        return KMC_ERR_NOMEM;
+    }
+    if (!a->labelled) {  // the first label of the table as it stands
+        if (hipError_t he = hipMemsetAsync(a->labels, 0, C * 4, stream)) return (int)he;
+        a->labelled = true;
+    }
+    if (num_seqs == 0) return KMC_OK;
+    int device = 0, cus = 0;
+    if (int e = current_device_cus(&device, &cus)) return e;
+    const Table T = table_of(a, a->active);
+    LArgs g;
+    g.w = walk_args(data, indices, num_seqs, data_bytes, a->k, a->flags, cus);
+    g.seed = a->seed;
+    g.maxh = max_hash(a->j);
+    g.j = a->j;
+    g.bit = 1u << source;
+    g.hd = a->L.hd;
+    g.keys = T.keys;
+    g.mask = T.mask;
+    g.chain = T.chain;
+    g.labels = a->labels;
+    for_walk(a->flags, a->k, [&](auto fwd, auto big) {
+        hipLaunchKernelGGL((accum_label_kernel<decltype(fwd)::value, decltype(big)::value>), dim3((unsigned)g.w.G),
+                           dim3(kBlock), 0, stream, g);
+    });
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t kmc_classify_workspace_size(uint64_t num_seqs, uint64_t data_bytes, uint32_t num_sources, int device) {
+    if (!walk_sizes_ok(num_seqs, data_bytes) || num_sources < 1 || num_sources > KMC_CLASSIFY_MAX_SOURCES || device < 0)
+        return 0;
+    int cus = 0;  // (the arguments are checked before any HIP call)
+    if (device_cus(device, &cus)) return 0;
+    return classify_layout(nullptr, walk_groups(data_bytes, cus)).bytes;
+}
+
+extern "C" int kmc_classify_from_accum(kmc_sketch_accum *a, const char *data, const int64_t *indices, uint64_t num_seqs,
+                                       uint64_t data_bytes, uint32_t num_sources, uint32_t min_count, uint32_t *windows,
+                                       uint32_t *sampled, uint32_t *hits, uint32_t *best, uint32_t *best_hits,
+                                       uint32_t *next_hits, uint32_t *scores, uint64_t *stats, void *workspace,
+                                       size_t workspace_bytes, hipStream_t stream) {
+    if (!a || !hits || num_seqs > kMaxSeqs) return KMC_ERR_INVALID_ARG;
+    if (!walk_ptrs_ok(data, indices, data_bytes) || !walk_sizes_ok(num_seqs, data_bytes)) return KMC_ERR_INVALID_ARG;
+    if (!best || !best_hits || !next_hits) return KMC_ERR_INVALID_ARG;
+    if (num_sources < 1 || num_sources > KMC_CLASSIFY_MAX_SOURCES || !a->labelled) return KMC_ERR_INVALID_ARG;
+    int device = 0, cus = 0;
+    if (int e = current_device_cus(&device, &cus)) return e;
+    const int G = walk_groups(data_bytes, cus);
+    if (workspace) {
+        if (workspace_bytes < classify_layout(nullptr, G).bytes) return KMC_ERR_WORKSPACE;
+        if (reinterpret_cast<uintptr_t>(workspace) & 7u) return KMC_ERR_ALIGNMENT;
+    }
+    CArgs c;
+    MArgs &g = c.m;
+    g.seed = a->seed;
+    g.maxh = max_hash(a->j);
+    g.j = a->j;
+    g.min_count = min_count;
+    g.hd = a->L.hd;
+    g.keys = a->L.keys[a->active];
+    g.counts = a->L.counts[a->active];
+    const Table T = table_of(a, a->active);
+    g.mask = T.mask;
+    g.chain = T.chain;
+    g.windows = windows;
+    g.sampled = sampled;
+    g.hits = hits;
+    g.stats = reinterpret_cast<unsigned long long *>(stats);
+    g.w = WalkArgs{};
+    if (stats) {
+        hipLaunchKernelGGL(accum_match_stats_kernel, dim3(1), dim3(1), 0, stream, g);
+        if (hipError_t he = hipGetLastError()) return (int)he;
+    }
+    if (num_seqs == 0) return KMC_OK;
+    CLayout l;
+    if (int e = bind_layout(classify_ws, device, workspace, workspace_bytes, 8,
+                            [&](void *b) { return classify_layout(b, G); }, &l))
+        return e;
+    g.w = walk_args(data, indices, num_seqs, data_bytes, a->k, a->flags, cus);
+    c.labels = a->labels;
+    c.ns = num_sources;
+    c.srcmask = num_sources == 32 ? ~0u : (1u << num_sources) - 1u;
+    c.best = best;
+    c.best_hits = best_hits;
+    c.next_hits = next_hits;
+    c.scores = scores;
+    c.tags = l.tags;
+    c.rows = l.rows;
+    c.waves = (int64_t)G * kWavesPerBlock;
+    const size_t n4 = (size_t)num_seqs * 4;
+    for (uint32_t *out : {windows, sampled, hits, best_hits, next_hits})
+        if (out)
+            if (hipError_t he = hipMemsetAsync(out, 0, n4, stream)) return (int)he;
+    if (hipError_t he = hipMemsetAsync(best, 0xFF, n4, stream)) return (int)he;  // KMC_CLASSIFY_NONE
+    if (scores)
+        if (hipError_t he = hipMemsetAsync(scores, 0, n4 * num_sources, stream)) return (int)he;
+    if (hipError_t he = hipMemsetAsync(l.tags, 0xFF, 2 * (size_t)c.waves * sizeof(long long), stream)) return (int)he;
+    for_walk(a->flags, a->k, [&](auto fwd, auto big) {
+        hipLaunchKernelGGL((accum_classify_kernel<decltype(fwd)::value, decltype(big)::value>), dim3((unsigned)g.w.G),
+                           dim3(kBlock), 0, stream, c);
+    });
+    if (hipError_t he = hipGetLastError()) return (int)he;
+    hipLaunchKernelGGL(classify_cut_kernel, dim3((unsigned)c.waves), dim3(kCutBlock), 0, stream, c);
+    return (int)hipGetLastError();
+}
+
 extern "C" int kmc_sketch_accum_reset(kmc_sketch_accum *a, hipStream_t stream) {
     if (!a) return KMC_ERR_INVALID_ARG;
     return start_over(a, stream);
@@ -703,5 +1101,6 @@ extern "C" int kmc_sketch_accum_reset(kmc_sketch_accum *a, hipStream_t stream) {
 extern "C" void kmc_sketch_accum_free(kmc_sketch_accum *a) {
     if (!a) return;
     if (a->base) (void)hipFree(a->base);
+    if (a->labels) (void)hipFree(a->labels);
     delete a;
 }

@@ -277,6 +277,12 @@ def _load(path):
     L.kmc_sketch_accum_free.restype = None
     L.kmc_spectrum_from_accum.argtypes = [_P, ctypes.c_uint32, _P, _P, _P]
     L.kmc_match_from_accum.argtypes = [_P, _P, _P, _U64, _U64, ctypes.c_uint32, _P, _P, _P, _P, _P]
+    L.kmc_label_accum.argtypes = [_P, _P, _P, _U64, _U64, ctypes.c_uint32, _P]
+    L.kmc_classify_workspace_size.restype = ctypes.c_size_t
+    L.kmc_classify_workspace_size.argtypes = [_U64, _U64, ctypes.c_uint32, ctypes.c_int]
+    L.kmc_classify_from_accum.argtypes = [_P, _P, _P, _U64, _U64, ctypes.c_uint32, ctypes.c_uint32, _P, _P, _P, _P, _P,
+                                          _P, _P, _P, _P, ctypes.c_size_t, _P]
+    L.kmc_classify_select.argtypes = [_P, _P, _P, _P, _U64, ctypes.c_uint32, ctypes.c_uint32, _P, _P, _P]
     L.kmc_spectrum_summarize.argtypes = [_P, ctypes.c_uint32, _U64, ctypes.POINTER(SpectrumSummary)]
     L.minKmeres2_hip.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.kmc_count_canonical_hash.argtypes = [_P, _P, _U64, ctypes.c_int, ctypes.c_uint, _P, _P, _U64, _P,
@@ -988,6 +994,55 @@ class SketchAccum:
                "kmc_match_from_accum")
         return win, smp, hit, st
 
+    def label(self, data, indices, source, data_bytes=None, stream=None):
+        """kmc_label_accum: the k-mers of the records (data, indices: as add) that
+        are in the set get bit `source` (0 .. 31) in their label.  All adds come first:
+        an add of records or a reset drops the labels.  It leaves the set as it is."""
+        h = self._handle()
+        n = int(indices.numel() - 1)
+        if data_bytes is None:
+            data_bytes = data.numel()
+        _check(self._lib.kmc_label_accum(h, _dptr(data), _dptr(indices), n, int(data_bytes), int(source),
+                                                _stream(stream)), "kmc_label_accum")
+
+    def classify(self, data, indices, num_sources, min_count=1, windows=True, sampled=True, scores=False, stats=True,
+                 data_bytes=None, workspace=None, out=None, stream=None):
+        """kmc_classify_from_accum: match() with the votes of the labelled sources.
+        Returns (windows, sampled, hits, best, best_hits, next_hits: int32 [n] holding
+        uint32 numbers; scores: int32 [n, num_sources] or None; stats int64 [4]).  best is
+        the smallest source with the most hit windows, CLASSIFY_NONE (-1 as int32) when
+        no source has one; best_hits its score and next_hits the runner-up's.  `windows`,
+        `sampled`, `scores`, `stats`: as match's; `out`: the caller's own (hits, best,
+        best_hits, next_hits); `workspace`: a tensor of classify_workspace_size() bytes,
+        None for the library's own."""
+        import torch
+        h = self._handle()
+        n = int(indices.numel() - 1)
+        ns = int(num_sources)
+        if data_bytes is None:
+            data_bytes = data.numel()
+        with _on(stream):
+            dv = torch.device("cuda", torch.cuda.current_device())
+
+            def take(want, shape, dtype):
+                if isinstance(want, torch.Tensor):
+                    return want
+                return torch.empty(shape, dtype=dtype, device=dv) if want else None
+            n0 = max(n, 0)
+            win, smp = take(windows, n0, torch.int32), take(sampled, n0, torch.int32)
+            hit, best, bh, nh = out if out is not None else [take(True, n0, torch.int32) for _ in range(4)]
+            sc = take(scores, (n0, max(ns, 0)), torch.int32)
+            st = take(stats, 4, torch.int64)
+            # (no record: an empty tensor has no address, and the library refuses null outputs; nothing is written there)
+            spare = torch.empty(1, dtype=torch.int32, device=dv) if n0 == 0 else None
+            at = [t if t.numel() else spare for t in (hit, best, bh, nh)]
+        ws, ws_bytes = _ws(workspace)
+        _check(self._lib.kmc_classify_from_accum(h, _dptr(data), _dptr(indices), n, int(data_bytes), ns, int(min_count),
+                                                 _dptr(win), _dptr(smp), _dptr(at[0]), _dptr(at[1]), _dptr(at[2]),
+                                                 _dptr(at[3]), _dptr(sc) if sc is not None and sc.numel() else None,
+                                                 _dptr(st), ws, ws_bytes, _stream(stream)), "kmc_classify_from_accum")
+        return win, smp, hit, best, bh, nh, sc, st
+
     def reset(self, stream=None):
         _check(self._lib.kmc_sketch_accum_reset(self._handle(), _stream(stream)), "kmc_sketch_accum_reset")
 
@@ -1069,6 +1124,35 @@ def match_select(sampled, hits, min_hits=1, min_fraction=0.0, count=True, out=No
     _check(lib().kmc_match_select(_dptr(sampled) if n else None, _dptr(hits) if n else None, n, int(min_hits),
                                   float(min_fraction), _dptr(keep) if n else None, _dptr(kept), _stream(stream)),
            "kmc_match_select")
+    return keep, kept
+
+
+CLASSIFY_MAX_SOURCES = 32
+CLASSIFY_NONE = 0xFFFFFFFF
+
+
+def classify_workspace_size(num_seqs, data_bytes, num_sources, device=0):
+    return int(lib().kmc_classify_workspace_size(int(num_seqs), int(data_bytes), int(num_sources), int(device)))
+
+
+def classify_select(listed, best, best_hits, next_hits, source, min_margin=1, count=True, out=None, stream=None):
+    """kmc_classify_select: keep[r] = listed[r] != 0 and best[r] == source and best_hits[r]
+    - next_hits[r] >= min_margin, the rule of `kmc --recruit --classify`, as int32 [n] of
+    ones and zeros on the device.  listed (match_select's keep) may be None: every record;
+    `out` may be listed itself.  Returns (keep, num_kept int64 [1] or None)."""
+    import torch
+    n = int(best.numel())
+    with _on(stream):
+        dv = torch.device("cuda", torch.cuda.current_device())
+        keep = out if out is not None else torch.empty(n, dtype=torch.int32, device=dv)
+        if isinstance(count, torch.Tensor):
+            kept = count
+        else:
+            kept = torch.empty(1, dtype=torch.int64, device=dv) if count else None
+    _check(lib().kmc_classify_select(_dptr(listed) if n else None, _dptr(best) if n else None,
+                                     _dptr(best_hits) if n else None, _dptr(next_hits) if n else None, n, int(source),
+                                     int(min_margin), _dptr(keep) if n else None, _dptr(kept), _stream(stream)),
+           "kmc_classify_select")
     return keep, kept
 
 

@@ -971,6 +971,79 @@ KMC_API int kmc_match_from_accum(kmc_sketch_accum *a, const char *data, const in
                                  uint32_t *hits, uint64_t *stats, hipStream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* Telling matched records apart by source: a label on the accumulator's k-mer set and
+ * per-record votes (read binning, depletion with a host and a target, contamination
+ * reports).  A source is one of up to KMC_CLASSIFY_MAX_SOURCES = 32 sequence sets,
+ * numbered from 0.  A label is a uint32 bitmask per slot of the active table: bit g
+ * means "source g holds this key".
+ *
+ * kmc_label_accum: data, indices, num_seqs, data_bytes as kmc_sketch_accum_add.
+ * Every valid window that is sampled (all, or hash < limit; both exactly those of
+ * kmc_sketch_accum_finish) is looked up in the active table by kmc_match_from_accum's
+ * probe, and where its key is found the slot's label takes an atomic OR of
+ * 1u << source.  A key below limit that was added is in the table, so the label of
+ * every sampled window is exact.
+ *   Read-only  counts, keys and the header are only read: finish, spectrum and match
+ *              give the same bits with and without label calls in between, and
+ *              labelling a source twice is labelling it once.
+ *   Storage    4 C bytes in a second allocation that the handle owns, made by the first
+ *              label call (that call allocates; everything after it is asynchronous on
+ *              `stream`) and released by kmc_sketch_accum_free.
+ *              kmc_sketch_accum_device_bytes is the size of a handle never labelled.
+ *   Lifetime   the labels describe the table as it stands: a kmc_sketch_accum_add of at
+ *              least one record and a kmc_sketch_accum_reset drop them (host state, no
+ *              device work), and the first label call after that clears the array on
+ *              its stream.  So the order is: all adds, then all labels, then classify.
+ * KMC_ERR_INVALID_ARG, judged before any device is touched: a null handle, source >= 32,
+ * num_seqs above 2^40, and with num_seqs > 0 null indices, null data with data_bytes >
+ * 0, data_bytes of 2^62 or more.  KMC_ERR_NOMEM when the array cannot be allocated.
+ * num_seqs == 0: KMC_OK, and the labels are established (allocated and cleared) all the
+ * same.  (The name follows kmc_match_from_accum's note: the six kmc_sketch_accum_* functions
+ * are the handle's life cycle.)
+ *
+ * kmc_classify_from_accum: kmc_match_from_accum with the votes.  windows, sampled, hits
+ * and stats are bit for bit kmc_match_from_accum's for the same arguments (windows and
+ * sampled may be NULL); a hit does not depend on the label.
+ *   score(r, g)  for g < num_sources: the hit windows of record r whose label has bit g.
+ *              Label bits at or above num_sources are ignored.
+ *   best       device uint32[num_seqs]: the smallest g with the largest score when that
+ *              score is above 0, else KMC_CLASSIFY_NONE
+ *   best_hits  device uint32[num_seqs]: that score, or 0
+ *   next_hits  device uint32[num_seqs]: the largest score among the other sources (0
+ *              when num_sources == 1); next_hits == best_hits is a tie
+ *   scores     may be NULL; else device uint32[num_seqs * num_sources], row r holding
+ *              score(r, .).  best, best_hits and next_hits are the same bits with and
+ *              without it.
+ *              Every entry of every given output is overwritten; nothing a former call
+ *              left in the outputs or the workspace is read.
+ *   workspace  device scratch of kmc_classify_workspace_size() bytes, 8-byte aligned
+ *              (KMC_ERR_WORKSPACE when smaller, then KMC_ERR_ALIGNMENT), or NULL for a
+ *              library-owned buffer under kmc_pair_distances' rule (NULL-workspace calls
+ *              on a device must not overlap).  It holds the partial score rows of the
+ *              records cut between the launch's waves, two tagged rows of 32 words per
+ *              wave: a few MB at most, growing with data_bytes up to the device's width
+ *              and not at all with num_seqs * num_sources.  The query takes host numbers
+ *              and the device's CU count only and returns 0 for arguments the call
+ *              refuses.
+ * Asynchronous on `stream`, no host read-back; the launches depend on the host arguments
+ * and the handle's host state only; the result does not depend on where the launch cuts
+ * the records.  It only reads the accumulator.  KMC_ERR_INVALID_ARG, judged before any
+ * device is touched: the conditions of kmc_match_from_accum; a null best, best_hits or
+ * next_hits; num_sources outside 1..32; a handle whose labels are not established (no
+ * label call since create, the last add of records or the last reset).  num_seqs == 0:
+ * KMC_OK, nothing is written except stats when given. */
+#define KMC_CLASSIFY_MAX_SOURCES 32
+#define KMC_CLASSIFY_NONE UINT32_MAX
+KMC_API int kmc_label_accum(kmc_sketch_accum *a, const char *data, const int64_t *indices, uint64_t num_seqs,
+                                   uint64_t data_bytes, uint32_t source, hipStream_t stream);
+KMC_API size_t kmc_classify_workspace_size(uint64_t num_seqs, uint64_t data_bytes, uint32_t num_sources, int device);
+KMC_API int kmc_classify_from_accum(kmc_sketch_accum *a, const char *data, const int64_t *indices, uint64_t num_seqs,
+                                    uint64_t data_bytes, uint32_t num_sources, uint32_t min_count,
+                                    uint32_t *windows, uint32_t *sampled, uint32_t *hits,
+                                    uint32_t *best, uint32_t *best_hits, uint32_t *next_hits, uint32_t *scores,
+                                    uint64_t *stats, void *workspace, size_t workspace_bytes, hipStream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* Tracing (the reference times step 1 with cudaEvents, main.cu:262-300): when set,
  * every following dense count call on this host thread records `before` right
  * before its histogram kernel and `after` right after it, on the call's stream,
@@ -1242,6 +1315,20 @@ KMC_API int kmc_select_records(const char *src, const int64_t *offsets, uint64_t
  * with num_seqs > 0 and min_fraction above 0, and for num_seqs above 2^40. */
 KMC_API int kmc_match_select(const uint32_t *sampled, const uint32_t *hits, uint64_t num_seqs, uint32_t min_hits,
                      double min_fraction, uint32_t *keep, uint64_t *num_kept, hipStream_t stream);
+
+/* kmc_classify_select: the rule by which `kmc --recruit --classify` assigns a record to
+ * a source, on the device:
+ *   keep[r] = listed[r] != 0 && best[r] == source && best_hits[r] - next_hits[r] >= min_margin
+ * written as 1 or 0.  listed is kmc_match_select's keep and may be NULL, meaning all
+ * ones; best, best_hits and next_hits are kmc_classify_from_accum's; keep may be the
+ * same array as listed.  num_kept is a device uint64 (the number of ones) and may be
+ * NULL.  min_margin 1 assigns a tie to nobody, 0 to the smaller index.  Asynchronous on
+ * `stream`, no workspace.  KMC_ERR_INVALID_ARG, before any device is touched, for a
+ * source >= 32, for a null best, best_hits, next_hits or keep with num_seqs > 0, and for
+ * num_seqs above 2^40. */
+KMC_API int kmc_classify_select(const uint32_t *listed, const uint32_t *best, const uint32_t *best_hits,
+                                const uint32_t *next_hits, uint64_t num_seqs, uint32_t source, uint32_t min_margin,
+                                uint32_t *keep, uint64_t *num_kept, hipStream_t stream);
 
 #ifdef __cplusplus
 }

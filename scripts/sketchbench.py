@@ -28,7 +28,9 @@ With --cluster: kmc_sketch_cluster beside kmc_sketch_distances on the same rows,
 rows and 64-member clusters of near-identical rows (profiles/pr_sketch_cluster.jsonl).
 With --links: kmc_sketch_links, count-only and with a fitting capacity, beside
 kmc_sketch_distances with counts and kmc_sketch_cluster on those rows
-(profiles/pr_sketch_links.jsonl).
+(profiles/pr_sketch_links.jsonl).  With --classify: kmc_classify_from_accum beside
+kmc_match_from_accum, kmc_label_accum beside kmc_sketch_accum_add
+(profiles/pr_classify.jsonl).
 
 Inputs (synthetic, generated on the device):
   iid          8 x 50 Mbase independent records, k = 31
@@ -661,6 +663,103 @@ def match_main(args, dev):
     other.close()
 
 
+def classify_main(args, dev):
+    """--classify: kmc_classify_from_accum beside kmc_match_from_accum on --match's two
+    workloads (2.6 M reads of 150 bases, 8 x 50 Mbase; k = 21, a table of 2^26 slots filled
+    from 100 Mbase, half of each input drawn from it), with 2, 8 and 32 sources, each with
+    and without `scores`; the set is cut into as many equal pieces as there are sources and
+    piece g labelled g, so a hit window votes for one source.  And kmc_label_accum
+    of the whole set as one source beside kmc_sketch_accum_add of it (reset timed alone and
+    subtracted).  windows, sampled, hits and stats are asserted equal to the match's, the
+    votes with and without scores to each other and best_hits to the scores' largest,
+    before anything is timed; HIP events, 2 warm-ups, median of 7."""
+    k, lg, runs = 21, 26, 7
+    set_len = max(int(50_000_000 * args.scale), 5000)
+    sdata = torch.empty(2 * (set_len + 1), dtype=torch.uint8, device=dev)
+    kmc.synth_fill(sdata, 2, set_len, 0x5EED0008)
+    sidx = torch.from_numpy(kmc.synth_indices(2, set_len)).to(dev)
+    acc, other = kmc.SketchAccum(1, k, log2_slots=lg), kmc.SketchAccum(1, k, log2_slots=lg)
+    acc.add(sdata, sidx)
+
+    def label_pieces(ns):
+        """piece g of the set's bytes is source g (a record's terminator ends a window)"""
+        cuts = np.linspace(0, sdata.numel(), ns + 1).astype(np.int64)
+        acc.reset()
+        acc.add(sdata, sidx)
+        for g in range(ns):
+            acc.label(sdata, torch.from_numpy(cuts[g:g + 2].copy()).to(dev), g)
+
+    def reads():
+        n, ln = max(int(2_600_000 * args.scale), 64), 150
+        d = torch.empty(n * (ln + 1), dtype=torch.uint8, device=dev)
+        kmc.synth_fill(d, n, ln, 0x5EED0010)
+        step = max((sdata.numel() - ln) // (n // 2 + 1), 1)
+        d.view(n, ln + 1)[::2, :ln] = sdata.unfold(0, ln, step)[:(n + 1) // 2]
+        return d, torch.from_numpy(kmc.synth_indices(n, ln)).to(dev), n, ln
+
+    def long_records():
+        n, ln = 8, set_len
+        d = torch.empty(n * (ln + 1), dtype=torch.uint8, device=dev)
+        kmc.synth_fill(d, n, ln, 0x5EED0011)
+        d.view(n, ln + 1)[::2] = sdata.view(2, ln + 1).repeat(2, 1)
+        return d, torch.from_numpy(kmc.synth_indices(n, ln)).to(dev), n, ln
+
+    def reset_and_add():
+        other.reset()
+        other.add(sdata, sidx)
+    other.reset()
+    other.add(sdata, sidx)
+    turn = [0]
+
+    def label_next():  # a new source every call: every key's word takes the atomic OR
+        other.label(sdata, sidx, turn[0] % 32)
+        turn[0] += 1
+    label = {"set_bases": 2 * set_len, "k": k, "log2_slots": lg,
+             "kmc_label_accum": timed(label_next, runs),
+             "reset_and_add": timed(reset_and_add, runs),
+             "kmc_sketch_accum_reset": timed(lambda: other.reset(), runs)}
+    label["kmc_sketch_accum_add_ms"] = label["reset_and_add"]["ms_median"] - label["kmc_sketch_accum_reset"]["ms_median"]
+    label["label_over_add"] = label["kmc_label_accum"]["ms_median"] / label["kmc_sketch_accum_add_ms"]
+    with open(args.out, "a") as out:
+        out.write(json.dumps(label) + "\n")
+        print(json.dumps(label), flush=True)
+        for name, make in (("read_set", reads), ("long_records", long_records)):
+            d, i, n, ln = make()
+            ws = torch.empty(kmc.classify_workspace_size(n, d.numel(), 32, torch.cuda.current_device()),
+                             dtype=torch.uint8, device=dev)
+            plain = acc.match(d, i)
+            match_ms = timed(lambda: acc.match(d, i), runs)
+            for ns in (2, 8, 32):
+                label_pieces(ns)
+                full = acc.classify(d, i, ns, scores=True, workspace=ws)
+                bare = acc.classify(d, i, ns, workspace=ws)
+                torch.cuda.synchronize()
+                assert all(torch.equal(a, b) for a, b in zip(full[:3] + (full[7],), plain)), (name, ns)
+                assert all(torch.equal(a, b) for a, b in zip(full[:6], bare[:6])), (name, ns)
+                assert torch.equal(full[6].max(dim=1).values, full[4]), (name, ns)
+                # (a k-mer over a cut has no label, one that two pieces hold has two: a few in 10^8)
+                votes, hits = int(full[6][::2].long().sum().item()), int(full[2][::2].long().sum().item())
+                assert abs(votes - hits) <= 0.01 * hits, (name, ns, votes, hits)
+                rec = {
+                    "input": name, "records": n, "record_len": ln, "k": k, "log2_slots": lg, "set_bases": 2 * set_len,
+                    "num_sources": ns, "workspace_bytes": ws.numel(), "outputs_equal_match": True,
+                    "assigned": int((full[4] > full[5]).sum().item()),
+                    "kmc_match_from_accum": match_ms,
+                    "kmc_classify_from_accum": timed(lambda: acc.classify(d, i, ns, workspace=ws), runs),
+                    "kmc_classify_from_accum_scores": timed(lambda: acc.classify(d, i, ns, scores=True, workspace=ws), runs),
+                }
+                rec["classify_over_match"] = rec["kmc_classify_from_accum"]["ms_median"] / match_ms["ms_median"]
+                rec["classify_scores_over_match"] = rec["kmc_classify_from_accum_scores"]["ms_median"] / match_ms["ms_median"]
+                out.write(json.dumps(rec) + "\n")
+                out.flush()
+                print(json.dumps(rec), flush=True)
+                del full, bare
+            del d, i, plain, ws
+            torch.cuda.empty_cache()
+    acc.close()
+    other.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(HERE), "profiles", "pr_sketch.jsonl"))
@@ -710,8 +809,15 @@ def main():
                          "kmc_sketch_accum_add and kmc_sketch_screen_count on the same records (outputs asserted equal "
                          "to a second call's; 2 warm-ups, median of 5); appends to --out "
                          "profiles/pr_accum_match.jsonl")
+    ap.add_argument("--classify", action="store_true",
+                    help="time kmc_classify_from_accum with 2, 8 and 32 sources, with and without scores, beside "
+                         "kmc_match_from_accum on --match's two workloads, and kmc_label_accum beside "
+                         "kmc_sketch_accum_add (outputs asserted equal to the match's; 2 warm-ups, median of 7); "
+                         "appends to --out profiles/pr_classify.jsonl")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.classify:
+        return classify_main(args, dev)
     if args.match:
         return match_main(args, dev)
     if args.links:
